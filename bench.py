@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- CT slices/s of the full dual-domain partial-diffusion sample on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the steps one by one).  --full
+adds everything else the line can carry, each piece behind its own --no-* switch: the shader clock under the last warm-up
+step, the dominant kernel's roofline and the per-class kernel figures, the B=1 latency / drop-in / alt-shape / img-only legs,
+the alt_modes legs and the CPU baselines.  --dump-outputs DIR writes the gathered output of the last timed step as
+DIR/denoised.npy (float32; inputs, weights and noise draws are seeded, so the same arguments give the same inputs).
 
 N>1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set: the driver's form) this process IS a rank; a bare
 `python bench.py --gpus N` starts its own ranks -- the parent, before it has imported anything that touches the GPU, runs
@@ -106,7 +112,37 @@ def parse():
                          "config C2 (B x 512x512 low-dose images, image-domain UNet only, t_start_img, no ultra pass); reported "
                          "beside the headline as `img_only`")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the B=1 latency and alt-shape legs (N=1 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: clock probe, rooflines and kernel classes, extra legs, alt_modes, CPU baselines "
+                         "(each still switched off by its --no-* option).  Without it all of them are off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the gathered output of the last one as DIR/denoised.npy (float32; a seeded "
+                         "sample of whole slices above %d MB)" % (DUMP_LIMIT_BYTES // 10**6))
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_alt = args.no_extra_legs = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float64 stays float64).  When they hold more than `limit`
+    bytes in all, each keeps a fixed seeded sample of whole slices (its leading axis), in order, and the kept slice ids go
+    beside it as out_dir/<name>_slice_ids.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = limit - 8 * sum(a.shape[0] for a in arrays.values())          # (room for the slice-id files)
+    for name, a in arrays.items():
+        if total > limit:
+            k = max(1, int(budget * a.nbytes / total) // (a.nbytes // a.shape[0]))
+            ids = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            np.save(os.path.join(out_dir, name + "_slice_ids.npy"), ids.astype(np.float64))
+            a = np.ascontiguousarray(a[ids])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def spawn_ranks(n):
@@ -414,6 +450,8 @@ def main():
     own_ms = idist.gather_over_ranks(own_mean, device)
     per_step = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
     elapsed = idist.max_over_ranks(elapsed, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"denoised": out.cpu().numpy()})      # (rank 0 holds every rank's slices)
     roofline = None
     extra = {}
     if prof:
