@@ -2,6 +2,7 @@
 the golden vectors of the imported reference.  Tolerances are absolute unless noted and written
 next to each check; north_star: 1e-5 max-abs on the FBP index map, 1e-4 relative PSNR end to end."""
 import os
+import time
 
 import numpy as np
 import pytest
@@ -14,6 +15,7 @@ from oracle import fbp as of         # noqa: E402
 from oracle import unet as ou        # noqa: E402
 from ipdm_pytorch_amd import synth   # noqa: E402
 from tests._oracle_pool import host_threads   # noqa: E402
+from tests import _accuracy as acc             # noqa: E402
 from tests.golden.cases import SMALL_CFGS, SMALL_SHAPES, LOOP_CFG, LOOP_CASES, noise_feed  # noqa: E402
 
 DEV = "cuda:0"
@@ -281,13 +283,18 @@ def test_guidance_map_and_lambda_ratio(gd5):
 
 
 # =========================================================================== conv / attention kernels
-def _conv_case(B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res, seed):
+def _conv_case(B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res, seed, prep=None, exact_zero=False):
+    """One fused convolution through ipdm_op_conv2d against the float32 torch op (2e-5 relative) and the accuracy gate
+    (tests/_accuracy.py).  prep(x1, x2, w) -> (x1, x2, w) reshapes the inputs of an edge case; exact_zero: outputs whose receptive
+    field holds only zeros must equal fl(bias + res)."""
     from ipdm_pytorch_amd import _lib
     import torch.nn.functional as F
     Cin = C1 + C2
     x1 = torch.from_numpy(synth.hash_normal((B, C1, Hs, Ws), seed))
     x2 = torch.from_numpy(synth.hash_normal((B, C2, Hs, Ws), seed + 1)) * 2 + 0.5 if C2 else None
     w = torch.from_numpy(synth.hash_normal((Cout, Cin, ks, ks), seed + 2)) / np.sqrt(Cin * ks * ks)
+    if prep is not None:
+        x1, x2, w = prep(x1, x2, w)
     bias = torch.from_numpy(synth.hash_normal((Cout,), seed + 3))
     gamma = torch.from_numpy(synth.hash_uniform((Cin,), seed + 4)) + 0.5
     beta = torch.from_numpy(synth.hash_normal((Cin,), seed + 5)) * 0.2
@@ -314,6 +321,9 @@ def _conv_case(B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res, seed):
     got = out.cpu()
     err = (got - want).abs().max().item()
     assert err <= 2e-5 * max(1.0, want.abs().max().item()), (err, (B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res))
+    acc.conv_gate(got, want, xin, w, bias, act=act, groups=groups, gamma=gamma, beta=beta, size=(H, W), stride=stride, res=r,
+                  tag=_lib.lib().ipdm_conv_kernel_code(B, Cout, Cin, ks, stride, H, W), exact_zero=exact_zero,
+                  ctx=(B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res))
     return got
 
 
@@ -410,6 +420,121 @@ def test_conv_kernel_random_shapes():
         _conv_case(B, c1, c2, Hs, Ws, H, W, cout, ks, stride, act, res, seed=1000 + 17 * i)
 
 
+def _offset(x1, x2, w):
+    """x = 40 + N(0, 1): the Winograd input transform cancels the offset (r05 measured zero-mean inputs only)."""
+    return x1 + 40.0, x2, w
+
+
+def _cancel(x1, x2, w):
+    """3x3 kernels with zero mean over an offset input: outputs much smaller than their terms."""
+    return x1 + 40.0, (None if x2 is None else x2 + 40.0), w - w.mean(dim=(2, 3), keepdim=True)
+
+
+def _wide_range(x1, x2, w):
+    """x2 = 1e3 N(0, 1) next to x1 ~ N(0, 1) across the concat (_conv_case's x2 is 2 N(0, 1) + 0.5)."""
+    return x1, (x2 - 0.5) * 500.0, w
+
+
+def _box(x):
+    """Zero outside a central box (CT air)."""
+    H, W = x.shape[-2:]
+    m = torch.zeros((H, W))
+    m[H // 4:3 * H // 4, W // 4:3 * W // 4] = 1
+    return x * m
+
+
+def _zero_field(x1, x2, w):
+    return _box(x1), (None if x2 is None else _box(x2)), w
+
+
+EDGE_PREP = {"offset": _offset, "cancel": _cancel, "range": _wide_range, "zero": _zero_field}
+
+# kind, case (B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res  |  up-*: an UP2_CASES row), kernel code, options.  Together with
+# the other gated tests they cover every code ipdm_conv_kernel_code returns (test_gated_edge_cases_cover_every_kernel_code).
+EDGE_CASES = [
+    ("offset", (8, 128, 0, 64, 96, 64, 96, 128, 3, 1, 0, False), 2, {}),
+    ("offset", (2, 128, 0, 19, 250, 19, 250, 128, 3, 1, 0, True), 1, {}),
+    ("offset", (2, 256, 0, 13, 125, 13, 125, 256, 3, 1, 0, True), 9, {}),
+    ("offset", (2, 64, 0, 32, 32, 32, 32, 64, 3, 1, 0, True), 4, {}),
+    ("offset", (1, 16, 0, 50, 200, 50, 200, 16, 3, 1, 0, False), 6, {"conv_nm": 2}),
+    ("offset", (1, 48, 0, 20, 24, 20, 24, 24, 3, 1, 0, False), 8, {}),
+    ("up-offset", (2, 128, 16, 32, 128, 0, 128, 3, 2), 11, {}),
+    ("up-offset", (1, 64, 13, 21, 64, 64, 64, 3, 2), 7, {}),
+    ("cancel", (2, 128, 0, 37, 145, 37, 145, 128, 3, 1, 0, True), 2, {"wino2_min_tiles": 1}),
+    ("cancel", (2, 128, 0, 37, 145, 37, 145, 128, 3, 1, 0, True), 12, {"conv_bf16x3": 1}),
+    ("cancel", (8, 128, 0, 64, 96, 64, 96, 128, 3, 1, 0, False), 3, {"conv_no_wino": 1}),
+    ("cancel", (1, 256, 0, 32, 32, 32, 32, 256, 3, 1, 0, True), 9, {}),
+    ("cancel", (1, 8, 4, 33, 57, 33, 57, 8, 3, 1, 0, False), 5, {}),
+    ("range", (3, 128, 16, 40, 104, 40, 104, 128, 3, 1, 0, True), 2, {"wino2_min_tiles": 1}),
+    ("range", (3, 128, 16, 40, 104, 40, 104, 128, 3, 1, 2, True), 2, {"wino2_min_tiles": 1}),
+    ("range", (2, 128, 128, 45, 95, 45, 95, 128, 1, 1, 0, False), 10, {"pw_force": 1}),
+    ("range", (2, 128, 128, 45, 95, 45, 95, 128, 1, 1, 1, False), 10, {"pw_force": 1}),    # (conv_pw takes no SiLU prologue)
+    ("range", (1, 8, 4, 33, 57, 33, 57, 8, 3, 1, 0, False), 5, {}),
+    ("range", (1, 8, 4, 33, 57, 33, 57, 8, 3, 1, 2, False), 5, {}),
+    ("zero", (8, 128, 0, 64, 96, 64, 96, 128, 3, 1, 0, True), 2, {}),
+    ("zero", (2, 64, 0, 32, 32, 32, 32, 64, 3, 1, 0, True), 4, {}),
+    ("zero", (1, 8, 4, 33, 57, 33, 57, 8, 3, 1, 0, False), 5, {}),
+    ("zero", (2, 256, 0, 40, 72, 40, 72, 256, 1, 1, 0, True), 10, {"pw_force": 1}),
+    ("up-zero", (2, 128, 16, 32, 128, 0, 128, 3, 2), 11, {}),
+]
+
+
+def _up_kernel_code(case):
+    """The kernel of an Upsample chain's parity form (the rule _up_conv_chain asserts through its `used` report): 11 conv_wup2,
+    7 the 2x2-tap parity kernels, None the 3x3 form with nearest addressing."""
+    from ipdm_pytorch_amd import _lib
+    C, CA = case[1], case[4]
+    wide_mfma = _lib.lib().ipdm_conv_layout_code(CA, 3, 1) in (2, 4)
+    if wide_mfma and CA % 128 == 0 and C % 16 == 0 and C >= 32 and not _lib.get_option("conv_no_wup2"):
+        return 11
+    return 7 if wide_mfma or 4 < CA <= 16 else None
+
+
+@pytest.mark.parametrize("kind,case,code,opts", EDGE_CASES, ids=["%s-%d-%d" % (e[0], e[2], i) for i, e in enumerate(EDGE_CASES)])
+def test_conv_accuracy_edge_cases(kind, case, code, opts):
+    """The accuracy gate (tests/_accuracy.py) on the inputs where Winograd transforms, padding and K splits differ from a direct
+    sum and where CT data lives: an offset input into a no-prologue layer, kernels that cancel, a 1e3 dynamic range across a
+    concat, a zero field (with the exact check: outputs over all-zero receptive fields are fl(bias + res))."""
+    import contextlib
+    from ipdm_pytorch_amd import _lib
+    with contextlib.ExitStack() as st:
+        for k, v in opts.items():
+            st.enter_context(_lib.option(k, v))
+        if kind.startswith("up-"):
+            assert _up_kernel_code(case) == code, (case, code)
+            _up_conv_chain(case, prep=(lambda x: x + 40.0) if kind == "up-offset" else _box, exact_zero=kind == "up-zero")
+            return
+        B, C1, C2, Hs, Ws, H, W, Cout, ks, stride = case[:10]
+        assert _lib.lib().ipdm_conv_kernel_code(B, Cout, C1 + C2, ks, stride, H, W) == code, (case, code)
+        _conv_case(*case, seed=4000 + sum(case[:8]), prep=EDGE_PREP[kind], exact_zero=kind == "zero")
+
+
+def test_gated_edge_cases_cover_every_kernel_code():
+    """Every code ipdm_conv_kernel_code can return (1-12) has a gated case that asserts it."""
+    assert {e[2] for e in EDGE_CASES} == set(range(1, 13))
+
+
+@pytest.mark.parametrize("T", [1, 65, 1827, 7125])
+@pytest.mark.parametrize("kind", ["one_hot", "equal_keys", "v_offset"])
+def test_attention_accuracy_edge_cases(kind, T):
+    """The accuracy gate on attention inputs the random tests do not make: a near-one-hot softmax (q x 20), all keys equal (the
+    output is the mean of v), v = 100 + noise."""
+    from ipdm_pytorch_amd import _lib
+    d = 64
+    B, heads = (1, 1) if T > 4096 else (2, 2)
+    qkv = torch.from_numpy(synth.hash_normal((B, heads * 3 * d, T), 600 + T)).reshape(B, heads, 3 * d, T)
+    if kind == "one_hot":
+        qkv[:, :, :d] *= 20.0
+    elif kind == "equal_keys":
+        qkv[:, :, d:2 * d] = qkv[:, :, d:2 * d, :1].clone()
+    else:
+        qkv[:, :, 2 * d:] += 100.0
+    qkv = qkv.reshape(B, heads * 3 * d, T).contiguous()
+    out = torch.full((B, heads * d, T), float("nan"), device=DEV)
+    _lib.call("ipdm_op_attention", _lib.ptr(qkv.to(DEV)), _lib.ptr(out), B, heads, d, T, _lib.current_stream())
+    acc.attention_gate(out.cpu(), qkv, heads, d, ctx=(kind, B, heads, T))
+
+
 @pytest.mark.parametrize("B,heads,T", [(1, 1, 35), (2, 4, 117), (1, 4, 1024), (1, 2, 1827), (1, 1, 7125)])
 def test_attention_kernel(B, heads, T):
     from ipdm_pytorch_amd import _lib
@@ -422,6 +547,7 @@ def test_attention_kernel(B, heads, T):
     attn = torch.einsum("bct,bcs->bts", (q * scale).double(), (k * scale).double()).softmax(dim=-1)
     want = torch.einsum("bts,bcs->bct", attn, v.double()).reshape(B, heads * d, T).float()
     assert (out.cpu() - want).abs().max() <= 2e-5
+    acc.attention_gate(out.cpu(), qkv, heads, d, ctx=(B, heads, T))
 
 
 @pytest.mark.parametrize("T", [1024, 1827, 4096, 640])
@@ -444,6 +570,7 @@ def test_attention_key_slices_do_not_depend_on_the_schedule(T):
     attn = torch.einsum("bct,bcs->bts", (q * scale).double(), (k * scale).double()).softmax(dim=-1)
     want = torch.einsum("bts,bcs->bct", attn, v.double()).reshape(1, heads * d, T).float()
     assert (out[:1].cpu() - want).abs().max() <= 2e-5
+    acc.attention_gate(out.cpu(), qkv.cpu(), heads, d, ctx=(B, heads, T))
 
 
 def test_attention_random_lengths():
@@ -461,6 +588,7 @@ def test_attention_random_lengths():
         attn = torch.einsum("bct,bcs->bts", (q * scale).double(), (k * scale).double()).softmax(dim=-1)
         want = torch.einsum("bts,bcs->bct", attn, v.double()).reshape(B, heads * d, T).float()
         assert (out.cpu() - want).abs().max() <= 2e-5, (B, heads, T)
+        acc.attention_gate(out.cpu(), qkv, heads, d, ctx=(B, heads, T))
 
 
 def test_attention_softmax_rescale_branch():
@@ -475,6 +603,7 @@ def test_attention_softmax_rescale_branch():
     attn = torch.einsum("bct,bcs->bts", q / 64 ** 0.25, k / 64 ** 0.25).softmax(dim=-1)
     want = torch.einsum("bts,bcs->bct", attn, v).float()
     assert (out.cpu() - want).abs().max() <= 2e-5
+    acc.attention_gate(out.cpu(), qkv, 1, d, ctx=T)
     assert (out.cpu()[0, :, 10] - v[0, :, 150].float()).abs().max() < 1e-3
 
 
@@ -597,6 +726,15 @@ def _conv_gn_conv(case):
     assert (d_mid.cpu() - mid).abs().max() <= 2e-5 * max(1.0, mid.abs().max().item())
     err = (d_out.cpu() - want).abs().max().item()
     assert err <= 2e-5 * max(1.0, want.abs().max().item()), (err, case)
+    # accuracy gate (tests/_accuracy.py): mid as conv A alone, the output as the whole chain from x, both against float64
+    acc.conv_gate(d_mid.cpu(), mid, x, wA, bA, stride=sA, res=r, tag=_lib.lib().ipdm_conv_kernel_code_stats(B, CA, C, ksA, sA, H, W),
+                  ctx=case)
+    t0, bs, cs = time.perf_counter(), acc.samples(B), acc.out_channels(CB)
+    m64 = F.conv2d(x[bs].double(), wA.double(), bA.double(), stride=sA, padding=ksA // 2)
+    if resA:
+        m64 = m64 + r[bs].double()
+    rB, aB, _ = acc.conv_ref(acc.prologue(m64, act, groups, gamma, beta), wB, bB, cs=cs)
+    acc.check(acc.pick(d_out.cpu(), bs, cs), acc.pick(want, bs, cs), rB, aB, "gn-chain", case, t0)
     return d_mid.cpu(), d_out.cpu(), rows.value
 
 
@@ -705,6 +843,9 @@ def test_wino_kernels_bit_identical(case):
     assert torch.equal(outs[0], outs[1]), (outs[0] - outs[1]).abs().max()
     err = (outs[1] - want).abs().max().item()
     assert err <= 2e-5 * max(1.0, want.abs().max().item()), (err, case)
+    xin = x1 if x2 is None else torch.cat([x1, x2], 1)
+    for code, y in ((1, outs[0]), (2, outs[1])):
+        acc.conv_gate(y, want, xin, w, bias, act=act, groups=groups, gamma=gamma, beta=beta, res=r, tag=code, ctx=case)
 
 
 @pytest.mark.parametrize("case", WINO128_CASES + [
@@ -751,6 +892,17 @@ def test_wino3_bf16x3_against_the_f32_kernels(case):
     scale = max(1.0, want.abs().max().item())
     e2, e3 = (outs[0] - want), (outs[1] - want)
     assert e3.abs().max().item() <= 2e-5 * scale, (e3.abs().max().item(), e2.abs().max().item(), case)
+    # the accuracy gate (tests/_accuracy.py) against the float32 torch op, as for every float32 kernel: the same absolute bounds
+    xin = x1 if x2 is None else torch.cat([x1, x2], 1)
+    h32 = xin
+    if act:
+        h32 = F.group_norm(h32, groups, gamma, beta, eps=1e-5)
+        if act == 2:
+            h32 = F.silu(h32)
+    y32 = F.conv2d(h32, w, bias, padding=1)
+    if res:
+        y32 = y32 + r
+    acc.conv_gate(outs[1], y32, xin, w, bias, act=act, groups=groups, gamma=gamma, beta=beta, res=r, tag=12, ctx=case)
     r2, r3 = e2.pow(2).mean().sqrt().item(), e3.pow(2).mean().sqrt().item()
     print("wino3 %s: |f64 - wino2| rms %.3e max %.3e | |f64 - wino3| rms %.3e max %.3e | ratio %.2f" % (case, r2, e2.abs().max().item(), r3, e3.abs().max().item(), r3 / r2))
     assert r3 <= 1.5 * r2, (r3, r2, case)
@@ -915,12 +1067,14 @@ def test_pointwise_kernel_bit_identical_to_the_staged_one(case):
         staged = _op_conv(x, w, b, 1, act=act, gamma=gamma, beta=beta, res=r, x2=x2)
     assert torch.equal(got, staged)
     h = x if x2 is None else torch.cat([x, x2], 1)
+    xin = h
     if act:
         h = F.group_norm(h, ou.gn_groups(C1 + C2), gamma, beta, eps=1e-5)
     want = F.conv2d(h, w, b)
     if res:
         want = want + r
     assert (got.cpu() - want).abs().max() <= 2e-5 * max(1.0, want.abs().max().item())
+    acc.conv_gate(got.cpu(), want, xin, w, b, act=act, groups=ou.gn_groups(C1 + C2), gamma=gamma, beta=beta, res=r, tag=10, ctx=case)
 
 
 def test_pointwise_kernel_statistics_and_planar_reader_equal_the_staged_kernel():
@@ -1216,17 +1370,21 @@ UP2_CASES = [
 ]
 
 
-def _up_conv_chain(case):
+def _up_conv_chain(case, prep=None, exact_zero=False):
     """Upsample (nearest 2x + 3x3 conv) evaluated as four 2x2-tap convolutions over the source grid (the taps that fall on
     one source pixel added up when the weights are packed; on narrow levels inside the direct kernel), its parity-planar output, the fused statistics of that output
     and every kind of reader (3x3 / 1x1 wave-specialised kernels with and without a concatenated skip, the narrow direct
-    kernel, a K-split layer) against torch ops in float32: 2e-5 relative like the other convolution tests."""
+    kernel, a K-split layer) against torch ops in float32: 2e-5 relative like the other convolution tests; both results through
+    the accuracy gate (tests/_accuracy.py).  prep(x) reshapes the source of an edge case; exact_zero: mid outputs whose receptive
+    field holds only zeros must equal the bias."""
     import ctypes
     import torch.nn.functional as F
     from ipdm_pytorch_amd import _lib
     B, C, Hs, Ws, CA, C2, CB, ksB, act = case
     seed = 5000 + sum(case)
     x = torch.from_numpy(synth.hash_normal((B, C, Hs, Ws), seed)) * 1.1 + 0.3
+    if prep is not None:
+        x = prep(x)
     wA = torch.from_numpy(synth.hash_normal((CA, C, 3, 3), seed + 1)) / np.sqrt(C * 9)
     bA = torch.from_numpy(synth.hash_normal((CA,), seed + 2))
     Cc = CA + C2
@@ -1259,6 +1417,14 @@ def _up_conv_chain(case):
     assert (d_mid.cpu() - mid).abs().max() <= 2e-5 * max(1.0, mid.abs().max().item())
     err = (d_out.cpu() - want).abs().max().item()
     assert err <= 2e-5 * max(1.0, want.abs().max().item()), (err, case)
+    # accuracy gate: mid (the parity form: 11 conv_wup2, 7 the 2x2-tap kernels) and the reader's output as the whole chain from x
+    tag = 11 if used.value == 3 else 7 if used.value in (1, 2) else "up-nearest"
+    acc.conv_gate(d_mid.cpu(), mid, x, wA, bA, size=(2 * Hs, 2 * Ws), tag=tag, exact_zero=exact_zero, ctx=case)
+    t0, bs, cs = time.perf_counter(), acc.samples(B), acc.out_channels(CB)
+    m64 = F.conv2d(acc.resize(x[bs].double(), (2 * Hs, 2 * Ws)), wA.double(), bA.double(), padding=1)
+    h64 = acc.prologue(torch.cat([m64, skip[bs].double()], 1) if C2 else m64, act, groups, gamma, beta)
+    rB, aB, _ = acc.conv_ref(h64, wB, bB, cs=cs)
+    acc.check(acc.pick(d_out.cpu(), bs, cs), acc.pick(want, bs, cs), rB, aB, "up-reader", case, t0)
     return d_mid.cpu(), d_out.cpu()
 
 
