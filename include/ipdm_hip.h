@@ -43,7 +43,7 @@ int ipdm_abi_version(void);
  * as a debug alias) and changes only through this call afterwards.  Switches that shape packed weights or kernel choice
  * are recorded by ipdm_unet_create: a forward on a handle created under other values fails with IPDM_ERR_INVALID instead
  * of running on a mismatched layout; per-call switches (conv_no_up2, conv_no_wup2, conv_no_wino, conv_bf16x3, conv_no_pw, pw_item, pw_force, wino_v1, wino2_min_tiles, conv1x1_no_quarter, conv_nm, direct_no_skip_fuse, gn_unfused,
- * gn_two_stage, unet_transpose, attn_no_zseq, conv_dbg, art_per_view: every weight form they choose between is packed, the workspace
+ * gn_two_stage, unet_transpose, attn_no_zseq, attn_exact_f32, conv_dbg, art_per_view: every weight form they choose between is packed, the workspace
  * need is re-queried per forward) may change under a live handle.  Returns IPDM_ERR_INVALID for an unknown name. */
 int ipdm_set_option(const char *name, int value);
 int ipdm_get_option(const char *name, int *value);
@@ -306,7 +306,8 @@ int32_t ipdm_conv_kernel_code(int32_t B, int32_t Cout, int32_t Cin, int32_t ksiz
  * (conv_pw) here only if ONE sample brings >= 1024 items, whatever B. */
 int32_t ipdm_conv_kernel_code_stats(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W);
 /* Which attention kernel a launch with head dim d takes NOW: 0 = 4-wave kernel (d = 32, or IPDM_ATTN_LEGACY),
- * 1 = wave-specialised exact-f32 MFMA (the default for d = 64). */
+ * 1 = wave-specialised exact-f32 MFMA (d = 64 under the per-call option attn_exact_f32),
+ * 2 = bf16 matrix pipe through an error-free 3-way split of every operand, f32 accumulate (attn_bx3.hip; the default for d = 64). */
 int32_t ipdm_attention_kernel_code(int32_t d);
 
 #ifdef __cplusplus

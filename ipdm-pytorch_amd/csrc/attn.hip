@@ -24,8 +24,10 @@
 //   * out-of-range keys are masked only in the ragged last block.
 #include <cstdlib>
 #include "unet_kernels.h"
+#include "attn_common.h"
 
 using namespace ipdm;
+using namespace ipdm::attn;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -36,27 +38,6 @@ namespace {
 constexpr int KV = 64;         // keys per LDS tile
 constexpr int KP = 68;         // K pitch  [s][c]  (16-byte aligned rows, conflict-free b128 reads)
 constexpr int VP = 68;         // V pitch  [c][s]
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ inline int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// Maximum / sum over the two halves of the wave (lanes l and l ^ 32) by v_permlane32_swap (gfx950): one VALU instruction
-// turns two copies of x into {lo, lo} and {hi, hi}.  As __shfl_xor(x, 32) the exchange is a ds_bpermute, an LDS round trip
-// of ~100 cycles that the softmax waits for once per key block (the row maximum feeds every exponential).  Inline
-// assembly: the builtin mis-pairs its two results when both inputs are the same value; the two wait states are the
-// VALU-write -> permlane-read hazard the compiler would insert itself.
-__device__ inline float halves_max(float x)
-{
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-__device__ inline float halves_sum(float x)
-{
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
 
 template <int D, int QT>   // D: head dim C/heads (64 in both reference configs, 32 for reduced test nets); QT: 32-query tiles per wave
 __global__ void __launch_bounds__(256, 2) attention_kernel(const float *__restrict__ qkv, float *__restrict__ out,
@@ -200,22 +181,7 @@ __global__ void __launch_bounds__(256, 2) attention_kernel(const float *__restri
 // registers, MFMAs, softmax), waves 4-7 stage the NEXT K/V tile into the other LDS stage while the consumers work on the
 // current one -- global loads, LDS stores and the barrier latency leave the MFMA waves; one hand-over barrier per tile.
 // The only producer VALU is the 16 multiplies of K by the scale per tile (they fit the MFMA wave's stall gaps).
-// Key slices (short sequences, attention_kv_split): every slice is reduced with a FRESH running maximum / sum / output, and
-// the slices are folded in ascending order by this recurrence -- by the workgroup itself when it walks all slices of its
-// queries (zseq), or by attention_combine_kernel when the slices ran as separate workgroups (zsplit).  The same float
-// operations in the same order in both, so how a launch is scheduled (it depends on the batch size) never changes a bit.
-//   M' = max(M, m_k);  a = 2^((M - M') log2e);  b = 2^((m_k - M') log2e);  num = num a + o_k b;  den = den a + l_k b
-struct SliceWeights { float a, b; };
-__device__ inline SliceWeights slice_weights(float &M, float m_k)
-{
-    const float Mn = fmaxf(M, m_k);
-    SliceWeights w;
-    w.a = __builtin_amdgcn_exp2f((M - Mn) * LOG2E);        // first slice: M = -inf -> 0
-    w.b = __builtin_amdgcn_exp2f((m_k - Mn) * LOG2E);
-    M = Mn;
-    return w;
-}
-__device__ inline float slice_fold(float acc, float v, SliceWeights w) { return fmaf(acc, w.a, v * w.b); }
+// Key slices: slice_weights / slice_fold (attn_common.h), in ascending slice order.
 
 template <int D, int QT, bool ZSEQ = false>      // ZSEQ: a workgroup walks all key slices of its queries (zseq > 1)
 __global__ void __launch_bounds__(512, ZSEQ ? 2 : 1) attention_ws_kernel(const float *__restrict__ qkv, float *__restrict__ out,
@@ -497,7 +463,17 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
     const bool prof = prof_enabled();
     if (prof) prof_before(2, st);
     const bool legacy = opt(OPT_ATTN_LEGACY) != 0;
-    if (d == 64 && !legacy) {
+    const bool exact = opt(OPT_ATTN_EXACT_F32) != 0;
+    if (d == 64 && !legacy && !exact) {
+        // bf16 matrix pipe, error-free 3-way split (attn_bx3.hip): the same key slices, and the same choice between the split grid +
+        // combine pass and the in-workgroup walk, as the exact kernel below
+        const int Z = scratch ? attention_kv_split(B, heads, d, T) : 1;
+        const long wg1 = (long)cdiv(T, 128) * B * heads;
+        const bool seq = Z >= 4 && opt(OPT_ATTN_NO_ZSEQ) == 0 && wg1 >= 192;
+        attention_bx3_launch(qkv, out, B, heads, T, scale, Z, seq, scratch, st);
+        if (Z > 1 && !seq)
+            hipLaunchKernelGGL((attention_combine_kernel<64>), dim3(cdiv(T, 256), B * heads, 4), dim3(256), 0, st, scratch, out, T, Z, cdiv(T, KV));
+    } else if (d == 64 && !legacy) {
         // wave-specialised kernel, one 512-thread workgroup per CU.  64 queries per consumer wave (K/V operand reads
         // shared by two query tiles) when the 256-query workgroups come in whole rounds of the CUs, else 32
         constexpr size_t lds = (size_t)2 * (KV * KP + 64 * VP) * sizeof(float);
@@ -537,7 +513,8 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
 
 extern "C" int32_t ipdm_attention_kernel_code(int32_t d)
 {
-    return (d == 64 && !ipdm::opt(ipdm::OPT_ATTN_LEGACY)) ? 1 : 0;
+    if (d != 64 || ipdm::opt(ipdm::OPT_ATTN_LEGACY)) return 0;
+    return ipdm::opt(ipdm::OPT_ATTN_EXACT_F32) ? 1 : 2;
 }
 
 extern "C" int ipdm_op_attention(const float *d_qkv, float *d_out, int32_t B, int32_t heads, int32_t d, int32_t T,

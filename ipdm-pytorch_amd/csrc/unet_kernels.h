@@ -158,6 +158,10 @@ int gn_stats_launch(const GnArgs &a, hipStream_t st);
 // scratch: attention_scratch_floats() floats (the partial outputs of the key-slice split; null: never split)
 int attention_launch(const float *qkv, float *out, int B, int heads, int d, int T, hipStream_t st, float *scratch = nullptr);
 size_t attention_scratch_floats(int B, int heads, int d, int T);
+// d = 64 on the bf16 matrix pipe (attn_bx3.hip): Z key slices (attention_kv_split), walked inside the workgroup when seq, else as a
+// split grid whose partial outputs go to scratch (the caller launches the combine pass)
+void attention_bx3_launch(const float *qkv, float *out, int B, int heads, int T, float scale, int Z, bool seq, float *scratch,
+                          hipStream_t st);
 
 // time embedding: emb = Linear(SiLU(Linear(sinusoid(t)))) ; out = SiLU(emb)  (Model/model.py:14-32,218-222,105-108)
 int temb_launch(const float *freqs, int mc, int t, const float *w0, const float *b0, const float *w2, const float *b2,
