@@ -181,6 +181,65 @@ int ipdm_unet_forward(ipdm_unet *net, const float *d_x, int32_t t, float *d_eps,
 int ipdm_unet_forward_graph(ipdm_unet *net, const float *d_x, int32_t t, float *d_eps, int32_t B, int32_t H,
                             int32_t W, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ native reverse loop ----- */
+/* The sampler proper inside the library (csrc/sampler.hip): one call per outer pass, or one call for the whole
+ * fixed-schedule process, instead of a host loop that issues ipdm_randn, (ipdm_lambda_ratio,) ipdm_unet_forward and
+ * ipdm_ddpm_step per reverse step.  Same arithmetic, same draw numbering, same bits as that composition.
+ * IPDM_ABI_VERSION stays 5: these entries were added without touching an existing signature, and a binder detects them
+ * by symbol (dlsym of ipdm_guided_reverse).
+ *
+ * The two fused ops of a step, exported so that they can be held to the launches they replace:
+ * ipdm_q_sample_rng = ipdm_randn + ipdm_q_sample (q_sample, Model/model.py:438-445) and ipdm_ddpm_step_rng = ipdm_randn +
+ * ipdm_ddpm_step (p_sample_condition, :492-515), with the N(0,1) value of (seed, slice_id0 + b, draw, element) made in
+ * registers.  Tensors are [B, n_per_slice]; any n_per_slice (the 16-byte path needs n_per_slice % 4 == 0 and 16-byte
+ * aligned pointers, otherwise elements go one by one). */
+int ipdm_q_sample_rng(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B, int64_t n_per_slice,
+                      uint64_t seed, int64_t slice_id0, int64_t draw, void *stream);
+int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
+                       uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B, int32_t H, int32_t W,
+                       double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw, int32_t clip_denoised,
+                       void *d_ws, size_t ws_bytes, void *stream);
+
+/* Arguments of guided_reverse_process (Model/model.py:517-536) that shape a pass. */
+typedef struct ipdm_reverse_args {
+    int32_t mode;            /* 0 img, 1 proj (clamp rule, guide-update rule, guidance curve) */
+    int32_t clip;            /* guided_reverse_process(clip=): clip_denoised of every step + the clamp after a pass */
+    int32_t guidance;        /* pass: 0 constant scalar, 1 cosine_beta_schedule(ts, lambda_power)[i], 2 map from d_Lambda;
+                              * process: 0 constant_guidance, 1 constant guidance off (curve on pass 0, then the map) */
+    double constant_guidance, lambda_power, eta;
+    int32_t kernel_size;     /* guidance map after pass 0 (process call only) */
+    double amplitude;
+    double p1[5], p2[3];     /* weight_lambda curve, as ipdm_guidance_map takes it */
+    uint64_t seed;           /* counter-based noise: draw k of the call is draw0 + k */
+    int64_t slice_id0, draw0;
+    const float *d_noise;    /* or NULL; else injected draws [n_draws, B, H*W], used in order (parity mode) */
+    const float *d_ldct;     /* img-mode guide update (Model/model.py:625-628), else NULL (process call only) */
+} ipdm_reverse_args;
+
+/* bytes of scratch either call below needs: UNet workspace, step and guidance workspaces, the x ping-pong, eps, the
+ * guide and the small lambda maps are all carved out of the caller's d_ws -- neither call allocates or synchronises. */
+size_t ipdm_reverse_workspace_bytes(ipdm_unet *net, int32_t B, int32_t H, int32_t W);
+
+/* ONE outer pass (Model/model.py:537-573): q_sample at ts, then for i = ts-1 .. 0 { UNet forward at i, guided step },
+ * then the clamp.  d_x_in: the pass's start image; d_guide: x_0 of every step; d_Lambda [B,mh,mw] when guidance == 2;
+ * d_iter [B,H,W]: the pass's result.  Consumes ts + 1 draws (a->draw0 .. a->draw0 + ts, or the first ts + 1 of
+ * a->d_noise).  Bad arguments (NULL handles, ts <= 0, guidance 2 without a map, a short workspace) are refused before
+ * any launch. */
+int ipdm_reverse_pass(const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
+                      const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W,
+                      int32_t ts, const ipdm_reverse_args *a, void *d_ws, size_t ws_bytes, void *stream);
+
+/* guided_reverse_process with an explicit t_start list (Model/model.py:517-642, t_start != None): all passes, the
+ * guidance map after pass 0 when constant guidance is off (:574-614), the guide updates (:625-635), the reset of x
+ * after pass 0 (:621-622) and the final 0.5*(last + previous) (:637-638).  d_iters [n_out, B, H, W],
+ * n_out = n_pass + (n_pass > 1); *draws_used (may be NULL) receives sum(ts + 1).  The adaptive schedule
+ * (t_start = None) needs one device-to-host scalar and, when sharded, a MAX all-reduce between pass 0 and pass 1: it
+ * is NOT in this call -- a binder composes ipdm_reverse_pass, ipdm_guidance_map and its own decision
+ * (INTEGRATION.md). */
+int ipdm_guided_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_img, float *d_iters, int32_t B,
+                        int32_t H, int32_t W, const int32_t *t_start, int32_t n_pass, const ipdm_reverse_args *a,
+                        int64_t *draws_used, void *d_ws, size_t ws_bytes, void *stream);
+
 /* op-level entry points (parity tests of the individual kernels against torch-CPU ops) */
 /* F.conv2d(cat(x1,x2) [upsampled to H,W by nearest], w, b, stride, padding=k/2) with optional fused
  * GroupNorm(+SiLU) prologue over the concatenated input and optional residual add.

@@ -28,6 +28,16 @@ class UnetCfg(C.Structure):
                 ("attention_resolutions", C.c_int32 * 16)]
 
 
+class ReverseArgs(C.Structure):
+    """ipdm_reverse_args: what shapes a pass of the native reverse loop (ipdm_reverse_pass / ipdm_guided_reverse)."""
+    _fields_ = [("mode", C.c_int32), ("clip", C.c_int32), ("guidance", C.c_int32),
+                ("constant_guidance", C.c_double), ("lambda_power", C.c_double), ("eta", C.c_double),
+                ("kernel_size", C.c_int32), ("amplitude", C.c_double),
+                ("p1", C.c_double * 5), ("p2", C.c_double * 3),
+                ("seed", C.c_uint64), ("slice_id0", C.c_int64), ("draw0", C.c_int64),
+                ("d_noise", C.c_void_p), ("d_ldct", C.c_void_p)]
+
+
 _vp, _i32, _i64, _u64, _f32, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); restype int => status code checked by _call
@@ -74,6 +84,14 @@ PROTOTYPES = {
     "ipdm_unet_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "ipdm_unet_forward": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "ipdm_unet_forward_graph": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ipdm_q_sample_rng": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _u64, _i64, _i64, _vp]),
+    "ipdm_ddpm_step_rng": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _u64, _i64, _i64, _vp, _i32, _i32, _i32, _f64, _vp, _i32, _i32,
+                                     _i32, _vp, _sz, _vp]),
+    "ipdm_reverse_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "ipdm_reverse_pass": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, C.POINTER(ReverseArgs),
+                                    _vp, _sz, _vp]),
+    "ipdm_guided_reverse": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(ReverseArgs),
+                                      C.POINTER(_i64), _vp, _sz, _vp]),
     "ipdm_op_conv2d": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
                                  _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ipdm_op_conv_gn_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp,

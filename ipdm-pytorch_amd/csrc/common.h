@@ -70,6 +70,9 @@ int ensure_dynamic_lds(const void *kernel, size_t bytes);
 // multiprocessor count of the CURRENT device (cached per device)
 int device_cu_count();
 
+// input / output channel counts of a UNet handle (unet.hip)
+int unet_io_channels(const ipdm_unet *net, int *cin, int *cout);
+
 // wave64 reductions (CDNA wavefront = 64 lanes)
 __device__ inline double wave_sum(double v)
 {

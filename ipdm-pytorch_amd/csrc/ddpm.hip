@@ -11,6 +11,7 @@
 #include <cmath>
 #include <vector>
 #include "common.h"
+#include "ddpm_dev.h"   // philox4x32_10, randn_quad, StepCoef, lambda_at, load_totals, mean_std: shared with sampler.hip
 
 using namespace ipdm;
 
@@ -103,22 +104,6 @@ extern "C" int ipdm_cosine_lambda(int32_t ts, double power, int32_t i, double *o
 }
 
 // =============================================================================== noise
-__device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        uint32_t n1 = (uint32_t)p1;
-        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        uint32_t n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
 // counter = (element/4 lo32, element/4 hi32 | draw << 8 .., slice lo, slice hi ^ draw hi): see host note.
 __global__ void __launch_bounds__(256) randn_kernel(float *__restrict__ out, long n, uint32_t seed_lo,
                                                     uint32_t seed_hi, long slice_id0, long draw)
@@ -127,20 +112,8 @@ __global__ void __launch_bounds__(256) randn_kernel(float *__restrict__ out, lon
     const long nq = (n + 3) / 4;
     if (q >= nq) return;
     const long slice = slice_id0 + blockIdx.y;
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)draw, (uint32_t)slice, (uint32_t)((uint64_t)slice >> 32) ^ ((uint32_t)((uint64_t)q >> 32) << 16) ^ (uint32_t)((uint64_t)draw >> 32)};
-    philox4x32_10(c, seed_lo, seed_hi);
     float z[4];
-    const float two_pi = 6.283185307179586f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        float rad = sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(two_pi * u2, &sn, &cs);
-        z[2 * h] = rad * cs;
-        z[2 * h + 1] = rad * sn;
-    }
+    randn_quad(q, slice, draw, seed_lo, seed_hi, z);
     float *dst = out + (size_t)blockIdx.y * n + q * 4;
     if (q * 4 + 3 < n && ((n & 3) == 0)) {
         *reinterpret_cast<float4 *>(dst) = make_float4(z[0], z[1], z[2], z[3]);
@@ -236,26 +209,7 @@ extern "C" int ipdm_axpbypcz(const float *d_x, const float *d_y, const float *d_
 }
 
 // =============================================================================== guided reverse step
-// Per-slice statistics use RED_BLOCKS workgroups per slice; block partials (fp64) land in the
-// workspace and every consumer workgroup re-reduces them in a fixed order.
-constexpr int RED_BLOCKS = 64;
-
-struct StepCoef {
-    float sa, s1m, sr, srm1, c1, c2, sigma;
-    float w_pred, w_cond;   // scalar guidance
-    int use_map, H, W, mh, mw, clip;
-    float sy, sx;           // nearest scales (float32, as ATen computes them)
-    float d_a, d_b, d_p, d_dir, d_sig;   // DDIM step: sqrt(1-ac_t), sqrt(ac_t), sqrt(ac_prev), sqrt(1-ac_prev-sigma^2), eta*post_var
-};
-
-__device__ inline float lambda_at(const StepCoef &k, const float *__restrict__ lmap, long idx)
-{
-    int y = (int)(idx / k.W), x = (int)(idx - (long)y * k.W);
-    int syi = min((int)floorf((float)y * k.sy), k.mh - 1);
-    int sxi = min((int)floorf((float)x * k.sx), k.mw - 1);
-    return lmap[(size_t)syi * k.mw + sxi];
-}
-
+// (RED_BLOCKS, StepCoef, lambda_at, load_totals and mean_std: ddpm_dev.h)
 __device__ inline void block_reduce_store(double *vals, int nvals, double *dst)
 {
     __shared__ double red[4][8];
@@ -266,30 +220,6 @@ __device__ inline void block_reduce_store(double *vals, int nvals, double *dst)
     }
     __syncthreads();
     if (threadIdx.x < nvals) dst[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// sums partials[b][0..RED_BLOCKS)[k] in fixed order -> every thread gets the totals
-__device__ inline void load_totals(const double *__restrict__ partials, int nvals, double *tot)
-{
-    __shared__ double totals[8];
-    if (threadIdx.x < 64) {
-        for (int k = 0; k < nvals; ++k) {
-            double v = (threadIdx.x < RED_BLOCKS) ? partials[threadIdx.x * 8 + k] : 0.0;
-            v = wave_sum(v);
-            if (threadIdx.x == 0) totals[k] = v;
-        }
-    }
-    __syncthreads();
-    for (int k = 0; k < nvals; ++k) tot[k] = totals[k];
-    __syncthreads();
-}
-
-__device__ inline void mean_std(double sum, double sumsq, long n, float &mean, float &sd)
-{
-    double m = sum / (double)n;
-    double var = (sumsq - (double)n * m * m) / (double)(n - 1);   // unbiased (torch.std)
-    mean = (float)m;
-    sd = (float)sqrt(var > 0 ? var : 0.0);
 }
 
 // pass A: sums of pred, pred^2, cond, cond^2  (cond = (x_t - sa*x0)/s1m, Model/model.py:447-450)
@@ -363,6 +293,13 @@ __global__ void __launch_bounds__(256) step_apply_kernel(const float *__restrict
     }
 }
 
+void ipdm::step_stats_launch(const float *d_eps_pred, const float *d_x_t, const float *d_x0, const float *d_lambda_map, long n, int B,
+                             const StepCoef &k, double *ws, hipStream_t st)
+{
+    hipLaunchKernelGGL(step_stats1_kernel, dim3(RED_BLOCKS, B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, n, k, ws);
+    hipLaunchKernelGGL(step_stats2_kernel, dim3(RED_BLOCKS, B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_lambda_map, n, k, ws);
+}
+
 extern "C" size_t ipdm_ddpm_workspace_bytes(int32_t B)
 {
     return B <= 0 ? 0 : (size_t)B * 2 * RED_BLOCKS * 8 * sizeof(double);
@@ -379,24 +316,13 @@ extern "C" int ipdm_ddpm_step(const ipdm_schedule *s, int32_t t, const float *d_
     float c[8];
     int rc = ipdm_schedule_coeffs(s, t, c);
     if (rc) return rc;
+    if (d_lambda_map) IPDM_REQUIRE(mh > 0 && mw > 0, "ddpm_step: lambda map without dims");
     StepCoef k;
-    k.sa = c[0]; k.s1m = c[1]; k.sr = c[2]; k.srm1 = c[3]; k.c1 = c[4]; k.c2 = c[5];
-    // nonzero_mask * exp(0.5*logvar) (Model/model.py:511-514): f32 arithmetic
-    k.sigma = (t == 0) ? 0.0f : expf(0.5f * c[6]);
-    k.w_pred = (float)(1.0 - lambda_scalar);   // python: (1 - lambda_) in double, then cast (torch scalar rule)
-    k.w_cond = (float)lambda_scalar;
-    k.use_map = d_lambda_map != nullptr;
-    k.H = H; k.W = W; k.mh = mh; k.mw = mw; k.clip = clip_denoised;
-    if (k.use_map) {
-        IPDM_REQUIRE(mh > 0 && mw > 0, "ddpm_step: lambda map without dims");
-        k.sy = (float)mh / (float)H;   // ATen nearest: scale = in/out in float32
-        k.sx = (float)mw / (float)W;
-    } else { k.sy = k.sx = 0.f; }
+    step_coef_fill(k, c, t, lambda_scalar, d_lambda_map != nullptr, H, W, mh, mw, clip_denoised);
     const long n = (long)H * W;
     hipStream_t st = (hipStream_t)stream;
     double *ws = (double *)d_ws;
-    hipLaunchKernelGGL(step_stats1_kernel, dim3(RED_BLOCKS, B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, n, k, ws);
-    hipLaunchKernelGGL(step_stats2_kernel, dim3(RED_BLOCKS, B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_lambda_map, n, k, ws);
+    step_stats_launch(d_eps_pred, d_x_t, d_x0, d_lambda_map, n, B, k, ws, st);
     int gx = cdiv(n, 256 * 4); if (gx > 512) gx = 512;
     hipLaunchKernelGGL(step_apply_kernel, dim3(gx, B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_noise, d_lambda_map, d_out, n, k, ws);
     IPDM_LAUNCH_CHECK();

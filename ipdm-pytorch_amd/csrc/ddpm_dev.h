@@ -1,0 +1,115 @@
+// Device helpers shared by ddpm.hip (the op-level entry points) and sampler.hip (the kernels of the native reverse loop):
+// counter-based noise, the coefficient block of a guided reverse step, the per-slice statistics' fixed-order totals.
+// Both files must produce the same bits from them, so they live here once.
+#pragma once
+#include <cmath>
+#include "common.h"
+
+namespace ipdm {
+
+// =============================================================================== noise
+__device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+        uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+        uint32_t n1 = (uint32_t)p1;
+        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        uint32_t n3 = (uint32_t)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// The four N(0,1) values of quad q (elements 4q .. 4q+3) of global slice `slice`, draw `draw`:
+// counter = (element/4 lo32, element/4 hi32 | draw << 8 .., slice lo, slice hi ^ draw hi): see ipdm_randn's note in the header.
+__device__ inline void randn_quad(long q, long slice, long draw, uint32_t seed_lo, uint32_t seed_hi, float z[4])
+{
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)draw, (uint32_t)slice, (uint32_t)((uint64_t)slice >> 32) ^ ((uint32_t)((uint64_t)q >> 32) << 16) ^ (uint32_t)((uint64_t)draw >> 32)};
+    philox4x32_10(c, seed_lo, seed_hi);
+    const float two_pi = 6.283185307179586f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(two_pi * u2, &sn, &cs);
+        z[2 * h] = rad * cs;
+        z[2 * h + 1] = rad * sn;
+    }
+}
+
+// =============================================================================== guided reverse step
+// Per-slice statistics use RED_BLOCKS workgroups per slice; block partials (fp64) land in the
+// workspace and every consumer workgroup re-reduces them in a fixed order.
+constexpr int RED_BLOCKS = 64;
+
+struct StepCoef {
+    float sa, s1m, sr, srm1, c1, c2, sigma;
+    float w_pred, w_cond;   // scalar guidance
+    int use_map, H, W, mh, mw, clip;
+    float sy, sx;           // nearest scales (float32, as ATen computes them)
+    float d_a, d_b, d_p, d_dir, d_sig;   // DDIM step: sqrt(1-ac_t), sqrt(ac_t), sqrt(ac_prev), sqrt(1-ac_prev-sigma^2), eta*post_var
+};
+
+__device__ inline float lambda_at(const StepCoef &k, const float *__restrict__ lmap, long idx)
+{
+    int y = (int)(idx / k.W), x = (int)(idx - (long)y * k.W);
+    int syi = min((int)floorf((float)y * k.sy), k.mh - 1);
+    int sxi = min((int)floorf((float)x * k.sx), k.mw - 1);
+    return lmap[(size_t)syi * k.mw + sxi];
+}
+
+// sums partials[b][0..RED_BLOCKS)[k] in fixed order -> every thread gets the totals
+__device__ inline void load_totals(const double *__restrict__ partials, int nvals, double *tot)
+{
+    __shared__ double totals[8];
+    if (threadIdx.x < 64) {
+        for (int k = 0; k < nvals; ++k) {
+            double v = (threadIdx.x < RED_BLOCKS) ? partials[threadIdx.x * 8 + k] : 0.0;
+            v = wave_sum(v);
+            if (threadIdx.x == 0) totals[k] = v;
+        }
+    }
+    __syncthreads();
+    for (int k = 0; k < nvals; ++k) tot[k] = totals[k];
+    __syncthreads();
+}
+
+__device__ inline void mean_std(double sum, double sumsq, long n, float &mean, float &sd)
+{
+    double m = sum / (double)n;
+    double var = (sumsq - (double)n * m * m) / (double)(n - 1);   // unbiased (torch.std)
+    mean = (float)m;
+    sd = (float)sqrt(var > 0 ? var : 0.0);
+}
+
+// Host side of a dense step: the coefficient block of ipdm_ddpm_step / ipdm_ddpm_step_rng from the schedule's tables at t
+// (c[] as ipdm_schedule_coeffs returns them).
+static inline void step_coef_fill(StepCoef &k, const float c[8], int t, double lambda_scalar, bool use_map, int H, int W,
+                                  int mh, int mw, int clip_denoised)
+{
+    k.sa = c[0]; k.s1m = c[1]; k.sr = c[2]; k.srm1 = c[3]; k.c1 = c[4]; k.c2 = c[5];
+    // nonzero_mask * exp(0.5*logvar) (Model/model.py:511-514): f32 arithmetic
+    k.sigma = (t == 0) ? 0.0f : expf(0.5f * c[6]);
+    k.w_pred = (float)(1.0 - lambda_scalar);   // python: (1 - lambda_) in double, then cast (torch scalar rule)
+    k.w_cond = (float)lambda_scalar;
+    k.use_map = use_map;
+    k.H = H; k.W = W; k.mh = mh; k.mw = mw; k.clip = clip_denoised;
+    if (use_map) {
+        k.sy = (float)mh / (float)H;   // ATen nearest: scale = in/out in float32
+        k.sx = (float)mw / (float)W;
+    } else { k.sy = k.sx = 0.f; }
+    k.d_a = k.d_b = k.d_p = k.d_dir = k.d_sig = 0.0f;
+}
+
+// the two statistics passes of a guided step (step_stats1/2_kernel, ddpm.hip) on `st`: their partial-sum layout and reduction
+// order define the bits of a step, so sampler.hip launches them as they are
+void step_stats_launch(const float *d_eps_pred, const float *d_x_t, const float *d_x0, const float *d_lambda_map, long n, int B,
+                       const StepCoef &k, double *ws, hipStream_t st);
+
+}  // namespace ipdm

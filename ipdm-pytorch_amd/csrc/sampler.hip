@@ -1,0 +1,441 @@
+// The reverse loop of the guided partial-diffusion sampler inside the library: one C call per outer pass
+// (ipdm_reverse_pass) or per fixed-schedule process (ipdm_guided_reverse), and the elementwise kernels written for it --
+// q_sample and the third pass of a guided step with the N(0,1) draw made in registers instead of read from a buffer that
+// an ipdm_randn launch wrote, and a pass epilogue (clamp + guide update in one launch).
+//
+// Replaces (reference file:line): the control flow of GaussianDiffusion.guided_reverse_process with an explicit t_start
+// list (Model/model.py:517-642): q_sample (:537-541), the inner loop of p_sample_condition calls with its guidance choice
+// (:542-568), the clamp after a pass (:569-573), the guidance map after pass 0 (:574-614), the guide updates and the reset
+// of x after pass 0 (:619-635), the final average (:637-638).
+//
+// Bits.  Every kernel here gives exactly the bits of the launches it replaces (ipdm_randn into a buffer, then ipdm_q_sample /
+// ipdm_ddpm_step / ipdm_clamp + ipdm_axpbypcz).  The noise is the same pure function of (seed, slice, draw, element)
+// (randn_quad, ddpm_dev.h); the statistics passes of a step are ddpm.hip's own launches; the per-element expressions are
+// written with every rounding spelled out -- `#pragma clang fp contract(off)` and explicit fmaf -- in the form the compiler
+// gives ddpm.hip's kernels (read from their gfx950 code; tests/test_gpu_native_reverse.py holds the two to torch.equal):
+//   q_sample_kernel     out  = fma(sa, x, s1m*z)
+//   step_apply_kernel   cond = fma(-sa, x0, x) / s1m;  mix = wp*p + wc*c;  xr = sr*x - srm1*eps   (products rounded)
+//                       mean = fma(c1, xr, c2*x);  out = mean + sigma*z                           (product rounded)
+//   axpbypcz_kernel     v = a*x + b*y (products rounded);  v = fma(c, z, v)
+#include <cmath>
+#include "common.h"
+#include "ddpm_dev.h"
+
+using namespace ipdm;
+
+// =============================================================================== kernels
+// grid of a per-slice streaming kernel over nq quads: enough workgroups to fill the chip (256 CUs x 8), never more than
+// the work, the rest by a grid stride
+static inline int quad_grid(long nq, int B)
+{
+    long per = 2048 / (B < 1 ? 1 : B);
+    if (per < 1) per = 1;
+    long g = (nq + 255) / 256;
+    if (g > per) g = per;
+    return (int)(g < 1 ? 1 : g);
+}
+
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+__device__ inline float q_sample_elem(float sa, float s1m, float x, float z)
+{
+#pragma clang fp contract(off)
+    return fmaf(sa, x, s1m * z);
+}
+
+// out[b, e] = sa*x[b, e] + s1m*z(seed, slice_id0 + b, draw, e); vec: n % 4 == 0 and 16-byte aligned pointers
+__global__ void __launch_bounds__(256) q_sample_rng_kernel(const float *__restrict__ x, float *__restrict__ out, long n, float sa,
+                                                           float s1m, uint32_t seed_lo, uint32_t seed_hi, long slice_id0,
+                                                           long draw, int vec)
+{
+    const int b = blockIdx.y;
+    const size_t off = (size_t)b * n;
+    const long slice = slice_id0 + b;
+    const long nq = (n + 3) / 4;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        float z[4];
+        randn_quad(q, slice, draw, seed_lo, seed_hi, z);
+        const long e0 = q * 4;
+        if (vec) {
+            const float4 a = *reinterpret_cast<const float4 *>(x + off + e0);
+            *reinterpret_cast<float4 *>(out + off + e0) = make_float4(q_sample_elem(sa, s1m, a.x, z[0]), q_sample_elem(sa, s1m, a.y, z[1]),
+                                                                      q_sample_elem(sa, s1m, a.z, z[2]), q_sample_elem(sa, s1m, a.w, z[3]));
+        } else {
+            for (int e = 0; e < 4; ++e)
+                if (e0 + e < n) out[off + e0 + e] = q_sample_elem(sa, s1m, x[off + e0 + e], z[e]);
+        }
+    }
+}
+
+struct SliceStats { float m1, s1, m2, s2, m3, s3; };
+
+// one element of step_apply_kernel (ddpm.hip), noise handed in
+__device__ inline float step_apply_elem(const StepCoef &k, const SliceStats &s, const float *__restrict__ lm, long i, float pred,
+                                        float x, float x0, float z)
+{
+#pragma clang fp contract(off)
+    const float p = (pred - s.m1) / s.s1;
+    const float c = (fmaf(-k.sa, x0, x) / k.s1m - s.m2) / s.s2;
+    float wp = k.w_pred, wc = k.w_cond;
+    if (k.use_map) { wc = lambda_at(k, lm, i); wp = 1.0f - wc; }
+    const float eps = ((wp * p + wc * c) - s.m3) / s.s3;
+    float xr = k.sr * x - k.srm1 * eps;
+    if (k.clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
+    const float mean = fmaf(k.c1, xr, k.c2 * x);
+    return mean + k.sigma * z;
+}
+
+// pass C of a guided step with the draw made in registers: eps = whiten(mixed); x0_hat; clamp; posterior mean; + sigma*z
+// (Model/model.py:497-515).  One Philox quad per thread per four consecutive elements.
+__global__ void __launch_bounds__(256) step_apply_rng_kernel(const float *__restrict__ pred, const float *__restrict__ xt,
+                                                             const float *__restrict__ x0, const float *__restrict__ lmap,
+                                                             float *__restrict__ out, long n, StepCoef k,
+                                                             const double *__restrict__ ws, uint32_t seed_lo, uint32_t seed_hi,
+                                                             long slice_id0, long draw, int vec)
+{
+    const int b = blockIdx.y;
+    const size_t off = (size_t)b * n;
+    double t[4], u[2];
+    load_totals(ws + (size_t)b * 2 * RED_BLOCKS * 8, 4, t);
+    load_totals(ws + ((size_t)b * 2 * RED_BLOCKS + RED_BLOCKS) * 8, 2, u);
+    SliceStats s;
+    mean_std(t[0], t[1], n, s.m1, s.s1);
+    mean_std(t[2], t[3], n, s.m2, s.s2);
+    mean_std(u[0], u[1], n, s.m3, s.s3);
+    const float *lm = k.use_map ? lmap + (size_t)b * k.mh * k.mw : nullptr;
+    const long slice = slice_id0 + b;
+    const long nq = (n + 3) / 4;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        float z[4];
+        randn_quad(q, slice, draw, seed_lo, seed_hi, z);
+        const long e0 = q * 4;
+        if (vec) {
+            const float4 p = *reinterpret_cast<const float4 *>(pred + off + e0);
+            const float4 x = *reinterpret_cast<const float4 *>(xt + off + e0);
+            const float4 g = *reinterpret_cast<const float4 *>(x0 + off + e0);
+            *reinterpret_cast<float4 *>(out + off + e0) =
+                make_float4(step_apply_elem(k, s, lm, e0, p.x, x.x, g.x, z[0]), step_apply_elem(k, s, lm, e0 + 1, p.y, x.y, g.y, z[1]),
+                            step_apply_elem(k, s, lm, e0 + 2, p.z, x.z, g.z, z[2]), step_apply_elem(k, s, lm, e0 + 3, p.w, x.w, g.w, z[3]));
+        } else {
+            for (int e = 0; e < 4; ++e)
+                if (e0 + e < n)
+                    out[off + e0 + e] = step_apply_elem(k, s, lm, e0 + e, pred[off + e0 + e], xt[off + e0 + e], x0[off + e0 + e], z[e]);
+        }
+    }
+}
+
+struct EpiCoef { int clip, mode, want_guide, has_z; float a, b, c; };
+
+// clamp_kernel's value (mode 0: [0,1]; 1: min 0; clip == 0: a copy)
+__device__ inline float epi_clamp(const EpiCoef &k, float v)
+{
+    if (k.clip) {
+        v = fmaxf(v, 0.0f);
+        if (k.mode == 0) v = fminf(v, 1.0f);
+    }
+    return v;
+}
+
+// axpbypcz_kernel's value
+__device__ inline float epi_guide(const EpiCoef &k, float it, float img, float z)
+{
+#pragma clang fp contract(off)
+    float v = k.a * it + k.b * img;
+    if (k.has_z) v = fmaf(k.c, z, v);
+    return v;
+}
+
+// after the last step of a pass: iter = clamp(x) (Model/model.py:569-573) and, where asked, guide = a*iter + b*img (+ c*ldct)
+// (:625-635) in one launch.  n = B*H*W; vec: n % 4 == 0 and 16-byte aligned pointers.
+__global__ void __launch_bounds__(256) pass_epilogue_kernel(const float *__restrict__ x, const float *__restrict__ img,
+                                                            const float *__restrict__ ldct, float *__restrict__ iter,
+                                                            float *__restrict__ guide, long n, EpiCoef k, int vec)
+{
+    const long stride = (long)gridDim.x * 256;
+    if (vec) {
+        for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride * 4) {
+            const float4 v = *reinterpret_cast<const float4 *>(x + i);
+            const float4 o = make_float4(epi_clamp(k, v.x), epi_clamp(k, v.y), epi_clamp(k, v.z), epi_clamp(k, v.w));
+            *reinterpret_cast<float4 *>(iter + i) = o;
+            if (k.want_guide) {
+                const float4 m = *reinterpret_cast<const float4 *>(img + i);
+                float4 l = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (k.has_z) l = *reinterpret_cast<const float4 *>(ldct + i);
+                *reinterpret_cast<float4 *>(guide + i) =
+                    make_float4(epi_guide(k, o.x, m.x, l.x), epi_guide(k, o.y, m.y, l.y), epi_guide(k, o.z, m.z, l.z), epi_guide(k, o.w, m.w, l.w));
+            }
+        }
+    } else {
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+            const float o = epi_clamp(k, x[i]);
+            iter[i] = o;
+            if (k.want_guide) guide[i] = epi_guide(k, o, img[i], k.has_z ? ldct[i] : 0.0f);
+        }
+    }
+}
+
+// =============================================================================== fused ops
+extern "C" int ipdm_q_sample_rng(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B, int64_t n_per_slice,
+                                 uint64_t seed, int64_t slice_id0, int64_t draw, void *stream)
+{
+    IPDM_REQUIRE(s && d_x && d_out && B > 0 && n_per_slice > 0, "q_sample_rng: bad argument");
+    float c[8];
+    int rc = ipdm_schedule_coeffs(s, t, c);
+    if (rc) return rc;
+    const long n = (long)n_per_slice;
+    const int vec = (n & 3) == 0 && aligned16(d_x) && aligned16(d_out);
+    hipLaunchKernelGGL(q_sample_rng_kernel, dim3(quad_grid((n + 3) / 4, B), B), dim3(256), 0, (hipStream_t)stream, d_x, d_out, n,
+                       c[0], c[1], (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
+    IPDM_LAUNCH_CHECK();
+    return IPDM_OK;
+}
+
+extern "C" int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
+                                  uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B, int32_t H, int32_t W,
+                                  double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw, int32_t clip_denoised,
+                                  void *d_ws, size_t ws_bytes, void *stream)
+{
+    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_x0 && d_out && d_ws && B > 0 && H > 0 && W > 0, "ddpm_step_rng: bad argument");
+    IPDM_REQUIRE(!d_lambda_map || (mh > 0 && mw > 0), "ddpm_step_rng: lambda map without dims");
+    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("ddpm_step_rng: workspace too small"); return IPDM_ERR_WORKSPACE; }
+    float c[8];
+    int rc = ipdm_schedule_coeffs(s, t, c);
+    if (rc) return rc;
+    StepCoef k;
+    step_coef_fill(k, c, t, lambda_scalar, d_lambda_map != nullptr, H, W, mh, mw, clip_denoised);
+    const long n = (long)H * W;
+    hipStream_t st = (hipStream_t)stream;
+    double *ws = (double *)d_ws;
+    step_stats_launch(d_eps_pred, d_x_t, d_x0, d_lambda_map, n, B, k, ws, st);
+    const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(d_x_t) && aligned16(d_x0) && aligned16(d_out);
+    hipLaunchKernelGGL(step_apply_rng_kernel, dim3(quad_grid((n + 3) / 4, B), B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0,
+                       d_lambda_map, d_out, n, k, ws, (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
+    IPDM_LAUNCH_CHECK();
+    return IPDM_OK;
+}
+
+// =============================================================================== the loop
+namespace {
+
+// the carve-up of the caller's workspace (every block 256-byte aligned)
+struct Carve {
+    char *unet = nullptr; size_t unet_bytes = 0;
+    double *step = nullptr; size_t step_bytes = 0;
+    char *guid = nullptr; size_t guid_bytes = 0;
+    float *xa = nullptr, *xb = nullptr, *eps = nullptr, *guide = nullptr, *Lam = nullptr, *lr = nullptr;
+    size_t total = 0;
+};
+
+// base == NULL: sizes only (ipdm_reverse_workspace_bytes)
+Carve carve(ipdm_unet *net, int B, int H, int W, void *base)
+{
+    Carve c;
+    const size_t img = align_up((size_t)B * H * W * sizeof(float), 256);
+    c.unet_bytes = align_up(ipdm_unet_workspace_bytes(net, B, H, W), 256);
+    c.step_bytes = align_up(ipdm_ddpm_workspace_bytes(B), 256);
+    c.guid_bytes = align_up(ipdm_guidance_workspace_bytes(B, H, W), 256);
+    const size_t o_step = c.unet_bytes, o_guid = o_step + c.step_bytes, o_img = o_guid + c.guid_bytes;
+    c.total = o_img + 6 * img;         // xa, xb, eps, guide, and the two small maps ([B, H/k, W/k]: never larger than an image)
+    if (base) {
+        char *p = (char *)base;
+        c.unet = p;
+        c.step = (double *)(p + o_step);
+        c.guid = p + o_guid;
+        c.xa = (float *)(p + o_img);
+        c.xb = (float *)(p + o_img + img);
+        c.eps = (float *)(p + o_img + 2 * img);
+        c.guide = (float *)(p + o_img + 3 * img);
+        c.Lam = (float *)(p + o_img + 4 * img);
+        c.lr = (float *)(p + o_img + 5 * img);
+    }
+    return c;
+}
+
+struct PassIn {
+    const float *x_in, *guide, *Lam;     // start image, x_0 of every step, guidance map (guidance 2)
+    int mh, mw;
+    float *iter;                         // [B,H,W] out
+    float *guide_out;                    // or NULL: a*iter + b*img (+ c*ldct)
+    const float *img, *ldct;
+    double ga, gb, gc;
+    int guidance;                        // 0 constant, 1 cosine curve, 2 map
+    const float *noise;                  // injected draws of this pass, or NULL
+    int64_t draw;                        // first draw number of this pass
+};
+
+// host-side checks shared by both entries: nothing here touches a device
+int check_common(const char *who, const ipdm_schedule *s, ipdm_unet *net, int B, int H, int W, const ipdm_reverse_args *a)
+{
+    IPDM_REQUIRE(s && net && a, "%s: NULL schedule, net or args", who);
+    IPDM_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad shape %d x %d x %d", who, B, H, W);
+    IPDM_REQUIRE(a->mode == 0 || a->mode == 1, "%s: mode must be 0 (img) or 1 (proj)", who);
+    IPDM_REQUIRE(a->guidance >= 0 && a->guidance <= 2, "%s: guidance must be 0, 1 or 2", who);
+    return IPDM_OK;
+}
+
+int check_net(const char *who, ipdm_unet *net)
+{
+    int cin = 0, cout = 0;
+    IPDM_REQUIRE(unet_io_channels(net, &cin, &cout) == IPDM_OK && cin == 1 && cout == 1,
+                 "%s: the sampler runs a one-channel denoiser (net has %d -> %d)", who, cin, cout);
+    return IPDM_OK;
+}
+
+int check_ts(const char *who, const ipdm_schedule *s, int ts)
+{
+    IPDM_REQUIRE(ts > 0, "%s: a pass needs t_start > 0 (got %d)", who, ts);
+    float c[8];
+    return ipdm_schedule_coeffs(s, ts, c);      // t_start inside the schedule (q_sample gathers at ts)
+}
+
+// ONE outer pass on a carved workspace; every argument is checked by the callers
+int run_pass(const ipdm_schedule *s, ipdm_unet *net, const PassIn &p, int B, int H, int W, int ts, const ipdm_reverse_args *a,
+             const Carve &w, void *stream)
+{
+    const long n = (long)H * W;
+    const size_t bn = (size_t)B * n;
+    int rc;
+    const float *nz = p.noise;
+    // Model/model.py:537-541
+    if (nz) rc = ipdm_q_sample(s, ts, p.x_in, nz, w.xa, (int64_t)bn, stream);
+    else rc = ipdm_q_sample_rng(s, ts, p.x_in, w.xa, B, n, a->seed, a->slice_id0, p.draw, stream);
+    if (rc) return rc;
+    const bool epilogue = a->clip || p.guide_out;     // else the last step writes the pass's result itself
+    float *cur = w.xa, *nxt = w.xb;
+    for (int i = ts - 1, k = 1; i >= 0; --i, ++k) {
+        rc = ipdm_unet_forward(net, cur, i, w.eps, B, H, W, w.unet, w.unet_bytes, stream);
+        if (rc) return rc;
+        // guidance of this step (:544-560)
+        double lam = a->constant_guidance;
+        const float *lmap = nullptr;
+        if (p.guidance == 1) {
+            rc = ipdm_cosine_lambda(ts, a->lambda_power, i, &lam);
+            if (rc) return rc;
+        } else if (p.guidance == 2) {
+            rc = ipdm_lambda_ratio(p.Lam, w.lr, (int64_t)B * p.mh * p.mw, i, ts, stream);
+            if (rc) return rc;
+            lmap = w.lr;
+            lam = 0.0;
+        }
+        float *dst = (i == 0 && !epilogue) ? p.iter : nxt;
+        if (nz)
+            rc = ipdm_ddpm_step(s, i, w.eps, cur, p.guide, nz + (size_t)k * bn, dst, B, H, W, lam, lmap, p.mh, p.mw, a->clip, w.step,
+                                w.step_bytes, stream);
+        else
+            rc = ipdm_ddpm_step_rng(s, i, w.eps, cur, p.guide, a->seed, a->slice_id0, p.draw + k, dst, B, H, W, lam, lmap, p.mh, p.mw,
+                                    a->clip, w.step, w.step_bytes, stream);
+        if (rc) return rc;
+        nxt = cur;
+        cur = dst;
+    }
+    if (epilogue) {
+        EpiCoef k;
+        k.clip = a->clip; k.mode = a->mode; k.want_guide = p.guide_out != nullptr; k.has_z = p.guide_out && p.ldct;
+        k.a = (float)p.ga; k.b = (float)p.gb; k.c = (float)p.gc;
+        const int vec = (bn & 3) == 0 && aligned16(cur) && aligned16(p.iter) &&
+                        (!p.guide_out || (aligned16(p.guide_out) && aligned16(p.img) && aligned16(p.ldct)));
+        long g = vec ? (long)((bn / 4 + 255) / 256) : (long)((bn + 255) / 256);
+        if (g > 2048) g = 2048;
+        hipLaunchKernelGGL(pass_epilogue_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, cur, p.img, p.ldct, p.iter,
+                           p.guide_out, (long)bn, k, vec);
+        IPDM_LAUNCH_CHECK();
+    }
+    return IPDM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ipdm_reverse_workspace_bytes(ipdm_unet *net, int32_t B, int32_t H, int32_t W)
+{
+    if (!net || B <= 0 || H <= 0 || W <= 0) return 0;
+    return carve(net, B, H, W, nullptr).total;
+}
+
+extern "C" int ipdm_reverse_pass(const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
+                                 const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W,
+                                 int32_t ts, const ipdm_reverse_args *a, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = check_common("reverse_pass", s, net, B, H, W, a);
+    if (rc) return rc;
+    IPDM_REQUIRE(d_x_in && d_guide && d_iter && d_ws, "reverse_pass: NULL image, guide, result or workspace");
+    rc = check_ts("reverse_pass", s, ts);
+    if (rc) return rc;
+    if (a->guidance == 2)
+        IPDM_REQUIRE(d_Lambda && mh > 0 && mw > 0 && mh <= H && mw <= W, "reverse_pass: guidance 2 needs a map [B, mh <= H, mw <= W]");
+    rc = check_net("reverse_pass", net);
+    if (rc) return rc;
+    const Carve w = carve(net, B, H, W, d_ws);
+    if (ws_bytes < w.total) { set_error("reverse_pass: workspace too small (%zu < %zu)", ws_bytes, w.total); return IPDM_ERR_WORKSPACE; }
+    PassIn p = {};
+    p.x_in = d_x_in; p.guide = d_guide; p.Lam = a->guidance == 2 ? d_Lambda : nullptr;
+    p.mh = a->guidance == 2 ? mh : 0; p.mw = a->guidance == 2 ? mw : 0;
+    p.iter = d_iter; p.guide_out = nullptr; p.img = nullptr; p.ldct = nullptr;
+    p.guidance = a->guidance; p.noise = a->d_noise; p.draw = a->draw0;
+    return run_pass(s, net, p, B, H, W, ts, a, w, stream);
+}
+
+extern "C" int ipdm_guided_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_img, float *d_iters, int32_t B, int32_t H,
+                                   int32_t W, const int32_t *t_start, int32_t n_pass, const ipdm_reverse_args *a,
+                                   int64_t *draws_used, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = check_common("guided_reverse", s, net, B, H, W, a);
+    if (rc) return rc;
+    IPDM_REQUIRE(d_img && d_iters && d_ws && t_start, "guided_reverse: NULL image, result, workspace or t_start");
+    IPDM_REQUIRE(n_pass > 0, "guided_reverse: n_pass must be > 0 (got %d)", n_pass);
+    IPDM_REQUIRE(a->guidance != 2, "guided_reverse: guidance is 0 (constant) or 1 (curve on pass 0, the map it yields afterwards)");
+    for (int it = 0; it < n_pass; ++it) {
+        rc = check_ts("guided_reverse", s, t_start[it]);
+        if (rc) return rc;
+    }
+    const bool constant = a->guidance == 0;
+    const bool with_map = !constant && n_pass > 1;
+    const int ks = a->kernel_size;
+    if (with_map) IPDM_REQUIRE(ks > 0 && H >= ks && W >= ks, "guided_reverse: kernel_size %d does not fit %d x %d", ks, H, W);
+    // the guide is updated from ldct in img mode (:625-628) wherever a later pass reads it
+    if (a->mode == 0 && n_pass > 1) IPDM_REQUIRE(a->d_ldct, "guided_reverse: img mode needs d_ldct for the guide update");
+    rc = check_net("guided_reverse", net);
+    if (rc) return rc;
+    const Carve w = carve(net, B, H, W, d_ws);
+    if (ws_bytes < w.total) { set_error("guided_reverse: workspace too small (%zu < %zu)", ws_bytes, w.total); return IPDM_ERR_WORKSPACE; }
+
+    const size_t bn = (size_t)B * H * W;
+    const int mh = with_map ? H / ks : 0, mw = with_map ? W / ks : 0;
+    // guide update (:625-635): proj eta*x + (1-eta)*img; img eta*x + (0.95-eta)*img + 0.05*ldct
+    const double ga = a->eta, gb = a->mode == 1 ? 1 - a->eta : 0.95 - a->eta, gc = a->mode == 1 ? 0.0 : 0.05;
+    const float *ldct = a->mode == 1 ? nullptr : a->d_ldct;
+    const float *x = d_img, *guide = d_img;
+    int64_t draw = 0;
+    for (int it = 0; it < n_pass; ++it) {
+        const int ts = t_start[it];
+        PassIn p = {};
+        p.x_in = x; p.guide = guide;
+        p.guidance = constant ? 0 : (it == 0 ? 1 : 2);
+        p.Lam = p.guidance == 2 ? w.Lam : nullptr;
+        p.mh = p.guidance == 2 ? mh : 0; p.mw = p.guidance == 2 ? mw : 0;
+        p.iter = d_iters + (size_t)it * bn;
+        // the guide of the NEXT pass: every pass under constant guidance, passes >= 1 otherwise (:619-635); never after the last
+        const bool upd = it + 1 < n_pass && (constant || it >= 1);
+        p.guide_out = upd ? w.guide : nullptr;
+        p.img = d_img; p.ldct = ldct; p.ga = ga; p.gb = gb; p.gc = gc;
+        p.noise = a->d_noise ? a->d_noise + (size_t)draw * bn : nullptr;
+        p.draw = a->draw0 + draw;
+        rc = run_pass(s, net, p, B, H, W, ts, a, w, stream);
+        if (rc) return rc;
+        draw += ts + 1;
+        if (upd) guide = w.guide;
+        // the next pass starts from this one's result -- except after pass 0 without constant guidance: x is reset (:621-622)
+        x = (!constant && it == 0) ? d_img : p.iter;
+        if (it == 0 && with_map) {       // :574-614
+            rc = ipdm_guidance_map(p.iter, d_img, w.Lam, nullptr, B, H, W, ks, a->amplitude, a->mode, a->p1, a->p2, w.guid,
+                                   w.guid_bytes, stream);
+            if (rc) return rc;
+        }
+    }
+    if (n_pass > 1) {                    // :637-638
+        rc = ipdm_axpbypcz(d_iters + (size_t)(n_pass - 1) * bn, d_iters + (size_t)(n_pass - 2) * bn, nullptr,
+                           d_iters + (size_t)n_pass * bn, (int64_t)bn, 0.5, 0.5, 0.0, stream);
+        if (rc) return rc;
+    }
+    if (draws_used) *draws_used = draw;
+    return IPDM_OK;
+}

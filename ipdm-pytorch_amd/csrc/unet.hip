@@ -652,6 +652,15 @@ extern "C" int ipdm_unet_destroy(ipdm_unet *net)
     return IPDM_OK;
 }
 
+// input / output channel counts of a handle (sampler.hip: the reverse loop runs a one-channel denoiser)
+int ipdm::unet_io_channels(const ipdm_unet *net, int *cin, int *cout)
+{
+    if (!net || !cin || !cout) return IPDM_ERR_INVALID;
+    *cin = net->cfg.in_channels;
+    *cout = net->cfg.out_channels;
+    return IPDM_OK;
+}
+
 // ------------------------------------------------------------------------------------ forward walk
 namespace {
 

@@ -8,6 +8,7 @@ Semantics differences, by design: all statistics (`std`, `median
 a batch of B slices gives exactly what the reference gives when called B times with B=1.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -22,6 +23,10 @@ CURVE_COEFFS = {
     "proj": ([-71.02272727288062, 417.6136363644583, -893.418560607694, 800.875270564197, -234.09496753293],
              [2.3612714971236124, -14.22455278875205, 21.070551037502682]),
 }
+
+
+# Initial value of GaussianDiffusion.native_loop: IPDM_NATIVE_REVERSE=1 (read once, a debug alias like the library's own)
+_NATIVE_REVERSE = os.environ.get("IPDM_NATIVE_REVERSE", "0") not in ("", "0")
 
 
 def _stream():
@@ -87,6 +92,10 @@ class GaussianDiffusion:
         call("ipdm_schedule_create", int(timesteps), float(schedule_power), C.byref(h))
         self._h = h
         self._ws = {}
+        # guided_reverse_process on the library's own loop (ipdm_guided_reverse / ipdm_reverse_pass, csrc/sampler.hip)
+        # instead of the Python one below: same bits, one C call per process (explicit t_start) or per pass (adaptive)
+        self.native_loop = _NATIVE_REVERSE
+        self._rws = {}
 
     def __del__(self):
         try:
@@ -158,6 +167,89 @@ class GaussianDiffusion:
         _dcall(Lam, "ipdm_lambda_ratio", ptr(Lam), ptr(out), Lam.numel(), int(i), int(ts))
         return out
 
+    # ---- the library's own loop (include/ipdm_hip.h, "native reverse loop")
+    def _use_native(self, model, img, save_states):
+        """The native loop serves the library's own UNetModel on the GPU; any other callable, save_states=True (the states
+        are copied to the host step by step) and graph replay (a host-side choice of the model) keep the Python loop."""
+        from .unet import UNetModel
+        if not (self.native_loop and not save_states and isinstance(model, UNetModel) and not model.use_graph and img.is_cuda):
+            return False
+        d = model._device
+        return d.type == "cuda" and (d.index is None or d.index == img.device.index)
+
+    def _reverse_workspace(self, model, B, H, W, device):
+        """Scratch of ipdm_reverse_pass / ipdm_guided_reverse, cached by (device, B, H, W)."""
+        with torch.cuda.device(device):
+            need = lib().ipdm_reverse_workspace_bytes(model._ensure(), B, H, W)
+        key = (device, B, H, W)
+        w = self._rws.get(key)
+        if w is None or w.numel() < need:
+            w = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+            self._rws[key] = w
+        return w
+
+    def _reverse_args(self, mode, clip, guidance, constant_guidance, lambda_ratio, eta, kwargs, noise, n_draws, like, keep):
+        """ipdm_reverse_args of one native call that consumes `n_draws` draws.  A NoiseSource goes in as (seed, slice_id0,
+        draw); any other noise object is asked for the draws, in order, and they are stacked (parity mode).  `keep`
+        collects the tensors the struct points to."""
+        a = _lib.ReverseArgs()
+        a.mode = 0 if mode == "img" else 1
+        a.clip = 1 if clip else 0
+        a.guidance = guidance
+        a.constant_guidance = float(constant_guidance) if constant_guidance is not None else 0.0
+        a.lambda_power = float(lambda_ratio)
+        a.eta = float(eta)
+        p1, p2 = CURVE_COEFFS[mode]
+        a.p1[:] = p1
+        a.p2[:] = p2
+        if guidance != 0 and ("kernel_size_" + mode) in kwargs:
+            a.kernel_size = int(kwargs["kernel_size_" + mode])
+            a.amplitude = float(kwargs["amplitude_" + mode])
+        if isinstance(noise, NoiseSource):
+            a.seed, a.slice_id0, a.draw0 = noise.seed, noise.slice_id0, noise.draw
+            noise.draw += n_draws
+        else:
+            z = torch.stack([noise.next_like(like) for _ in range(n_draws)]).to(like.device, torch.float32).contiguous()
+            keep.append(z)
+            a.d_noise = z.data_ptr()
+        ldct = kwargs.get("ldct")
+        if mode == "img" and ldct is not None:
+            ld = ldct.to(like.device, torch.float32).contiguous()
+            keep.append(ld)
+            a.d_ldct = ld.data_ptr()
+        return a
+
+    def _native_process(self, model, img, t_start, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs):
+        """Explicit t_start: the whole process in ONE call (ipdm_guided_reverse).  Returns the list of raw iterates
+        (the n_pass results, then their final average when n_pass > 1)."""
+        B, _, H, W = img.shape
+        n_pass = len(t_start)
+        n_out = n_pass + (1 if n_pass > 1 else 0)
+        keep = []
+        a = self._reverse_args(mode, clip, 0 if constant_guidance is not None else 1, constant_guidance, lambda_ratio, eta,
+                               kwargs, noise, sum(int(t) + 1 for t in t_start), img, keep)
+        ws = self._reverse_workspace(model, B, H, W, img.device)
+        out = torch.empty((n_out,) + tuple(img.shape), dtype=torch.float32, device=img.device)
+        ts = (C.c_int32 * n_pass)(*[int(t) for t in t_start])
+        used = C.c_int64()
+        _dcall(img, "ipdm_guided_reverse", self._h, model._ensure(), ptr(img), ptr(out), B, H, W, ts, n_pass, C.byref(a),
+               C.byref(used), ptr(ws), ws.numel())
+        return [out[k] for k in range(n_out)]
+
+    def _native_pass(self, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs):
+        """One outer pass (q_sample, ts guided steps, the clamp) in ONE call (ipdm_reverse_pass)."""
+        B, _, H, W = x.shape
+        guidance = 0 if constant_guidance is not None else (1 if it == 0 else 2)
+        keep = []
+        a = self._reverse_args(mode, clip, guidance, constant_guidance, lambda_ratio, eta, {}, noise, int(ts) + 1, x, keep)
+        ws = self._reverse_workspace(model, B, H, W, x.device)
+        out = torch.empty_like(x)
+        lm = Lam.contiguous() if guidance == 2 else None
+        mh, mw = (lm.shape[-2], lm.shape[-1]) if lm is not None else (0, 0)
+        _dcall(x, "ipdm_reverse_pass", self._h, model._ensure(), ptr(x), ptr(guide), ptr(lm), mh, mw, ptr(out), B, H, W, int(ts),
+               C.byref(a), ptr(ws), ws.numel())
+        return out
+
     # ---- Model/model.py:517-642
     @torch.no_grad()
     def guided_reverse_process(self, model, img, t_start=None, clip=True, lambda_ratio=1, eta=0.5, save_states=False,
@@ -177,28 +269,45 @@ class GaussianDiffusion:
         adaptive = t_start is None
         t_list = [20] if adaptive else list(t_start)
         noise_strength = None
+        native = self._use_native(model, img, save_states)
+        if native and not adaptive and t_list:
+            raw = self._native_process(model, img, t_list, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs)
+            if not normal:
+                return raw, reverse_states, noise_strength
+            from .normalize import yeo_johnson_inverse_transform
+            iters_out = [yeo_johnson_inverse_transform(r.contiguous(), kwargs["transformer"]).to(torch.float32)
+                         for r in raw[:len(t_list)]]
+            if len(iters_out) > 1:      # the average is taken over the REPORTED (transformed) iterates, as below
+                avg = torch.empty_like(iters_out[-1])
+                _dcall(avg, "ipdm_axpbypcz", ptr(iters_out[-1]), ptr(iters_out[-2]), None, ptr(avg), n, 0.5, 0.5, 0.0)
+                iters_out.append(avg)
+            return iters_out, reverse_states, noise_strength
         it = 0
         Lam = None
         ldct = kwargs.get("ldct")
         while t_list:
             ts = t_list.pop(0)
-            x = self.q_sample(x, ts, noise.next_like(x))
-            for i in reversed(range(ts)):
-                if constant_guidance is None:
-                    if it == 0:
-                        l_s = cosine_lambda(ts, lambda_ratio, i)
+            if native:      # the adaptive schedule: one call per pass, the between-pass decisions below stay here
+                x = self._native_pass(model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise,
+                                      kwargs)
+            else:
+                x = self.q_sample(x, ts, noise.next_like(x))
+                for i in reversed(range(ts)):
+                    if constant_guidance is None:
+                        if it == 0:
+                            l_s = cosine_lambda(ts, lambda_ratio, i)
+                        else:
+                            l_s = self.lambda_ratio(Lam, i, ts)
                     else:
-                        l_s = self.lambda_ratio(Lam, i, ts)
-                else:
-                    l_s = constant_guidance
-                x = self.p_sample_condition(model, x, guide, i, clip_denoised=clip, lambda_=l_s,
-                                            noise=noise.next_like(x))
-                if save_states:
-                    reverse_states.append(x.detach().cpu().numpy())
-            if clip:
-                y = torch.empty_like(x)
-                _dcall(x, "ipdm_clamp", ptr(x), ptr(y), n, 0 if mode == "img" else 1)
-                x = y
+                        l_s = constant_guidance
+                    x = self.p_sample_condition(model, x, guide, i, clip_denoised=clip, lambda_=l_s,
+                                                noise=noise.next_like(x))
+                    if save_states:
+                        reverse_states.append(x.detach().cpu().numpy())
+                if clip:
+                    y = torch.empty_like(x)
+                    _dcall(x, "ipdm_clamp", ptr(x), ptr(y), n, 0 if mode == "img" else 1)
+                    x = y
             if it == 0 and constant_guidance is None:
                 if mode == "img":
                     Lam, emax = self.guidance_map(x, img, "img", kwargs["kernel_size_img"], kwargs["amplitude_img"])
