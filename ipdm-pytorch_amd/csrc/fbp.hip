@@ -30,9 +30,8 @@ extern "C" int ipdm_fbp_plan_create(const ipdm_fbp_geom *geom, ipdm_fbp_plan **o
     IPDM_REQUIRE(geom && out, "fbp_plan_create: null argument");
     IPDM_REQUIRE(geom->n_views > 1 && geom->n_det > 1 && geom->grid_n > 0 && geom->da > 0,
                  "fbp_plan_create: bad geometry");
-    // the ramp kernel visits only the taps of the parity that is non-zero for an even detector count (h_RL has its
-    // non-zero taps at even indices and at the centre N-1, Recon/FBP_kernel.py:52-56, N = 912 there)
-    IPDM_REQUIRE(geom->n_det % 2 == 0, "fbp_plan_create: n_det %d must be even", geom->n_det);
+    // (h_RL has its non-zero taps at even indices and at the centre N-1, Recon/FBP_kernel.py:52-56, N = 912 there; the ramp
+    // kernel visits the taps of that parity for an even and for an odd detector count)
     ipdm_fbp_plan *p = new ipdm_fbp_plan();
     p->g = *geom;
     const int M = geom->n_views, N = geom->n_det, G = geom->grid_n;
@@ -150,10 +149,12 @@ __global__ void __launch_bounds__(BLOCK) ramp_kernel(const float *__restrict__ s
     }
     for (int j = threadIdx.x; j < 2 * N - 1; j += BLOCK) taps[j] = h[j];
     __syncthreads();
+    const int odd = N & 1;
     for (int n = threadIdx.x; n < N; n += BLOCK) {
-        double acc = (double)row[n] * (double)taps[N - 1];
-        // j of opposite parity to n
-        for (int j = (n + 1) & 1; j < N; j += 2) acc = fma((double)row[j], (double)taps[n + N - 1 - j], acc);
+        // even N: the centre tap, then j of opposite parity to n; odd N: the centre N-1 is itself an even index, the
+        // non-zero taps are those with n - j even (j = n among them)
+        double acc = odd ? 0.0 : (double)row[n] * (double)taps[N - 1];
+        for (int j = (n + 1 + odd) & 1; j < N; j += 2) acc = fma((double)row[j], (double)taps[n + N - 1 - j], acc);
         out[rowoff + n] = (float)acc;
     }
 }

@@ -174,6 +174,11 @@ CURVES = {
 def weight_lambda(x, mode):
     """weight_lambda via np.vectorize (Utils/train_test_utils.py:831-865): float64 Horner on each
     element (np.poly1d.__call__ == polyval), output cast to f32."""
+    return weight_lambda64(x, mode).float()
+
+
+def weight_lambda64(x, mode):
+    """weight_lambda before its cast to float32 (the float64 value of the curve: the accuracy gate's reference)."""
     p1, p2 = CURVES[mode]
     x64 = x.double()
 
@@ -187,7 +192,7 @@ def weight_lambda(x, mode):
     y = torch.where(x64 < 1, horner(p1, one),
                     torch.where(x64 <= 1.7, horner(p1, x64),
                                 torch.where(x64 <= 2.75, horner(p2, x64), horner(p2, 2.75 * one))))
-    return y.float()
+    return y
 
 
 def delta_map(x, img, mode, kernel_size, amplitude):
