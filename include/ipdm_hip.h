@@ -315,6 +315,41 @@ int ipdm_art_reconstruct(ipdm_art_plan *plan, const float *d_proj, float *d_volu
 int ipdm_art_project(ipdm_art_plan *plan, const float *d_volume, float *d_proj, int32_t B, void *d_ws,
                      size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ image-quality metrics --- */
+/* The five metrics of metric_calculate (Utils/train_test_utils.py:789-806) on the device (csrc/metrics.hip), float64
+ * throughout: psnr and ssim (skimage.metrics.peak_signal_noise_ratio / structural_similarity, win_size=11, data_range=1),
+ * fsim and vif (piq.fsim(chromatic=False) / piq.vif_p, data_range=1) and nqm (Utils/NQM.py), as evaluate.py restates
+ * them.  IPDM_ABI_VERSION stays 5: the entries were added without touching an existing signature; a binder detects them
+ * by symbol (dlsym of ipdm_metrics). */
+#define IPDM_METRIC_PSNR 1u
+#define IPDM_METRIC_SSIM 2u
+#define IPDM_METRIC_FSIM 4u
+#define IPDM_METRIC_VIF 8u
+#define IPDM_METRIC_NQM 16u
+typedef struct ipdm_metrics_plan ipdm_metrics_plan;
+/* Host tables for H x W images (64 .. 8192 each way), uploaded when a device is present: the Gaussian windows of vif, and --
+ * when H and W are powers of two in 64 .. 1024, the sizes the FFT takes -- the twiddles, NQM's band filters and FSIM's filter
+ * bank with its image-independent sums.  Without a device the plan serves ipdm_metrics_table only.  Allocates and
+ * synchronises. */
+int ipdm_metrics_plan_create(int32_t H, int32_t W, ipdm_metrics_plan **out);
+int ipdm_metrics_plan_destroy(ipdm_metrics_plan *plan);
+size_t ipdm_metrics_workspace_bytes(const ipdm_metrics_plan *plan, int32_t B, uint32_t mask);
+/* d_ref [B,H,W] (ref_stride = H*W) or [1,H,W] (ref_stride = 0), d_img [B,H,W]: pixel-domain float32 (after miu2pixel); a
+ * NaN in d_img reads as 0.5 (metric_calculate's guard).  d_out [B][5] float64 in the order psnr, ssim, fsim, vif, nqm;
+ * entries outside `mask` (IPDM_METRIC_* bits) are left untouched.  Every reduction is per slice in a fixed order: a batch
+ * is bit-equal to single-slice calls.  nqm or fsim in the mask of a plan whose size the FFT does not take is refused with
+ * IPDM_ERR_UNSUPPORTED before any launch (a binder scores those two on the host); a short workspace with
+ * IPDM_ERR_WORKSPACE.  Asynchronous on `stream`, allocates nothing, does not synchronise. */
+int ipdm_metrics(ipdm_metrics_plan *plan, const float *d_ref, int64_t ref_stride, const float *d_img, int32_t B,
+                 uint32_t mask, double *d_out, void *d_ws, size_t ws_bytes, void *stream);
+/* host copies of the plan's float64 tables, callable without a GPU like ipdm_fbp_table: which = 0..5 NQM's six cosine-log
+ * bands [H*W] (evaluate.NQM's `filters`, fftshift'ed: the form the spectrum is multiplied with); 6 + 4*o + s FSIM's
+ * lowpass x log-Gabor x angular-spread filter of orientation o, scale s [h*w] at the size fsim works on (2x2 block means when
+ * round(min(H,W)/256) > 1); 22 sum_an2[4], 23 sum_aiaj[4], 24 sum(filt[0]^2)[4] per orientation; 25 the four normalised
+ * Gaussian windows of vif, concatenated (17^2 + 9^2 + 5^2 + 3^2).  Returns the element count, or < 0
+ * (IPDM_ERR_UNSUPPORTED for 0..24 on a size the FFT does not take). */
+int64_t ipdm_metrics_table(const ipdm_metrics_plan *plan, int32_t which, void *host_out, int64_t cap_elems);
+
 /* ------------------------------------------------------------------ measurement ------------- */
 /* Per-launch HIP-event timing of the hot kernels on their launch stream (bench.py roofline leg; no
  * reference counterpart -- the reference has no profiling).  Classes: 0 = conv 3x3

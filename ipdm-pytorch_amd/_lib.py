@@ -114,6 +114,11 @@ PROTOTYPES = {
     "ipdm_art_workspace_bytes": (C.c_size_t, [_vp, _i32]),
     "ipdm_art_reconstruct": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),
     "ipdm_art_project": (C.c_int, [_vp, _vp, _vp, _i32, _vp, C.c_size_t, _vp]),
+    "ipdm_metrics_plan_create": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+    "ipdm_metrics_plan_destroy": (C.c_int, [_vp]),
+    "ipdm_metrics_workspace_bytes": (_sz, [_vp, _i32, C.c_uint32]),
+    "ipdm_metrics": (C.c_int, [_vp, _vp, _i64, _vp, _i32, C.c_uint32, _vp, _vp, _sz, _vp]),
+    "ipdm_metrics_table": (_i64, [_vp, _i32, _vp, _i64]),
 }
 
 _lib = None

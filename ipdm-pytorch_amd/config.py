@@ -37,7 +37,20 @@ _FLAGS = [
     ("test_numbers", int, 50, None), ("data_type", str, "siemens", None),
     ("test_dataset_path_FD_img", str, None, None), ("test_dataset_path_LD_img", str, None, None),
     ("test_dataset_path_FD_proj", str, None, None), ("test_dataset_path_LD_proj", str, None, None),
+    # where metric_calculate's five metrics run (no reference counterpart): "numpy" = the host functions of evaluate.py, "hip" =
+    # the float64 kernels of csrc/metrics.hip, one call per scored slice.  test_batch_size (above; the reference defines the key
+    # and never reads it on this path) > 1 makes test() run the denoisers on that many slices at once; in adaptive mode
+    # (t_start_proj=None) such a batch takes the branch of its maximum, as guided_reverse_process does for any batch.
+    ("metrics_backend", str, "numpy", None),
 ]
+METRICS_BACKENDS = ("numpy", "hip")
+
+
+def check_metrics_backend(value):
+    """An unknown metrics_backend is refused (argparse `choices` for the command line; this for a JSON overlay or update_opt)."""
+    if value not in METRICS_BACKENDS:
+        raise ValueError("metrics_backend must be one of %s, not %r" % (METRICS_BACKENDS, value))
+    return value
 
 
 def default_cfg(argv=None):
@@ -48,12 +61,15 @@ def default_cfg(argv=None):
         kw = dict(type=typ, default=default)
         if nargs:
             kw["nargs"] = nargs
+        if name == "metrics_backend":
+            kw["choices"] = METRICS_BACKENDS
         parser.add_argument("--" + name, **kw)
     argv = sys.argv[1:] if argv is None else argv
     opt = parser.parse_args(argv)
     given = [a[2:] for a in argv if "--" in a]
     if opt.load_option_path is not None:
         load_option(opt, opt.load_option_path, given)
+    check_metrics_backend(opt.metrics_backend)
     return opt
 
 

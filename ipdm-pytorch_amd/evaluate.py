@@ -212,6 +212,133 @@ def fsim(x, y, data_range=1.0, chromatic=False):
     return float(np.sum(s_g * s_pc * pc_max) / np.sum(pc_max))
 
 
+# ----------------------------------------------------------------------------------------------- metrics on the device
+METRIC_NAMES = ("psnr", "ssim", "fsim", "vif", "nqm")             # the column order of ipdm_metrics' [B][5] block
+_METRIC_BITS = dict(psnr=1, ssim=2, fsim=4, vif=8, nqm=16)
+_HOST_METRIC = dict(psnr=lambda r, x: compare_psnr(r, x, data_range=1), ssim=lambda r, x: compare_ssim(r, x, win_size=11, data_range=1),
+                    fsim=lambda r, x: fsim(r, x, data_range=1, chromatic=False), vif=lambda r, x: vif_p(r, x, data_range=1),
+                    nqm=lambda r, x: NQM(r, x))
+
+
+class MetricsPlan:
+    """ipdm_metrics_plan of one image size: the float64 host tables (uploaded when a device is present) and, once used on a
+    device, a workspace that grows to the largest batch scored."""
+
+    def __init__(self, H, W):
+        import ctypes as C
+        from . import _lib
+        self.H, self.W = int(H), int(W)
+        h = C.c_void_p()
+        _lib.call("ipdm_metrics_plan_create", self.H, self.W, C.byref(h))
+        self.handle = h
+        self.fft_ok = _lib.lib().ipdm_metrics_table(h, 0, None, 0) > 0
+        self._ws = None
+
+    def table(self, which):
+        """Host copy of table `which` (include/ipdm_hip.h: ipdm_metrics_table) as a float64 array; needs no GPU."""
+        from . import _lib
+        n = _lib.lib().ipdm_metrics_table(self.handle, int(which), None, 0)
+        if n < 0:
+            raise _lib.IpdmError("ipdm_metrics_table(%d) failed (%d): %s" % (which, n, _lib.lib().ipdm_last_error().decode()))
+        out = np.empty(n, np.float64)
+        _lib.lib().ipdm_metrics_table(self.handle, int(which), _lib.ptr(out), n)
+        return out
+
+    def workspace(self, B, mask, device):
+        from . import _lib
+        need = _lib.lib().ipdm_metrics_workspace_bytes(self.handle, int(B), int(mask))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._ws
+
+    def __del__(self):
+        try:
+            from . import _lib
+            _lib.lib().ipdm_metrics_plan_destroy(self.handle)
+        except Exception:                                          # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+_PLANS = {}
+
+
+def metrics_plan(H, W):
+    key = (int(H), int(W))
+    if key not in _PLANS:
+        _PLANS[key] = MetricsPlan(*key)
+    return _PLANS[key]
+
+
+def metrics_hip(ref, imgs, names=METRIC_NAMES, plan=None, device=None):
+    """The metrics `names` of every image of `imgs` [N,H,W] against `ref` [H,W] (pixel domain, as metric_calculate scores
+    them; a NaN in `imgs` reads as 0.5) on the GPU: ONE ipdm_metrics call (csrc/metrics.hip, float64 throughout) and one
+    device-to-host copy of N x 5 doubles.  `ref` / `imgs` are device tensors or numpy arrays (uploaded).  Returns a list of N
+    dicts {name: float} in the order of `names`.  On a size the device FFT does not take (H or W not a power of two in
+    64..1024) nqm and fsim are scored by the host functions; everything else has no host fall-back: a failing call raises."""
+    from . import _lib
+    names = list(names)
+    for k in names:
+        if k not in _METRIC_BITS:
+            raise ValueError("metrics_hip: unknown metric %r" % (k,))
+    dev = torch.device(device) if device is not None else (imgs.device if isinstance(imgs, torch.Tensor) and imgs.is_cuda
+                                                           else torch.device("cuda", torch.cuda.current_device()))
+    ref_np = ref if not isinstance(ref, torch.Tensor) else None
+    imgs_np = imgs if not isinstance(imgs, torch.Tensor) else None
+    r = (ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)))
+    x = (imgs if isinstance(imgs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(imgs, dtype=np.float32)))
+    r = r.to(dev, torch.float32).contiguous()
+    x = x.to(dev, torch.float32).contiguous()
+    if x.dim() == 2:
+        x = x[None]
+    N, H, W = x.shape
+    if tuple(r.shape[-2:]) != (H, W) or r.numel() != H * W:
+        raise ValueError("metrics_hip: ref must be one [H,W] image of the size of imgs")
+    plan = metrics_plan(H, W) if plan is None else plan
+    if (plan.H, plan.W) != (H, W):
+        raise ValueError("metrics_hip: plan is for %dx%d images, got %dx%d" % (plan.H, plan.W, H, W))
+    on_host = [k for k in names if k in ("nqm", "fsim") and not plan.fft_ok]
+    mask = sum(_METRIC_BITS[k] for k in names if k not in on_host)
+    res = None
+    if mask:
+        with torch.cuda.device(dev):
+            out = torch.zeros((N, 5), dtype=torch.float64, device=dev)
+            ws = plan.workspace(N, mask, dev)
+            _lib.call("ipdm_metrics", plan.handle, _lib.ptr(r), 0, _lib.ptr(x), N, mask, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                      _lib.current_stream())
+            res = out.cpu().numpy()
+    if on_host:
+        ref_np = r.cpu().numpy().reshape(H, W) if ref_np is None else np.asarray(ref_np, dtype=np.float32).reshape(H, W)
+        imgs_np = x.cpu().numpy() if imgs_np is None else np.asarray(imgs_np, dtype=np.float32).reshape(N, H, W)
+        imgs_np = np.where(np.isnan(imgs_np), np.float32(0.5), imgs_np)
+    return [{k: (float(_HOST_METRIC[k](ref_np, imgs_np[i])) if k in on_host else float(res[i, METRIC_NAMES.index(k)]))
+             for k in names} for i in range(N)]
+
+
+# (module-level: they serve any object that carries the harness's attributes, like the methods of EvaluationMixin)
+def _metrics_backend(self):
+    """opt.metrics_backend of a harness object ("numpy" when the key is absent); an unknown value is refused."""
+    from .config import check_metrics_backend
+    return check_metrics_backend(getattr(self.opt, "metrics_backend", "numpy"))
+
+def _metric_prefetch(self, mode):
+    """metrics_backend="hip": every image result_figure_save(mode) is about to score, in its order, scored in one call;
+    metric_calculate then takes each from the cache (same keys, same order, Python floats)."""
+    from .denoiser import miu2pixel
+    todo = [("LDCT", 0, self.ldct_np)]
+    if mode == "progressive":
+        top, store = self.proj_denoise_convert2img_result, self.progressive_denoise_result
+        todo += [("deProj", i, miu2pixel(top["iter_%d" % i][0, 0])) for i in range(1, len(top) + 1)]
+        todo += [("deProg", it, miu2pixel(store["iter_%d" % it][0, 0])) for it in range(len(store), 0, -1)]
+    else:
+        store, key = {"dimg": (self.img_denoise_result, "deImg"), "dproj2img": (self.proj_denoise_convert2img_result, "deProj2img")}[mode]
+        todo += [(key, it, miu2pixel(store["iter_%d" % it][0, 0])) for it in range(len(store), 0, -1)]
+    want = [k for k in METRIC_NAMES if k in self.opt.metrics]
+    self._metric_cache = {}
+    if want:
+        got = metrics_hip(self.fdct, np.stack([np.asarray(t[2], dtype=np.float32) for t in todo]), want, device=self.opt.device)
+        self._metric_cache = {(t[0], t[1]): g for t, g in zip(todo, got)}
+
+
 # ----------------------------------------------------------------------------------------------- metric bookkeeping
 def aggregate_metrics(samples):
     """metric_total_save's arithmetic (Utils/train_test_utils.py:59-118, 812-822): per key the mean over the samples
@@ -332,6 +459,14 @@ class EvaluationMixin:
         i, ld = kwargs["it"], kwargs["denoise_result"]
         ld[np.isnan(ld)] = 0.5
         m, want = self.metric_instance[mode], self.opt.metrics
+        if _metrics_backend(self) == "hip":
+            got = self._metric_cache.pop((mode, i), None) if getattr(self, "_metric_cache", None) else None
+            if got is None:
+                got = metrics_hip(self.fdct, ld[None], [k for k in METRIC_NAMES if k in want], device=self.opt.device)[0]
+            for k in ("psnr", "ssim", "fsim", "vif", "nqm"):
+                if k in want:
+                    m["%s_iter_%d" % (k, i)] = got[k]
+            return
         if "psnr" in want:
             m["psnr_iter_%d" % i] = float(compare_psnr(self.fdct, ld, data_range=1))
         if "ssim" in want:
@@ -433,6 +568,8 @@ class EvaluationMixin:
                 ax[0, k].imshow(r, "inferno", vmin=lo, vmax=hi)
             savefig("dProj.png", 100)
         else:
+            if _metrics_backend(self) == "hip":
+                _metric_prefetch(self, mode)
             self.metric_calculate(mode="LDCT", it=0, denoise_result=self.ldct_np)
             if mode == "progressive":
                 top, store, key = self.proj_denoise_convert2img_result, self.progressive_denoise_result, "deProg"
@@ -484,8 +621,57 @@ class EvaluationMixin:
                                                 fdproj_path=o.test_dataset_path_FD_proj, proj_clip=o.clip_proj,
                                                 img_clip=o.clip_img, data_type=o.data_type)
 
+    def _test_batched(self, epoch, ids, B):
+        """test() with test_batch_size = B > 1: the denoisers run once per batch of B stacked samples (the last batch may be
+        short), then every slice is scored and written from its own row -- the same files, in the same tree, as the B = 1 loop
+        writes.  Slice b of a batch draws its noise under slice id slice_id0 + b, as the pipeline does for any batch, while
+        the B = 1 loop gives every sample slice_id0: a batched run is a different, equally valid realisation of the sampler's
+        noise, not the bits of the unbatched run.  In adaptive mode (t_start_proj=None) a batch takes the branch of its
+        maximum, as guided_reverse_process does for any batch."""
+        o = self.opt
+        ds = self.test_dataset
+        for lo in range(0, len(ids), B):
+            chunk = [int(i) for i in ids[lo:lo + B]]
+            ld_img, fd_proj, fd_img, ld_proj = ds.collate([ds[i] for i in chunk])
+            self.temp_clear()
+            self.data_sample_load(ldct=ld_img, ldproj=ld_proj, fdproj=None, fdct=None)
+            if o.mode in ("train_proj", "test_proj"):
+                self.proj_denoiser(self.ldproj)
+                fig_mode = "dproj2img"
+            elif o.mode in ("train_img", "test_img"):
+                self.img_denoiser(self.ldct, mode="img_only")
+                fig_mode = "dimg"
+            elif o.mode == "test_prog":
+                self.progressive_denoiser()
+                fig_mode = "progressive"
+            else:
+                fig_mode = None
+            from .denoiser import miu2pixel
+            names = ("proj_denoise_result", "proj_denoise_convert2img_result", "img_denoise_result", "progressive_denoise_result")
+            whole = {n: getattr(self, n) for n in names}
+            for b, i in enumerate(chunk):
+                for n in names:                                    # this slice's row of every stored iterate, as [1,1,H,W]
+                    setattr(self, n, type(whole[n])({k: v[b:b + 1] for k, v in whole[n].items()}))
+                # the host-side views of this row that scoring and the figures read, as data_sample_load makes them for one
+                # sample (nothing is uploaded or refitted: the device tensors and the fitted transforms stay the batch's)
+                self.ldct_np = miu2pixel(ld_img[b].squeeze().cpu().numpy())
+                self.ldproj_np = None if ld_proj is None else ld_proj[b].squeeze().cpu().numpy()
+                self.fdct = miu2pixel(fd_img[b:b + 1]).squeeze().numpy()
+                self.fdproj = None if fd_proj is None else fd_proj[b].squeeze().numpy()
+                self.metric_clear()
+                self.save_path_load(epoch, ds.patient_name[i], ds.slice_name[i])
+                if fig_mode is not None:
+                    self.result_figure_save(mode=fig_mode, display=False, only_metric=not o.display_result)
+                self.result_data_save(data_save=o.test_result_data_save)
+                self.metric_update()
+            for n in names:
+                setattr(self, n, whole[n])
+
     @torch.no_grad()
     def test(self, epoch):
+        """Scores the test dataset slice by slice (Utils/train_test_utils.py:274-348).  Option test_batch_size > 1 runs the
+        denoisers on that many slices at once (_test_batched: same files, another realisation of the noise); option
+        metrics_backend="hip" scores on the GPU (metrics_hip)."""
         o = self.opt
         if self.test_dataset is None:
             self.init_data_loader()
@@ -493,6 +679,10 @@ class EvaluationMixin:
             o.test_numbers = len(self.test_dataset)
         np.random.seed(9527)
         ids = np.sort(np.random.choice(len(self.test_dataset), o.test_numbers, replace=False))
+        if int(getattr(o, "test_batch_size", 1) or 1) > 1:
+            self._test_batched(epoch, ids, int(o.test_batch_size))
+            self.metric_total_save(epoch)
+            return
         for idx in range(o.test_numbers):
             ld_img, fd_proj, fd_img, ld_proj = self.test_dataset[ids[idx]]
             ld_img, fd_img = ld_img[None], fd_img[None]
