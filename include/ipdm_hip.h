@@ -350,6 +350,28 @@ int ipdm_metrics(ipdm_metrics_plan *plan, const float *d_ref, int64_t ref_stride
  * (IPDM_ERR_UNSUPPORTED for 0..24 on a size the FFT does not take). */
 int64_t ipdm_metrics_table(const ipdm_metrics_plan *plan, int32_t which, void *host_out, int64_t cap_elems);
 
+/* ------------------------------------------------------------------ low-dose simulation ----- */
+/* Dose noise injected into clean sinograms (csrc/lowdose.hip): the noise stage of Utils/Low_dose_CT_simulate.py, whose other
+ * stages (recons_torch, proj_torch, FBP.convert) are the entries above.  IPDM_ABI_VERSION stays 5: the entries were added
+ * without touching an existing signature; a binder detects them by symbol (dlsym of ipdm_lowdose_noise).
+ *
+ * replaces add_noise (Utils/Low_dose_CT_simulate.py:38-44) and the per-slice loop around it (worker, :21-32) for a batch
+ * [B, n_per_slice] of line integrals p, with dose fraction `factor` in (0, 1], incident photons n0 (the reference's 1.4e5) and
+ * electronic-noise variance ne (5.8):
+ *   model 0 (add_noise)      out = p + sqrt((1-f) e^p (1 + (1+f) ne e^p / (f n0)) / (f n0)) z1
+ *   model 1 (counts domain)  lambda = n0 f e^-p;  n = max(lambda + sqrt(lambda) z1 + sqrt(ne) z2, 1);  out = -log(n / (n0 f))
+ * evaluated in float64 from the float32 inputs and rounded once.  d_z1, d_z2 [B, n_per_slice]: N(0,1) draws of the caller
+ * (np.random.randn at :41); d_z2 may be NULL for model 0.  d_out == d_proj is allowed.  Any n_per_slice; accesses are 16 bytes
+ * wide when the pointers are 16-byte aligned.  factor outside (0, 1], n0 <= 0, ne < 0 or another model: IPDM_ERR_INVALID
+ * before any launch.  Asynchronous on `stream`, allocates nothing, does not synchronise. */
+int ipdm_lowdose_noise(const float *d_proj, const float *d_z1, const float *d_z2, float *d_out, int32_t B,
+                       int64_t n_per_slice, double factor, double n0, double ne, int32_t model, void *stream);
+/* ... with the draws made in registers: z1 is draw `draw0`, z2 (model 1) draw `draw0 + 1` of ipdm_randn's generator for
+ * (seed, slice_id0 + b, element).  Same bits as ipdm_randn into buffers followed by ipdm_lowdose_noise; a batch is its slices,
+ * so results do not depend on how slices are batched or sharded. */
+int ipdm_lowdose_noise_rng(const float *d_proj, float *d_out, int32_t B, int64_t n_per_slice, double factor, double n0,
+                           double ne, int32_t model, uint64_t seed, int64_t slice_id0, int64_t draw0, void *stream);
+
 /* ------------------------------------------------------------------ measurement ------------- */
 /* Per-launch HIP-event timing of the hot kernels on their launch stream (bench.py roofline leg; no
  * reference counterpart -- the reference has no profiling).  Classes: 0 = conv 3x3

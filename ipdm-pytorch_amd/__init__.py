@@ -5,6 +5,7 @@ sampling hot path, behind the reference's own call surface.
   GaussianDiffusion.guided_reverse_process                           (Model/model.py:517-642)
   UNetModel.forward                                                  (Model/model.py:283-310)
   FBP.convert                                                        (Recon/FBP_kernel.py:86-122)
+  add_noise / init_convertor / ldct_simulate                         (Utils/Low_dose_CT_simulate.py; simulate.py)
 
 All arithmetic runs in libipdm_hip.so (hand-written HIP, C ABI in include/ipdm_hip.h); torch is
 used for device memory, streams and torch.distributed only.  There is no CPU fallback.
@@ -19,6 +20,7 @@ _LAZY = {
     "default_cfg": "config", "cfg_load": "config",
     "GaussianDiffusion": "diffusion", "NoiseSource": "diffusion", "InjectedNoise": "diffusion",
     "UNetModel": "unet", "FBP": "fbp", "tensor_sharpen": "fbp",
+    "add_noise": "simulate", "init_convertor": "simulate", "ldct_simulate": "simulate", "LowDoseSimulator": "simulate",
 }
 __all__ += list(_LAZY)
 

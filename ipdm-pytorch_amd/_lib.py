@@ -119,6 +119,8 @@ PROTOTYPES = {
     "ipdm_metrics_workspace_bytes": (_sz, [_vp, _i32, C.c_uint32]),
     "ipdm_metrics": (C.c_int, [_vp, _vp, _i64, _vp, _i32, C.c_uint32, _vp, _vp, _sz, _vp]),
     "ipdm_metrics_table": (_i64, [_vp, _i32, _vp, _i64]),
+    "ipdm_lowdose_noise": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _f64, _f64, _f64, _i32, _vp]),
+    "ipdm_lowdose_noise_rng": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _f64, _f64, _i32, _u64, _i64, _i64, _vp]),
 }
 
 _lib = None

@@ -121,13 +121,16 @@ class ArtPlan:
 _PLANS = {}
 
 
-def _plan_for(lut_area, betas, device):
-    """recons_torch / proj_torch take the tables on every call; the plan built from them is cached by content."""
+def _plan_for(lut_area, betas, device, geom=None):
+    """recons_torch / proj_torch take the tables on every call; the plan built from them is cached by content (and by the
+    geometry, when one other than the reference's hard-coded `params` is asked for)."""
     lut = np.ascontiguousarray(np.asarray(lut_area, dtype=np.float32))
     bet = np.ascontiguousarray(np.asarray(betas, dtype=np.float32))
     key = (str(torch.device(device)), lut.size, bet.size, hash(lut.tobytes()), hash(bet.tobytes()))
+    if geom is not None:
+        key += (bytes(geom),)
     if key not in _PLANS:
-        _PLANS[key] = ArtPlan(lut, bet, device=device)
+        _PLANS[key] = ArtPlan(lut, bet, device=device, geom=geom)
     return _PLANS[key]
 
 
@@ -137,19 +140,19 @@ def _device_of(t, device):
     return t.device if t.device.type == "cuda" else torch.device("cuda:0")
 
 
-def recons_torch(h_proj, lut_area, betas, nstart, ntv, sample_rate=1, permute=True, device=None):
+def recons_torch(h_proj, lut_area, betas, nstart, ntv, sample_rate=1, permute=True, device=None, geom=None):
     """Same call as Recon/TASART2DNSL0.recons_torch (TASART2DNSL0.pyi:5-16): h_proj [B, 2000, 912] -> [B, 512, 512],
     transposed when `permute` (a view, PyAPI.cpp:55-57).  A CPU tensor comes back on the CPU (the reference returns a
-    host tensor), a CUDA tensor stays on its device."""
-    plan = _plan_for(lut_area, betas, _device_of(h_proj, device))
+    host tensor), a CUDA tensor stays on its device.  `geom` (an ArtGeom, not in the reference's call) plans another grid."""
+    plan = _plan_for(lut_area, betas, _device_of(h_proj, device), geom)
     out = plan.reconstruct_device(h_proj, nstart, ntv, sample_rate)
     if permute:
         out = out.permute(0, 2, 1)
     return out if h_proj.device.type == "cuda" else out.cpu()
 
 
-def proj_torch(h_volume, lut_area, betas, device=None):
+def proj_torch(h_volume, lut_area, betas, device=None, geom=None):
     """Same call as Recon/TASART2DNSL0.proj_torch (TASART2DNSL0.pyi:18-24): h_volume [B, 512, 512] -> [B, 2000, 912]."""
-    plan = _plan_for(lut_area, betas, _device_of(h_volume, device))
+    plan = _plan_for(lut_area, betas, _device_of(h_volume, device), geom)
     out = plan.project_device(h_volume)
     return out if h_volume.device.type == "cuda" else out.cpu()
