@@ -365,16 +365,10 @@ static int launch_conv(const ConvArgs &args, hipStream_t st)
 
 namespace ipdm {
 
-int conv2d_launch(const ConvArgs &a, hipStream_t st)
+// the 4-wave kernels of this file: what neither the wave-specialised family (packed weights) nor the direct kernel takes
+int conv2d_igemm_launch(const ConvArgs &a, hipStream_t st)
 {
-    IPDM_REQUIRE(a.x1 && a.w && a.out && a.B > 0 && a.Cout > 0 && a.C1 > 0, "conv2d: bad argument");
-    IPDM_REQUIRE(a.C2 == 0 || a.x2, "conv2d: second source missing");
-    IPDM_REQUIRE(!a.act || (a.gn_scale && a.gn_shift), "conv2d: GN prologue without scale/shift");
     const bool wide = a.Cout > 32;
-    // wide 3x3 convolutions (>80 % of the path's FLOPs) run on the persistent wave-specialised kernel (conv_ws.hip);
-    // when their weights were packed for it (conv_weight_interleave); IPDM_CONV_LEGACY=1 at pack time keeps them here
-    if (a.w_interleave) return conv_pw_eligible(a) ? conv2d_pw_launch(a, st) : conv2d_ws_launch(a, st);      // (1x1: conv_pw.hip)
-    if (!opt(OPT_CONV_NO_DIRECT) && conv_direct_eligible(a)) return conv2d_direct_launch(a, st);
     if (a.ksize == 3 && a.stride == 1) return wide ? launch_conv<3, 1, 2, 2, 8>(a, st) : launch_conv<3, 1, 1, 2, 8>(a, st);
     if (a.ksize == 3 && a.stride == 2) return wide ? launch_conv<3, 2, 2, 1, 8>(a, st) : launch_conv<3, 2, 1, 1, 8>(a, st);
     if (a.ksize == 1 && a.stride == 1) return wide ? launch_conv<1, 1, 2, 2, 8>(a, st) : launch_conv<1, 1, 1, 2, 8>(a, st);
@@ -382,42 +376,7 @@ int conv2d_launch(const ConvArgs &a, hipStream_t st)
     return IPDM_ERR_UNSUPPORTED;
 }
 
-// mirrors the dispatch of conv2d_launch: WHICH kernel this convolution runs on now (ipdm_conv_kernel_code)
-int conv_kernel_code(const ConvArgs &a)
-{
-    if (a.w_interleave) {
-        if (conv_pw_eligible(a)) return 10;
-        if (conv_up2_eligible(a)) return conv_wup2_eligible(a) ? 11 : 7;
-        if (conv_wino_eligible(a)) {
-            if (a.split_ws && conv_split(a) > 1) return 9;
-            if (conv_wino3_eligible(a)) return 12;
-            return (!opt(OPT_WINO_V1) && conv_wino2_eligible(a)) ? 2 : 1;
-        }
-        return (a.split_ws && conv_ws_split(a) > 1) ? 4 : 3;
-    }
-    if (!opt(OPT_CONV_NO_DIRECT) && conv_direct_eligible(a)) return conv_nm_eligible(a) ? 6 : 5;
-    return 8;
-}
-
-// mirrors the dispatch of conv2d_launch: rows of fused output statistics of the kernel this convolution runs on
-int conv_stats_rows(const ConvArgs &a)
-{
-    if (a.w_interleave) return conv_pw_stats_layer(a) ? conv_pw_stats_rows(a) : conv_ws_stats_rows(a);      // (asked for layers that want statistics)
-    if (!opt(OPT_CONV_NO_DIRECT) && conv_direct_eligible(a)) return conv_direct_stats_rows(a);
-    return a.Ho * cdiv(a.Wo, 32);                                       // the 4-wave kernels below: a row per pixel row and tile column
-}
-
-int conv_split(const ConvArgs &a)
-{
-    if (!a.w_interleave || conv_pw_layer_ok(a)) return 1;      // (conv_pw's layers are never K-split ones)
-    if (conv_wino_eligible(a)) return conv_ws_split(a) > 1 ? conv_wino_split(a) : 1;      // (K slices inside conv_wino2)
-    return conv_ws_split(a);
-}
-size_t conv_split_ws_bytes(const ConvArgs &a)
-{
-    const int S = conv_split(a);
-    return S > 1 ? (size_t)S * a.B * a.Cout * a.Ho * a.Wo * sizeof(float) : 0;
-}
+int conv_igemm_stats_rows(const ConvArgs &a) { return a.Ho * cdiv(a.Wo, 32); }      // a row per pixel row and tile column
 
 int conv_k_chunk() { return 8; }
 int conv_ws_k_chunk(int ks, int interleave) { return (interleave && ks == 1) ? 32 : 8; }
@@ -446,16 +405,6 @@ void conv_pack_weights_up2(const float *w, int Cout, int Cin, int interleave, st
         conv_pack_weights(w2.data(), Cout, Cin, 2, interleave, one, cin_pad, cout_pad);
         packed.insert(packed.end(), one.begin(), one.end());
     }
-}
-
-bool conv_planar_ok(const ConvArgs &a)
-{
-    if (a.upsample || (a.Hs & 1) || (a.Ws & 1)) return false;
-    // (a layer of the pointwise kernel may still land on conv_ws.hip -- a low-fill launch without fused statistics -- so the
-    //  producer's layout decision follows the STRICTER reader: conv_ws_planar_ok; conv_pw itself only needs even Ho / Wo)
-    if (a.w_interleave) return conv_ws_planar_ok(a);                    // the wave-specialised kernels (conv_ws.hip)
-    // (the stride-2 direct kernel and the 4-wave kernels below read NCHW only)
-    return a.stride == 1 && !opt(OPT_CONV_NO_DIRECT) && !opt(OPT_DIRECT_NO_PLANAR) && conv_direct_eligible(a);
 }
 
 namespace {

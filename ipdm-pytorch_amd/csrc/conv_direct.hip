@@ -472,6 +472,7 @@ bool conv_direct_skip_ok(const ConvArgs &a)
 
 int conv2d_direct_launch(const ConvArgs &a, hipStream_t st)
 {
+    IPDM_REQUIRE(conv_direct_eligible(a), "conv2d_direct: layer not eligible");
     IPDM_REQUIRE(!a.stats || a.stats_rows == conv_direct_stats_rows(a), "conv2d: statistics rows %d != %d", a.stats_rows,
                  conv_direct_stats_rows(a));
     IPDM_REQUIRE(!a.x1_planar || (!a.upsample && !(a.Hs & 1) && !(a.Ws & 1)), "conv2d: parity-planar input of odd size %dx%d", a.Hs, a.Ws);
@@ -483,7 +484,6 @@ int conv2d_direct_launch(const ConvArgs &a, hipStream_t st)
     IPDM_REQUIRE(!a.sk_w || ((long)a.sk_C1 * a.Hs * a.Ws < (1L << 29) && (long)(a.sk_C2 + 1) * a.Hs * a.Ws < (1L << 29)),
                  "conv2d: the fused shortcut's source exceeds the 2 GiB buffer-addressing range");
     IPDM_REQUIRE(!a.sk_w || !a.sk_planar || (!(a.Hs & 1) && !(a.Ws & 1)), "conv2d: parity-planar shortcut source of odd size %dx%d", a.Hs, a.Ws);
-    if (!a.sk_w && conv_nm_eligible(a)) return conv2d_nm_launch(a, st);      // same tiles, same statistics rows: interchangeable
     if (a.stride == 2) {
         if (a.Cout <= 4) return launch_direct_s2<4>(a, st);
         if (a.Cout <= 8) return launch_direct_s2<8>(a, st);

@@ -320,7 +320,7 @@ static bool conv_nm_eligible_impl(const ConvArgs &a)
 
 static int conv2d_nm_launch_impl(const ConvArgs &a, hipStream_t st)
 {
-    IPDM_REQUIRE(conv_nm_eligible_impl(a), "conv2d_nm: layer not eligible");
+    IPDM_REQUIRE(conv_nm_eligible_impl(a) && !a.sk_w, "conv2d_nm: layer not eligible (a fused shortcut stays on conv_direct)");
     IPDM_REQUIRE(!a.stats || a.stats_rows == conv_direct_stats_rows(a), "conv2d_nm: statistics rows %d != %d", a.stats_rows, conv_direct_stats_rows(a));
     IPDM_REQUIRE((long)a.C1 * a.Hs * a.Ws < (1L << 29) && (long)(a.C2 + 1) * a.Hs * a.Ws < (1L << 29) && (long)a.Cout * a.Ho * a.Wo < (1L << 29),
                  "conv2d_nm: per-sample tensor exceeds the 2 GiB buffer-addressing range");

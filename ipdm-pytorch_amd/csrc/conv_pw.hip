@@ -244,7 +244,7 @@ __global__ void __launch_bounds__(512) conv_pw_kernel(ConvArgs a, int nitems)
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(a.out + sample), 0, a.Cout * plane_bytes, 0x00020000);
         // (no residual: zero records -- the loads return 0 and the add stays unconditional)
         // (the GroupNorm instantiations -- the qkv projections -- have no residual path: no layer of the reference normalises the
-        //  input of a 1x1 AND adds a residual, conv_pw_layer_ok refuses such a layer, and the 32 registers of the residual
+        //  input of a 1x1 AND adds a residual, conv_pw_eligible refuses such a layer, and the 32 registers of the residual
         //  prefetch were what made the ACT / 64-pixel instantiations spill next to the register ring: ADVICE r04.  The Makefile
         //  refuses a build in which any instantiation of this kernel spills a vector register)
         const bool has_res = !ACT && a.res;
@@ -339,17 +339,16 @@ __global__ void __launch_bounds__(512) conv_pw_kernel(ConvArgs a, int nitems)
 namespace ipdm {
 
 // The layers this kernel CAN take: every wide 1x1 with whole 128-cout groups and whole 32-channel chunks (all of the reference
-// architectures' qkv / proj_out / shortcut layers from 128 couts up), except the few low-resolution ones conv_ws.hip splits
-// along K (conv_ws_split: a rule of the layer alone).
-bool conv_pw_layer_ok(const ConvArgs &a)
+// architectures' qkv / proj_out / shortcut layers from 128 couts up; the plan keeps the few low-resolution ones that are split
+// along K away from it).
+static bool conv_pw_layer_ok(const ConvArgs &a)
 {
     if (opt(OPT_CONV_NO_PW)) return false;
     const int Ctot = a.C1 + a.C2;
     if (a.ksize != 1 || a.stride != 1 || a.w_interleave != 4 || a.Cout % BN || a.cout_pad != a.Cout) return false;
     if (a.upsample || a.H != a.Hs || a.W != a.Ws || a.Ho != a.H || a.Wo != a.W) return false;
     if (Ctot % KC_MIN || Ctot < 2 * KC_MIN || (a.C2 && a.C1 % KC_MIN) || a.act == 2 || a.sk_w || (a.act && a.res)) return false;
-    if ((long)(a.C1 > a.C2 ? a.C1 : a.C2) * a.Ho * a.Wo >= (1L << 29) || (long)a.Cout * a.Ho * a.Wo >= (1L << 29)) return false;
-    return conv_ws_split(a) == 1;
+    return (long)(a.C1 > a.C2 ? a.C1 : a.C2) * a.Ho * a.Wo < (1L << 29) && (long)a.Cout * a.Ho * a.Wo < (1L << 29);
 }
 
 // ... and the ones it DOES take.  An item is one wave walking all input channels: a launch with fewer items than waves runs
@@ -358,40 +357,29 @@ bool conv_pw_layer_ok(const ConvArgs &a)
 // either way, so a layer WITHOUT fused statistics chooses by the fill of THIS launch (>= 1.3 rounds of 32-pixel items);
 // the statistics rows of the two kernels differ in geometry (sums over different pixel sets round differently), so a layer
 // WITH fused statistics must not look at the batch: it comes here only if one sample alone brings >= 1024 items.
-bool conv_pw_stats_layer(const ConvArgs &a)
+bool conv_pw_eligible(const ConvArgs &a, bool stats)
 {
     if (!conv_pw_layer_ok(a)) return false;
-    return opt(OPT_PW_FORCE) || (long)cdiv((long)a.Ho * a.Wo, 32) * (a.Cout / BN) >= 1024;      // (pw_force: tests drive small shapes through the kernel)
-}
-bool conv_pw_eligible(const ConvArgs &a)
-{
-    if (!conv_pw_layer_ok(a)) return false;
-    if (a.stats) return conv_pw_stats_layer(a);
-    if (opt(OPT_PW_FORCE)) return true;
-    const long items = (long)cdiv((long)a.Ho * a.Wo, 32) * (a.Cout / BN) * a.B;
-    return 10 * items >= 13L * device_cu_count() * NW;
+    if (opt(OPT_PW_FORCE)) return true;      // (pw_force: tests drive small shapes through the kernel)
+    const long items = (long)cdiv((long)a.Ho * a.Wo, 32) * (a.Cout / BN);
+    return stats ? items >= 1024 : 10 * items * a.B >= 13L * device_cu_count() * NW;
 }
 
 int conv_pw_stats_rows(const ConvArgs &a) { return cdiv((long)a.Ho * a.Wo, 32); }
 
 namespace {
 template <int NPB>
-void launch_pw(const ConvArgs &a, long G, size_t lds_bytes, long nitems, hipStream_t st)
+const void *pw_kernel(bool act, bool planar)
 {
-    if (a.act) {
-        if (a.x1_planar) hipLaunchKernelGGL((conv_pw_kernel<true, true, NPB>), dim3((unsigned)G), dim3(512), lds_bytes, st, a, (int)nitems);
-        else hipLaunchKernelGGL((conv_pw_kernel<true, false, NPB>), dim3((unsigned)G), dim3(512), lds_bytes, st, a, (int)nitems);
-    } else {
-        if (a.x1_planar) hipLaunchKernelGGL((conv_pw_kernel<false, true, NPB>), dim3((unsigned)G), dim3(512), lds_bytes, st, a, (int)nitems);
-        else hipLaunchKernelGGL((conv_pw_kernel<false, false, NPB>), dim3((unsigned)G), dim3(512), lds_bytes, st, a, (int)nitems);
-    }
+    return act ? (planar ? (const void *)conv_pw_kernel<true, true, NPB> : (const void *)conv_pw_kernel<true, false, NPB>)
+               : (planar ? (const void *)conv_pw_kernel<false, true, NPB> : (const void *)conv_pw_kernel<false, false, NPB>);
 }
 }  // namespace
 
 int conv2d_pw_launch(const ConvArgs &args, hipStream_t st)
 {
     ConvArgs a = args;
-    IPDM_REQUIRE(conv_pw_eligible(a), "conv2d_pw: not a layer of this kernel");
+    IPDM_REQUIRE(conv_pw_eligible(a, a.stats != nullptr), "conv2d_pw: not a layer of this kernel");
     IPDM_REQUIRE(!a.x1_planar || (!(a.Ho & 1) && !(a.Wo & 1)), "conv2d_pw: parity-planar source of odd size %dx%d", a.Ho, a.Wo);
     const int HW = a.Ho * a.Wo, Ctot = a.C1 + a.C2;
     IPDM_REQUIRE(!a.stats || a.stats_rows == conv_pw_stats_rows(a), "conv2d_pw: statistics rows %d != %d", a.stats_rows, conv_pw_stats_rows(a));
@@ -414,8 +402,9 @@ int conv2d_pw_launch(const ConvArgs &args, hipStream_t st)
     IPDM_REQUIRE(lds_bytes <= 64 * 1024, "conv2d_pw: %d input channels exceed the scale/shift tables", Ctot);
     const bool prof = prof_enabled();
     if (prof) prof_before(1, st);
-    if (npb == 2) launch_pw<2>(a, G, lds_bytes, nitems, st);
-    else launch_pw<1>(a, G, lds_bytes, nitems, st);
+    int ni = (int)nitems;
+    void *params[] = {&a, &ni};
+    (void)hipLaunchKernel(npb == 2 ? pw_kernel<2>(a.act, a.x1_planar) : pw_kernel<1>(a.act, a.x1_planar), dim3((unsigned)G), dim3(512), params, lds_bytes, st);
     if (prof) prof_after(1, 2.0 * a.B * HW * (double)a.Cout * Ctot, st);
     IPDM_LAUNCH_CHECK();
     return IPDM_OK;

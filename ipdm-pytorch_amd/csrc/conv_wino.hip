@@ -716,10 +716,9 @@ __global__ void __launch_bounds__(512) conv_wino_kernel(ConvArgs a, int ntiles)
 
 namespace ipdm {
 
-// Which convolutions run in the Winograd domain: wide 3x3 stride-1 layers with packed U weights, whole 64-cout tiles and
-// whole 8-channel chunks, no resampling on the way in.  Layers the direct tiling splits along K (conv_ws_split(a) > 1: too few
-// tiles for any tiling) run here too when the 128-cout kernel can split them itself (conv_wino_split: K slices INSIDE
-// conv_wino2, round 4), otherwise they stay on the K-split direct kernel.  The rule looks at the layer only, never at the batch.
+// Which convolutions can run in the Winograd domain: wide 3x3 stride-1 layers with packed U weights, whole 64-cout tiles and
+// whole 8-channel chunks, no resampling on the way in.  The rule looks at the layer only, never at the batch.  (What becomes of
+// the layers the direct tiling splits along K is the plan's business: conv_plan.hip.)
 bool conv_wino_eligible(const ConvArgs &a)
 {
     if (opt(OPT_CONV_NO_WINO) || !a.w_wino) return false;
@@ -727,9 +726,7 @@ bool conv_wino_eligible(const ConvArgs &a)
     if (a.w_interleave != 2 && a.w_interleave != 4) return false;
     const int Ctot = a.C1 + a.C2;
     if (a.Cout % BN || Ctot % KC || Ctot < 32 || (a.C2 && a.C1 % KC)) return false;
-    if ((a.x1_planar && ((a.Hs | a.Ws) & 1)) || conv_up2_eligible(a)) return false;
-    if (conv_ws_split(a) == 1) return true;
-    return !opt(OPT_WINO_V1) && conv_wino_split(a) > 1;
+    return !(a.x1_planar && ((a.Hs | a.Ws) & 1));
 }
 
 bool conv_wino_shape_ok(int Cout, int Cin, int ks, int stride, int interleave)
@@ -780,7 +777,8 @@ void conv_pack_weights_wino(const float *w, int Cout, int Cin, std::vector<float
         }
 }
 
-int conv2d_wino_launch(const ConvArgs &args, hipStream_t st)
+// code: the plan's (conv_plan.hip) -- 1 this file's 64-cout-tile kernel, 2 conv_wino2, 9 conv_wino2 over args.ksplit K slices, 12 conv_wino3
+int conv2d_wino_launch(const ConvArgs &args, int code, hipStream_t st)
 {
     ConvArgs a = args;
     a.w = args.w_wino;
@@ -790,29 +788,29 @@ int conv2d_wino_launch(const ConvArgs &args, hipStream_t st)
     a.ksplit = args.ksplit > 1 ? args.ksplit : 1;
     a.dbg = (a.dbg_buf ? (opt(OPT_CONV_DBG) & 56) : 0) | (opt(OPT_CONV_DBG) & 7);
     IPDM_REQUIRE(conv_wino_eligible(args), "conv2d_wino: layer not eligible");
+    IPDM_REQUIRE(code == 1 || code == 2 || code == 9 || code == 12, "conv2d_wino: kernel code %d is not a Winograd kernel's", code);
     IPDM_REQUIRE((long)a.C1 * a.Hs * a.Ws < (1L << 29) && (long)(a.C2 + 1) * a.Hs * a.Ws < (1L << 29) &&
                      (long)a.Cout * a.Ho * a.Wo < (1L << 29) && (long)(a.C1 + a.C2) / KC * a.co_tiles * U_CHUNK_FLOATS < (1L << 29),
                  "conv2d_wino: per-sample tensor exceeds the 2 GiB buffer-addressing range");
     const long ntiles = (long)a.tiles_x * a.tiles_y * a.co_tiles * a.B;
     IPDM_REQUIRE(ntiles < (1L << 31), "conv2d_wino: too many tiles");
     IPDM_REQUIRE(!a.stats || a.stats_rows == a.tiles_x * a.Ho, "conv2d_wino: statistics rows %d != %d", a.stats_rows, a.tiles_x * a.Ho);
+    IPDM_REQUIRE((a.ksplit > 1) == (code == 9), "conv2d_wino: %d K slices under kernel code %d", a.ksplit, code);
     const int cus = device_cu_count();
     int G = (int)(ntiles < cus ? ntiles : cus);
     G = (G + 7) / 8 * 8;
-    const bool res = a.res != nullptr;
-    const void *fn = a.x1_planar ? (res ? (const void *)conv_wino_kernel<true, true> : (const void *)conv_wino_kernel<true, false>)
-                                 : (res ? (const void *)conv_wino_kernel<false, true> : (const void *)conv_wino_kernel<false, false>);
+    const void *fn = a.x1_planar ? (a.res ? (const void *)conv_wino_kernel<true, true> : (const void *)conv_wino_kernel<true, false>)
+                                 : (a.res ? (const void *)conv_wino_kernel<false, true> : (const void *)conv_wino_kernel<false, false>);
     if (int rc = ensure_dynamic_lds(fn, LDS_BYTES)) return rc;
-    const bool v3 = conv_wino3_eligible(a);               // (opt-in, option conv_bf16x3: a rule of the layer alone)
-    const bool prof = prof_enabled(), v2 = v3 || a.ksplit > 1 || (!opt(OPT_WINO_V1) && conv_wino2_eligible(a));
-    IPDM_REQUIRE(a.ksplit == 1 || conv_wino2_eligible(a), "conv2d_wino: this layer cannot be split into %d K slices", a.ksplit);
+    const bool prof = prof_enabled(), v2 = code != 1;
     if (prof) prof_before(v2 ? 5 : 3, st);
     if (v2) {
-        if (int rc = v3 ? conv2d_wino3_launch(a, st) : conv2d_wino2_launch(a, st)) return rc;
-    } else if (a.x1_planar && res) hipLaunchKernelGGL((conv_wino_kernel<true, true>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else if (a.x1_planar) hipLaunchKernelGGL((conv_wino_kernel<true, false>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else if (res) hipLaunchKernelGGL((conv_wino_kernel<false, true>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else hipLaunchKernelGGL((conv_wino_kernel<false, false>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
+        if (int rc = code == 12 ? conv2d_wino3_launch(a, st) : conv2d_wino2_launch(a, st)) return rc;
+    } else {
+        int nt = (int)ntiles;
+        void *params[] = {&a, &nt};
+        (void)hipLaunchKernel(fn, dim3((unsigned)G), dim3(512), params, LDS_BYTES, st);      // (the caller's launch check reads the error)
+    }
     // EXECUTED flops: 16 multiply-adds per 2x2 output tile and (cin, cout) pair (the 3x3 form counts 36)
     if (prof) prof_after(v2 ? 5 : 3, 2.0 * a.B * (double)cdiv(a.Ho, 2) * cdiv(a.Wo, 2) * 16.0 * a.Cout * (a.C1 + a.C2), st);
     IPDM_LAUNCH_CHECK();

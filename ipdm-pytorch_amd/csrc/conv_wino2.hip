@@ -751,7 +751,7 @@ bool conv_wino2_eligible(const ConvArgs &a)
     return ntiles >= opt(OPT_WINO2_MIN_TILES);      // (192; a per-call option so that tests can drive small shapes through this kernel)
 }
 
-// K slices for the layers the direct tiling splits (conv_ws_split(a) > 1: <= 16 tiles of 8x32x128 per sample, a rule of the
+// K slices for the layers the direct tiling splits (<= 16 tiles of 8x32x128 per sample, a rule of the
 // layer alone -- a split changes the summation order, so it must not depend on the batch): at most FOUR slices, each of at
 // least two 16-channel chunks (the pipeline's minimum).  Measured on 256->256 @63x29 (profiles/r04_wino_ksplit.txt): B = 8
 // 0.119 / 0.138 / 0.184 ms with 2 / 4 / 8 slices (every slice pays an output transform; the K-split direct kernel: 0.197), a
@@ -773,6 +773,7 @@ int conv2d_wino2_launch(const ConvArgs &prepared, hipStream_t st)
     ConvArgs a = prepared;
     a.co_tiles = a.Cout / BN;
     if (a.ksplit < 1) a.ksplit = 1;
+    IPDM_REQUIRE(conv_wino2_eligible(a), "conv2d_wino2: not a layer of this kernel, or one it cannot split into %d K slices", a.ksplit);
     const long ntiles = (long)a.tiles_x * a.tiles_y * a.co_tiles * a.B * a.ksplit;
     IPDM_REQUIRE(ntiles < (1L << 31), "conv2d_wino2: too many tiles");
     IPDM_REQUIRE(a.ksplit == 1 || (!a.bias && !a.res && !a.stats), "conv2d_wino2: a K-split launch writes bare partial sums");
@@ -784,10 +785,9 @@ int conv2d_wino2_launch(const ConvArgs &prepared, hipStream_t st)
     const void *fn = a.x1_planar ? (res ? (const void *)conv_wino2_kernel<true, true> : (const void *)conv_wino2_kernel<true, false>)
                                  : (res ? (const void *)conv_wino2_kernel<false, true> : (const void *)conv_wino2_kernel<false, false>);
     if (int rc = ensure_dynamic_lds(fn, LDS_BYTES)) return rc;
-    if (a.x1_planar && res) hipLaunchKernelGGL((conv_wino2_kernel<true, true>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else if (a.x1_planar) hipLaunchKernelGGL((conv_wino2_kernel<true, false>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else if (res) hipLaunchKernelGGL((conv_wino2_kernel<false, true>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else hipLaunchKernelGGL((conv_wino2_kernel<false, false>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
+    int nt = (int)ntiles;
+    void *params[] = {&a, &nt};
+    (void)hipLaunchKernel(fn, dim3((unsigned)G), dim3(512), params, LDS_BYTES, st);      // (the caller's launch check reads the error)
     return IPDM_OK;
 }
 

@@ -904,6 +904,7 @@ int conv2d_wino3_launch(const ConvArgs &prepared, hipStream_t st)
 {
     ConvArgs a = prepared;
     a.co_tiles = a.Cout / BN;
+    IPDM_REQUIRE(conv_wino3_eligible(a), "conv2d_wino3: not a layer of this kernel");
     a.ksplit = 1;
     const long ntiles = (long)a.tiles_x * a.tiles_y * a.co_tiles * a.B;
     IPDM_REQUIRE(ntiles < (1L << 31), "conv2d_wino3: too many tiles");
@@ -911,14 +912,12 @@ int conv2d_wino3_launch(const ConvArgs &prepared, hipStream_t st)
     const int cus = device_cu_count();
     long G = ntiles < cus ? ntiles : cus;
     G = (G + 7) / 8 * 8;
-    const bool res = a.res != nullptr;
-    const void *fn = a.x1_planar ? (res ? (const void *)conv_wino3_kernel<true, true> : (const void *)conv_wino3_kernel<true, false>)
-                                 : (res ? (const void *)conv_wino3_kernel<false, true> : (const void *)conv_wino3_kernel<false, false>);
+    const void *fn = a.x1_planar ? (a.res ? (const void *)conv_wino3_kernel<true, true> : (const void *)conv_wino3_kernel<true, false>)
+                                 : (a.res ? (const void *)conv_wino3_kernel<false, true> : (const void *)conv_wino3_kernel<false, false>);
     if (int rc = ensure_dynamic_lds(fn, LDS_BYTES)) return rc;
-    if (a.x1_planar && res) hipLaunchKernelGGL((conv_wino3_kernel<true, true>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else if (a.x1_planar) hipLaunchKernelGGL((conv_wino3_kernel<true, false>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else if (res) hipLaunchKernelGGL((conv_wino3_kernel<false, true>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
-    else hipLaunchKernelGGL((conv_wino3_kernel<false, false>), dim3((unsigned)G), dim3(512), LDS_BYTES, st, a, (int)ntiles);
+    int nt = (int)ntiles;
+    void *params[] = {&a, &nt};
+    (void)hipLaunchKernel(fn, dim3((unsigned)G), dim3(512), params, LDS_BYTES, st);      // (the caller's launch check reads the error)
     return IPDM_OK;
 }
 

@@ -639,8 +639,6 @@ __global__ void __launch_bounds__(512) conv_ws_kernel(ConvArgs a, int ntiles)
     }
 }
 
-int num_cus() { return device_cu_count(); }
-
 template <int KS, int STRIDE, int MB, int NB, int KC, int IL, int PBW, bool VEC4, bool PLANAR = false>
 int launch_ws_v(const ConvArgs &args, hipStream_t st, int prof_cls)
 {
@@ -671,7 +669,7 @@ int launch_ws_v(const ConvArgs &args, hipStream_t st, int prof_cls)
                      "conv2d: bad K split %d", a.ksplit);
     const long ntiles = (long)a.tiles_x * a.tiles_y * a.co_tiles * a.B * a.ksplit;
     IPDM_REQUIRE(ntiles < (1L << 31), "conv2d: too many tiles");
-    const int cus = num_cus();
+    const int cus = device_cu_count();
     int G = (int)(ntiles < cus ? ntiles : cus);
     G = (G + 7) / 8 * 8;
     IPDM_REQUIRE(!a.stats || a.stats_rows == a.tiles_x * a.Ho * (a.up2 ? 4 : 1), "conv2d: statistics rows %d != %d", a.stats_rows,
@@ -714,7 +712,7 @@ namespace ipdm {
 int conv_ws_split(const ConvArgs &a)
 {
     const bool off = opt(OPT_CONV_NO_SPLITK) != 0;
-    if (off || !a.w_interleave || a.w_interleave > 4 || conv_up2_eligible(a)) return 1;
+    if (off || !a.w_interleave || a.w_interleave > 4) return 1;
     const long per_sample = (long)cdiv(a.Wo, 32) * cdiv(a.Ho, 8) * cdiv(a.Cout, 128);
     if (per_sample > 16) return 1;
     const int nch = cdiv(a.C1 + a.C2, a.ksize == 1 ? 32 : 8);
@@ -741,12 +739,10 @@ bool conv_up2_eligible(const ConvArgs &a)
            a.act == 0 && !a.res && a.H == 2 * a.Hs && a.W == 2 * a.Ws && a.Ho == a.H && a.Wo == a.W;
 }
 
-int conv_ws_stats_rows(const ConvArgs &a)
-{
-    if (conv_up2_eligible(a)) return 4 * a.Hs * cdiv(a.Ws, 32);
-    if (a.split_ws && conv_split(a) > 1) return cdiv((long)a.Ho * a.Wo, SPLIT_PIX);      // the combine pass writes them (either kernel)
-    return a.Ho * cdiv(a.Wo, 32);      // one row per pixel row and 32-pixel tile column: independent of the tile variant
-}
+constexpr int SPLIT_PIX = 2048;                    // pixels per workgroup (= per statistics row) of the combine pass
+int conv_ws_stats_rows(const ConvArgs &a) { return a.Ho * cdiv(a.Wo, 32); }      // one row per pixel row and 32-pixel tile column: independent of the tile variant
+int conv_up2_stats_rows(const ConvArgs &a) { return 4 * a.Hs * cdiv(a.Ws, 32); }      // ... of each parity's image on the source grid
+int conv_splitk_stats_rows(const ConvArgs &a) { return cdiv((long)a.Ho * a.Wo, SPLIT_PIX); }      // the combine pass writes them (either kernel)
 
 namespace {
 // out = sum over the K slices (ascending: a fixed order) + bias (+ residual); the GroupNorm statistics of the result as
@@ -783,35 +779,34 @@ __global__ void __launch_bounds__(256) splitk_combine_kernel(const float *__rest
 }
 }  // namespace
 
-static int conv2d_ws_dispatch(const ConvArgs &a, hipStream_t st);
-
-// 3x3 stride-1 convolutions with more than 32 output channels (weights packed cout-interleaved, see
-// conv_weight_interleave / conv_pack_weights).
-int conv2d_ws_launch(const ConvArgs &a, hipStream_t st)
+// the wide Upsample layers as four 2x2-tap parity convolutions on the source grid (ConvArgs::w_up2), parity-planar output
+int conv2d_up2_launch(const ConvArgs &a, hipStream_t st)
 {
-    if (conv_up2_eligible(a)) {
-        if (conv_wup2_eligible(a)) return conv2d_wup2_launch(a, st, 7);      // the F(2x2,2x2) form of the same four convolutions
-        ConvArgs k = a;
-        k.up2 = 1; k.w = a.w_up2; k.ksize = 2; k.upsample = 0; k.H = k.Ho = a.Hs; k.W = k.Wo = a.Ws; k.split_ws = nullptr; k.ksplit = 1;
-        // (16-channel chunks -- 16k instead of 8k cycles of MFMA per hand-over -- measured 0.7 % slower per forward)
-        if (a.w_interleave == 4) return launch_ws<2, 1, 4, 2, 8>(k, st, 1);
-        return launch_ws<2, 1, 2, 4, 8>(k, st, 1);
-    }
-    const bool wino = conv_wino_eligible(a);                                 // the Winograd-domain form (conv_wino.hip / conv_wino2.hip)
-    const int S = a.split_ws ? conv_split(a) : 1;
-    if (S == 1) return wino ? conv2d_wino_launch(a, st) : conv2d_ws_dispatch(a, st);
+    IPDM_REQUIRE(conv_up2_eligible(a), "conv2d_up2: not an eligible Upsample layer");
     ConvArgs k = a;
-    k.out = a.split_ws; k.bias = nullptr; k.res = nullptr; k.stats = nullptr; k.stats_rows = 0; k.ksplit = S;
-    if (int rc = wino ? conv2d_wino_launch(k, st) : conv2d_ws_dispatch(k, st)) return rc;
-    const int HW = a.Ho * a.Wo, rows = cdiv(HW, SPLIT_PIX);
+    k.up2 = 1; k.w = a.w_up2; k.ksize = 2; k.upsample = 0; k.H = k.Ho = a.Hs; k.W = k.Wo = a.Ws; k.split_ws = nullptr; k.ksplit = 1;
+    // (16-channel chunks -- 16k instead of 8k cycles of MFMA per hand-over -- measured 0.7 % slower per forward)
+    if (a.w_interleave == 4) return launch_ws<2, 1, 4, 2, 8>(k, st, 1);
+    return launch_ws<2, 1, 2, 4, 8>(k, st, 1);
+}
+
+// plan codes 4 and 9: p.ksplit bare partial sums into a.split_ws (this file's kernel or conv_wino2), then the combine pass
+int conv2d_splitk_launch(const ConvArgs &a, const ConvPlan &p, hipStream_t st)
+{
+    IPDM_REQUIRE(a.split_ws && p.ksplit > 1 && (p.code == 4 || p.code == 9), "conv2d: bad K-split plan (code %d, %d slices)", p.code, p.ksplit);
+    ConvArgs k = a;
+    k.out = a.split_ws; k.bias = nullptr; k.res = nullptr; k.stats = nullptr; k.stats_rows = 0; k.ksplit = p.ksplit;
+    if (int rc = p.code == 9 ? conv2d_wino_launch(k, 9, st) : conv2d_ws_launch(k, st)) return rc;
+    const int HW = a.Ho * a.Wo, rows = conv_splitk_stats_rows(a);
     IPDM_REQUIRE(!a.stats || a.stats_rows == rows, "conv2d: statistics rows %d != %d (K split)", a.stats_rows, rows);
-    hipLaunchKernelGGL(splitk_combine_kernel, dim3(rows, a.Cout, a.B), dim3(256), 0, st, a.split_ws, S, a.bias, a.res, a.out,
+    hipLaunchKernelGGL(splitk_combine_kernel, dim3(rows, a.Cout, a.B), dim3(256), 0, st, a.split_ws, p.ksplit, a.bias, a.res, a.out,
                        a.stats, rows, a.B, a.Cout, HW);
     IPDM_LAUNCH_CHECK();
     return IPDM_OK;
 }
 
-static int conv2d_ws_dispatch(const ConvArgs &a, hipStream_t st)
+// convolutions with more than 32 output channels (weights packed cout-interleaved: conv_weight_interleave); a.ksplit: conv2d_splitk_launch
+int conv2d_ws_launch(const ConvArgs &a, hipStream_t st)
 {
     if (a.ksize == 3 && a.stride == 1 && a.w_interleave == 4) {
         // layers whose 8x32x128 tiling gives fewer tiles than CUs (32x32 and 63x29 at 256 channels) use 4x32x64 tiles

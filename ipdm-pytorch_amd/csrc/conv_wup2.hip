@@ -427,7 +427,7 @@ bool conv_wup2_shape_ok(int Cout, int Cin)
 // a rule of the layer alone (another summation order than the 2x2-tap parity form: the choice must not look at the batch)
 bool conv_wup2_eligible(const ConvArgs &a)
 {
-    return conv_up2_eligible(a) && a.w_wup2 && !opt(OPT_CONV_NO_WUP2) && conv_wup2_shape_ok(a.Cout, a.C1);
+    return a.w_wup2 && !opt(OPT_CONV_NO_WUP2) && conv_wup2_shape_ok(a.Cout, a.C1);      // (of the layers that run in parity form at all: conv_plan.hip)
 }
 
 // [Cin/8][Cout/128][a][b][cout quarter][position (p, q)][k parity][cout 32][k step]: U = G g_ab G^T of the parity's 2x2 filter
@@ -468,9 +468,10 @@ void conv_pack_weights_wup2(const float *w, int Cout, int Cin, std::vector<float
         }
 }
 
-// `orig`: the Upsample layer's arguments as the executor passes them (H x W = the up-sampled size), conv_wup2_eligible(orig)
+// `orig`: the Upsample layer's arguments as the executor passes them (H x W = the up-sampled size), a parity-form layer with conv_wup2_eligible(orig)
 int conv2d_wup2_launch(const ConvArgs &orig, hipStream_t st, int prof_cls)
 {
+    IPDM_REQUIRE(conv_up2_eligible(orig) && conv_wup2_eligible(orig), "conv2d_wup2: not an eligible Upsample layer");
     ConvArgs a = orig;
     a.w = orig.w_wup2; a.up2 = 1; a.upsample = 0; a.H = a.Ho = orig.Hs; a.W = a.Wo = orig.Ws; a.split_ws = nullptr; a.ksplit = 1;
     a.tiles_x = cdiv(a.W, TW); a.tiles_y = cdiv(a.H, TH); a.co_tiles = a.Cout / BN;

@@ -425,10 +425,11 @@ std::vector<TraceRec> g_trace_rec;
 char *g_trace_pool = nullptr;
 size_t g_trace_used = 0;
 const size_t g_trace_pool_bytes = (size_t)48 << 30;
+int trace_code(const ConvArgs &a) { return conv_plan(a, a.stats != nullptr, a.split_ws != nullptr).code; }      // the plan conv2d_launch just executed
 void trace_conv(const ConvArgs &a, size_t n, hipStream_t st)
 {
     char desc[256];
-    snprintf(desc, sizeof(desc), "code %2d  %3d+%-3d -> %3d @%4dx%-4d s%d act %d res %d planar %d stats %d", conv_kernel_code(a), a.C1, a.C2, a.Cout, a.Ho, a.Wo,
+    snprintf(desc, sizeof(desc), "code %2d  %3d+%-3d -> %3d @%4dx%-4d s%d act %d res %d planar %d stats %d", trace_code(a), a.C1, a.C2, a.Cout, a.Ho, a.Wo,
              a.stride, a.act, a.res ? 1 : 0, a.x1_planar, a.stats ? a.stats_rows : 0);
 #if IPDM_UNET_TRACE == 1
     std::vector<unsigned> h(n);
@@ -445,7 +446,7 @@ void trace_conv(const ConvArgs &a, size_t n, hipStream_t st)
         (void)hipMemcpyAsync(g_trace_pool + g_trace_used, a.out, n * 4, hipMemcpyDeviceToDevice, st);
         TraceRec rec{g_trace_used, n, a.B, a.Cout, a.Ho, a.Wo};
         g_trace_used += (n * 4 + 255) / 256 * 256;
-        rec.code = conv_kernel_code(a);
+        rec.code = trace_code(a);
         const size_t nx = (size_t)a.B * a.C1 * a.Hs * a.Ws * 4, ng = (size_t)a.B * (a.C1 + a.C2) * 4;
         if (rec.code == 12 && a.C2 == 0 && a.act && g_trace_used + nx + 2 * ng + 1024 <= g_trace_pool_bytes) {      // the inputs too: ipdm_trace_dump() writes them out for the first wrong one
             rec.C1 = a.C1; rec.w = a.w_wino;
@@ -746,20 +747,21 @@ struct Fwd {
         Tensor *o;
         if (ext_out) { o = new Tensor(); o->C = cp.cout; o->H = Ho; o->W = Wo; o->external = true; o->ext = ext_out; o->refs = 1; net->live.push_back(o); }
         else o = make(cp.cout, Ho, Wo);
-        ConvArgs a;
-        // (shape fields first: the statistics geometry depends on the kernel the dispatcher picks, in dry runs too)
-        a.C1 = x1->C; a.C2 = x2 ? x2->C : 0; a.B = net->B; a.Cout = cp.cout; a.ksize = cp.ks; a.stride = stride; a.Ho = Ho; a.Wo = Wo;
-        a.w_interleave = cp.interleave; a.cout_pad = cp.cout_pad;
-        a.Hs = x1->H; a.Ws = x1->W; a.H = H; a.W = W; a.upsample = (H != x1->H || W != x1->W); a.act = act; a.res = res ? (const float *)(uintptr_t)256 : nullptr;
-        a.w_up2 = net->transposed ? cp.w_up2_t : cp.w_up2;
-        a.w_wup2 = net->transposed ? cp.w_wup2_t : cp.w_wup2;
-        a.w_wino = net->transposed ? cp.w_wino_t : cp.w_wino;
         // parity-planar sources (outputs of up2 convolutions): x1 of the kernels that can read them, converted otherwise
         Tensor *lin1 = nullptr, *lin2 = linear_copy(x2), *linr = linear_copy(res);
-        if (x1->planar && !conv_planar_ok(a)) lin1 = linear_copy(x1);
-        if (lin1) x1 = lin1;
         if (lin2) x2 = lin2;
         if (linr) res = linr;
+        ConvArgs a;
+        a.C1 = x1->C; a.C2 = x2 ? x2->C : 0; a.B = net->B; a.Hs = x1->H; a.Ws = x1->W; a.H = H; a.W = W;
+        a.upsample = (H != x1->H || W != x1->W); a.scale_y = (float)x1->H / (float)H; a.scale_x = (float)x1->W / (float)W;
+        a.w = net->transposed ? cp.w_t : cp.w; a.cout_pad = cp.cout_pad; a.w_interleave = cp.interleave; a.bias = bias; a.Cout = cp.cout; a.ksize = cp.ks; a.stride = stride;
+        a.Ho = Ho; a.Wo = Wo; a.act = act; a.gn_scale = net->gn_scale; a.gn_shift = net->gn_shift;
+        a.w_up2 = (ext_out && cp.interleave) ? nullptr : net->transposed ? cp.w_up2_t : cp.w_up2;      // (an external output is NCHW: no parity-planar form)
+        a.w_wup2 = net->transposed ? cp.w_wup2_t : cp.w_wup2;
+        a.w_wino = net->transposed ? cp.w_wino_t : cp.w_wino;
+        a.res = res ? (const float *)(uintptr_t)256 : nullptr;      // (the plan only asks whether it is null; addresses: below, not in dry runs)
+        a.x1 = a.x2 = nullptr; a.out = nullptr; a.tiles_x = a.tiles_y = a.co_tiles = 0;
+        if (x1->planar && !conv_planar_ok(a)) x1 = lin1 = linear_copy(x1);
         a.x1_planar = x1->planar ? 1 : 0;
         Tensor *lins = sk ? linear_copy(sk_x2) : nullptr;
         if (lins) sk_x2 = lins;
@@ -769,41 +771,28 @@ struct Fwd {
             a.sk_C1 = sk_x1->C; a.sk_C2 = sk_x2 ? sk_x2->C : 0; a.sk_cout_pad = sk->cout_pad; a.sk_planar = sk_x1->planar ? 1 : 0;
             a.sk_w = sk->w;
         }
-        if (conv_up2_eligible(a) && !ext_out) o->planar = true;                 // wide levels: parity-planar output
-        else if (!conv_direct_up2_eligible(a)) a.w_up2 = nullptr;               // (narrow levels: the direct kernel's parity form writes NCHW)
-        // layers with too few tiles to fill the chip are split along K into a scratch buffer (conv_ws.hip)
-        const size_t split_bytes = conv_split_ws_bytes(a);
+        // the one decision: kernel, K split (layers with too few tiles to fill the chip, summed through a scratch buffer), statistics rows
+        const ConvPlan plan = conv_plan(a, want_stats && !ext_out && !net->no_fused_stats, true);
+        o->planar = plan.out_planar;
         size_t split_off = (size_t)-1;
-        if (split_bytes) {
-            split_off = net->arena.alloc(split_bytes);
+        if (plan.split_ws_bytes) {
+            split_off = net->arena.alloc(plan.split_ws_bytes);
             if (split_off == (size_t)-1) { set_error("unet_forward: workspace exhausted"); rc = IPDM_ERR_WORKSPACE; split_off = 0; }
-            a.split_ws = (float *)(net->ws + split_off);
-            if (!a.split_ws) a.split_ws = reinterpret_cast<float *>((uintptr_t)256);
         }
-        struct SplitGuard { Arena &ar; size_t off, bytes; ~SplitGuard() { if (off != (size_t)-1) ar.release(off, bytes); } } split_guard{net->arena, split_off, split_bytes};
-        if (want_stats && !ext_out && !net->no_fused_stats) {
-            const int rows = conv_stats_rows(a);
-            if (rows > 0) {
-                o->st_bytes = (size_t)net->B * rows * cp.cout * 2 * sizeof(float);
-                o->st_off = net->arena.alloc(o->st_bytes);
-                if (o->st_off == (size_t)-1) { set_error("unet_forward: workspace exhausted"); rc = IPDM_ERR_WORKSPACE; o->st_off = 0; }
-                o->nst = 1;
-                o->st[0].off = o->st_off; o->st[0].rows = rows; o->st[0].C = cp.cout;
-            }
+        struct SplitGuard { Arena &ar; size_t off, bytes; ~SplitGuard() { if (off != (size_t)-1) ar.release(off, bytes); } } split_guard{net->arena, split_off, plan.split_ws_bytes};
+        if (plan.stats_rows > 0) {
+            o->st_bytes = (size_t)net->B * plan.stats_rows * cp.cout * 2 * sizeof(float);
+            o->st_off = net->arena.alloc(o->st_bytes);
+            if (o->st_off == (size_t)-1) { set_error("unet_forward: workspace exhausted"); rc = IPDM_ERR_WORKSPACE; o->st_off = 0; }
+            o->nst = 1;
+            o->st[0].off = o->st_off; o->st[0].rows = plan.stats_rows; o->st[0].C = cp.cout;
         }
         if (rc || net->dry) return o;
-        if (o->nst) { a.stats = (float *)(net->ws + o->st_off); a.stats_rows = o->st[0].rows; }
-        a.x1 = ptr(x1); a.x2 = x2 ? ptr(x2) : nullptr;
-        a.C1 = x1->C; a.C2 = x2 ? x2->C : 0; a.B = net->B;
-        a.Hs = x1->H; a.Ws = x1->W; a.H = H; a.W = W;
-        a.upsample = (H != x1->H || W != x1->W);
-        a.scale_y = (float)x1->H / (float)H; a.scale_x = (float)x1->W / (float)W;
-        a.w = net->transposed ? cp.w_t : cp.w; a.cout_pad = cp.cout_pad; a.w_interleave = cp.interleave; a.bias = bias; a.Cout = cp.cout; a.ksize = cp.ks; a.stride = stride;
-        a.Ho = Ho; a.Wo = Wo; a.act = act; a.gn_scale = net->gn_scale; a.gn_shift = net->gn_shift;
-        a.res = res ? ptr(res) : nullptr;
+        // the addresses (a dry run has no workspace): they change nothing the plan read, so conv2d_launch takes the same plan
+        a.x1 = ptr(x1); a.x2 = x2 ? ptr(x2) : nullptr; a.res = res ? ptr(res) : nullptr; a.out = ext_out ? ext_out : wptr(o);
         if (sk) { a.sk_x1 = ptr(sk_x1); a.sk_x2 = sk_x2 ? ptr(sk_x2) : nullptr; }
-        a.out = ext_out ? ext_out : wptr(o);
-        a.tiles_x = a.tiles_y = a.co_tiles = 0;
+        if (plan.split_ws_bytes) a.split_ws = (float *)(net->ws + split_off);
+        if (o->nst) { a.stats = (float *)(net->ws + o->st_off); a.stats_rows = plan.stats_rows; }
         rc = conv2d_launch(a, net->st);
 #if IPDM_UNET_TRACE      // diagnostic build (tools/build_variants.sh unet.hip trace:-DIPDM_UNET_TRACE=1): a checksum of every convolution's output
         if (!rc) trace_conv(a, (size_t)net->B * cp.cout * Ho * Wo, net->st);
@@ -1193,7 +1182,7 @@ extern "C" int ipdm_op_conv2d(const float *d_x1, int32_t C1, const float *d_x2, 
         a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
         a.act = act; a.gn_scale = d_sc; a.gn_shift = d_sh; a.res = d_res; a.out = d_out;
         a.tiles_x = a.tiles_y = a.co_tiles = 0;
-        if (conv_split_ws_bytes(a)) IPDM_HIP_CHECK(hipMalloc((void **)&d_split, conv_split_ws_bytes(a)));
+        if (const size_t bytes = conv_plan(a, false, true).split_ws_bytes) IPDM_HIP_CHECK(hipMalloc((void **)&d_split, bytes));
         a.split_ws = d_split;
         rc = conv2d_launch(a, st);
     }
@@ -1255,10 +1244,11 @@ extern "C" int ipdm_op_up_conv_chain(const float *d_x, int32_t C, int32_t B, int
     a.scale_y = (float)Hs / (float)H; a.scale_x = (float)Ws / (float)W; a.w = d_wA; a.w_up2 = d_wU; a.w_wup2 = d_wW; a.cout_pad = coutpA; a.w_interleave = ilA;
     a.bias = d_bA; a.Cout = CA; a.ksize = 3; a.stride = 1; a.Ho = H; a.Wo = W; a.act = 0; a.gn_scale = a.gn_shift = nullptr; a.res = nullptr;
     a.out = d_pl; a.tiles_x = a.tiles_y = a.co_tiles = 0;
-    const bool up2 = conv_up2_eligible(a);
-    // 2: the direct kernel's parity form (NCHW output); 3: the F(2x2,2x2) form of the wide layers (conv_wup2.hip)
-    if (used_up2) *used_up2 = up2 ? (conv_wup2_eligible(a) ? 3 : 1) : (conv_direct_up2_eligible(a) ? 2 : 0);
-    const int rows = C2 == 0 ? conv_stats_rows(a) : 0;      // fused statistics when the GroupNorm covers mid alone
+    const ConvPlan planA = conv_plan(a, C2 == 0, false);      // fused statistics when the GroupNorm covers mid alone
+    const bool up2 = planA.out_planar;
+    const int rows = planA.stats_rows;
+    // 1: four parity convolutions (conv_ws.hip); 2: the direct kernel's parity form (NCHW output); 3: the F(2x2,2x2) form of the wide layers (conv_wup2.hip)
+    if (used_up2) *used_up2 = !planA.up2 ? 0 : !up2 ? 2 : planA.code == 11 ? 3 : 1;
     if (!rc && rows > 0) {
         rc = dev(nullptr, (size_t)B * rows * CA * 2 * 4, (void **)&d_stats);
         if (!rc) IPDM_HIP_CHECK(hipMemsetAsync(d_stats, 0xff, (size_t)B * rows * CA * 2 * 4, st));     // NaN: unwritten rows show
@@ -1293,7 +1283,8 @@ extern "C" int ipdm_op_up_conv_chain(const float *d_x, int32_t C, int32_t B, int
             if (!rc) rc = planar_to_linear_launch(d_pl, d_lin, (long)B * CA, H, W, st);
             b.x1 = d_lin;
         } else b.x1_planar = up2 ? 1 : 0;
-        if (!rc && conv_split_ws_bytes(b)) { float *d_sp; rc = dev(nullptr, conv_split_ws_bytes(b), (void **)&d_sp); if (!rc) b.split_ws = d_sp; }
+        const size_t split_bytes = conv_plan(b, false, true).split_ws_bytes;
+        if (!rc && split_bytes) { float *d_sp; rc = dev(nullptr, split_bytes, (void **)&d_sp); if (!rc) b.split_ws = d_sp; }
         if (!rc) rc = conv2d_launch(b, st);
     }
     (void)hipStreamSynchronize(st);
@@ -1348,8 +1339,9 @@ extern "C" int ipdm_op_conv_gn_conv(const float *d_x, int32_t C, int32_t B, int3
     if (!rc) rc = upload_wino(wB_host, CB, CA, 3, 1, ilB, &d_winoB);
     if (d_winoB) tofree.push_back(d_winoB);
     a.w_wino = d_winoA;
-    if (!rc && conv_split_ws_bytes(a)) { float *d_sp; rc = dev(nullptr, conv_split_ws_bytes(a), (void **)&d_sp); if (!rc) a.split_ws = d_sp; }
-    const int rows = conv_stats_rows(a);
+    const ConvPlan planA = conv_plan(a, true, true);
+    if (!rc && planA.split_ws_bytes) { float *d_sp; rc = dev(nullptr, planA.split_ws_bytes, (void **)&d_sp); if (!rc) a.split_ws = d_sp; }
+    const int rows = planA.stats_rows;
     if (fused_rows) *fused_rows = rows;
     if (!rc && rows > 0) {
         rc = dev(nullptr, (size_t)B * rows * CA * 2 * 4, (void **)&d_stats);
@@ -1439,10 +1431,11 @@ extern "C" int ipdm_bench_conv2d(int32_t B, int32_t C1, int32_t C2, int32_t H, i
     a.tiles_x = a.tiles_y = a.co_tiles = 0;
     if (x1_planar) { IPDM_REQUIRE(conv_planar_ok(a), "bench_conv2d: this shape has no parity-planar reader"); a.x1_planar = 1; }
     float *d_split = nullptr, *d_stats = nullptr;
-    if (conv_split_ws_bytes(a)) IPDM_HIP_CHECK(hipMalloc((void **)&d_split, conv_split_ws_bytes(a)));
+    const ConvPlan plan = conv_plan(a, up, true);      // (every Upsample of the networks feeds a GroupNorm: timed with its fused statistics)
+    if (plan.split_ws_bytes) IPDM_HIP_CHECK(hipMalloc((void **)&d_split, plan.split_ws_bytes));
     a.split_ws = d_split;
-    if (up && conv_stats_rows(a) > 0) {       // (every Upsample of the networks feeds a GroupNorm: timed with its fused statistics)
-        a.stats_rows = conv_stats_rows(a);
+    if (plan.stats_rows > 0) {
+        a.stats_rows = plan.stats_rows;
         IPDM_HIP_CHECK(hipMalloc((void **)&d_stats, (size_t)B * a.stats_rows * Cout * 2 * 4));
         a.stats = d_stats;
     }
@@ -1483,17 +1476,6 @@ extern "C" int32_t ipdm_conv_layout_code(int32_t Cout, int32_t ksize, int32_t st
     return conv_weight_interleave(Cout, ksize, stride);
 }
 
-static int32_t conv_kernel_code_impl(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W, bool with_stats);
-extern "C" int32_t ipdm_conv_kernel_code(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W)
-{
-    return conv_kernel_code_impl(B, Cout, Cin, ksize, stride, H, W, false);
-}
-// ... for a layer whose output feeds a GroupNorm (the executor asks it for fused statistics): the kernel rule of such a layer
-// looks at the layer alone, never at the batch (conv_pw_stats_layer), so the answer can differ from the plain query's
-extern "C" int32_t ipdm_conv_kernel_code_stats(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W)
-{
-    return conv_kernel_code_impl(B, Cout, Cin, ksize, stride, H, W, true);
-}
 static int32_t conv_kernel_code_impl(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W, bool with_stats)
 {
     if (B <= 0 || Cout <= 0 || Cin <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) || stride < 1 || stride > 2) return -1;
@@ -1509,9 +1491,18 @@ static int32_t conv_kernel_code_impl(int32_t B, int32_t Cout, int32_t Cin, int32
     a.act = 0; a.gn_scale = a.gn_shift = nullptr; a.res = nullptr; a.out = &dummy;
     a.tiles_x = a.tiles_y = a.co_tiles = 0;
     a.w_wino = conv_wino_shape_ok(Cout, Cin, ksize, stride, a.w_interleave) ? &dummy : nullptr;
-    a.split_ws = &dummy;
-    if (with_stats) { a.stats = &dummy; a.stats_rows = conv_stats_rows(a); }
-    return conv_kernel_code(a);
+    return conv_plan(a, with_stats, true).code;
+}
+
+extern "C" int32_t ipdm_conv_kernel_code(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W)
+{
+    return conv_kernel_code_impl(B, Cout, Cin, ksize, stride, H, W, false);
+}
+// ... for a layer whose output feeds a GroupNorm (the executor asks it for fused statistics): the kernel rule of such a layer
+// looks at the layer alone, never at the batch (conv_pw.hip), so the answer can differ from the plain query's
+extern "C" int32_t ipdm_conv_kernel_code_stats(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W)
+{
+    return conv_kernel_code_impl(B, Cout, Cin, ksize, stride, H, W, true);
 }
 
 extern "C" int ipdm_bench_attention(int32_t B, int32_t heads, int32_t d, int32_t T, int32_t iters, float *avg_ms)

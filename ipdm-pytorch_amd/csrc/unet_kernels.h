@@ -40,28 +40,28 @@ struct ConvArgs {
     // Fused GroupNorm statistics of the OUTPUT (for the GroupNorm that follows this convolution): when non-null, every
     // (tile, consumer wave) / workgroup writes one row of per-channel partial sums {sum, sum of squares} of the final
     // output values it produced: stats[((n * stats_rows + row) * Cout + c) * 2 + {0,1}] (float32 partials over <= a few
-    // hundred pixels; combined in float64 by gn_tiles_launch).  stats_rows = conv_stats_rows(args).
+    // hundred pixels; combined in float64 by gn_tiles_launch).  stats_rows = conv_plan(args, true, ...).stats_rows.
     float *stats = nullptr;
     int stats_rows = 0;
-    // K split of layers with too few output tiles to fill the chip (batch 1, low resolutions): conv_split(args) slices of
+    // K split of layers with too few output tiles to fill the chip (batch 1, low resolutions): ConvPlan::ksplit slices of
     // the input-channel range are summed by separate workgroups into split_ws [ksplit][B,Cout,Ho,Wo] (caller-provided,
-    // conv_split_ws_bytes(args) bytes) and a combine pass adds them in a fixed order (+ bias, residual, statistics).
+    // ConvPlan::split_ws_bytes bytes) and a combine pass adds them in a fixed order (+ bias, residual, statistics).
     // ksplit is set by the launcher; callers only provide split_ws (null: never split).
     float *split_ws = nullptr;
     int ksplit = 1;
     // The convolution of a 2x nearest up-sampled image (Upsample: F.interpolate + 3x3 conv) as four 2x2-tap convolutions on
     // the source grid, one per output parity, over weights whose coinciding taps were added up at pack time
     // (conv_pack_weights_up2): 4 instead of 9 multiply-adds per output.  The caller passes the ordinary arguments plus
-    // w_up2; when conv_up2_eligible(args) the launcher takes this path and writes `out` PARITY-PLANAR:
+    // w_up2; when the plan says so (ConvPlan::out_planar) the launcher takes this path and writes `out` PARITY-PLANAR:
     // [n][cout][row & 1][col & 1][Ho/2][Wo/2] (same channel stride as NCHW).  Readers set x1_planar (conv_planar_ok).
     const float *w_up2 = nullptr;
     // ... and, for the layers conv_wup2_shape_ok accepts, the parity filters in the Winograd F(2x2,2x2) domain
     // (conv_pack_weights_wup2): 9 instead of 16 multiply-adds per 2x2 outputs of a parity, same parity-planar output and
-    // statistics rows (conv_wup2.hip; conv_wup2_eligible).
+    // statistics rows (conv_wup2.hip).
     const float *w_wup2 = nullptr;
-    // The same layer's weights in the Winograd F(2x2,3x3) domain (conv_pack_weights_wino: U = G g G^T); when
-    // conv_wino_eligible(args) the launcher evaluates the convolution there (conv_wino.hip): 16 instead of 36
-    // multiply-adds per 2x2 outputs, same NCHW output and statistics rows as the direct kernel.
+    // The same layer's weights in the Winograd F(2x2,3x3) domain (conv_pack_weights_wino: U = G g G^T); the layers the plan
+    // sends there are evaluated in that domain (conv_wino.hip): 16 instead of 36 multiply-adds per 2x2 outputs, same NCHW
+    // output and statistics rows as the direct kernel.
     const float *w_wino = nullptr;
     // The 1x1 shortcut of a ResidualBlock whose channel count changes (Model/model.py:116-130), folded into the block's
     // SECOND 3x3 convolution on the narrow levels (conv_direct.hip, conv_direct_skip_ok): the block input (sk_x1 [, sk_x2],
@@ -75,13 +75,56 @@ struct ConvArgs {
     unsigned long long *dbg_buf = nullptr;   // dbg & 8: per-workgroup cycle stamps [grid][4]
 };
 
-int conv2d_launch(const ConvArgs &a, hipStream_t st);
-int conv_kernel_code(const ConvArgs &a);                  // which kernel conv2d_launch would take (codes: include/ipdm_hip.h)
-int conv2d_ws_launch(const ConvArgs &a, hipStream_t st);   // persistent wave-specialised variant (conv_ws.hip)
-bool conv_direct_eligible(const ConvArgs &a);             // narrow layers: direct packed-f32 VALU kernel (conv_direct.hip)
+// The ONE decision about a convolution (conv_plan.hip).  conv_plan reads the shape fields and options of `a`, whether w_up2 / w_wup2 /
+// w_wino / res / sk_w are null, and B (two choices between bit-identical kernels) -- nothing else, so dry runs get the launch's answer.
+struct ConvPlan {
+    int code = 0;                       // kernel code of include/ipdm_hip.h (1..12)
+    int ksplit = 1;                     // K slices (1: no split)
+    size_t split_ws_bytes = 0;          // ... and the bytes of ConvArgs::split_ws they need
+    int stats_rows = 0;                 // rows of ConvArgs::stats per sample (0: no statistics wanted)
+    bool up2 = false;                   // an Upsample layer in its parity form (w_up2): codes 7 and 11, and the narrow ones of code 5 (test entries report it)
+    bool out_planar = false;            // ... that writes `out` parity-planar (codes 7 and 11)
+};
+ConvPlan conv_plan(const ConvArgs &a, bool want_stats, bool may_split);      // want_stats / may_split: the caller will pass ConvArgs::stats / split_ws
+bool conv_planar_ok(const ConvArgs &a);           // the kernel this convolution will run on can read x1 parity-planar (asked before x1_planar is set)
+int conv2d_launch(const ConvArgs &a, hipStream_t st);      // conv_plan(a, a.stats, a.split_ws), then that kernel's launcher
+
+// ---- each kernel's own limits and launcher, in its own file; only conv_plan.hip orders and combines them
+int conv2d_igemm_launch(const ConvArgs &a, hipStream_t st);                   // conv.hip: the 4-wave kernels (code 8)
+bool conv_direct_eligible(const ConvArgs &a);             // narrow layers: direct packed-f32 VALU kernel (conv_direct.hip, code 5)
+bool conv_direct_up2_eligible(const ConvArgs &a);         // ... of those, the narrow Upsample layers in parity form (NCHW output)
+bool conv_direct_skip_ok(const ConvArgs &a);              // this 3x3 layer can carry the block's 1x1 shortcut as extra K chunks
 int conv2d_direct_launch(const ConvArgs &a, hipStream_t st);
-bool conv_nm_eligible(const ConvArgs &a);                 // ... of those, the stride-1 layers that run on the 16-cout MFMA (conv_nm.hip)
+bool conv_nm_eligible(const ConvArgs &a);                 // ... the stride-1 layers that run on the 16-cout MFMA (conv_nm.hip, code 6)
 int conv2d_nm_launch(const ConvArgs &a, hipStream_t st);
+int conv2d_ws_launch(const ConvArgs &a, hipStream_t st);  // persistent wave-specialised kernel (conv_ws.hip, code 3; a.ksplit slices)
+int conv_ws_split(const ConvArgs &a);                     // K slices of a layer with too few tiles for any tiling (1: none)
+bool conv_ws_planar_ok(const ConvArgs &a);
+// ... run as p.ksplit slices into a.split_ws by conv_ws (code 4) or conv_wino2 (code 9), then summed by the combine pass
+int conv2d_splitk_launch(const ConvArgs &a, const ConvPlan &p, hipStream_t st);
+bool conv_up2_eligible(const ConvArgs &a);                // wide Upsample layers as four parity convolutions (conv_ws.hip, code 7)
+int conv2d_up2_launch(const ConvArgs &a, hipStream_t st);
+bool conv_wup2_shape_ok(int Cout, int Cin);               // worth packing the F(2x2,2x2) image of an Upsample layer
+bool conv_wup2_eligible(const ConvArgs &a);               // ... and taking it (conv_wup2.hip, code 11): w_wup2 + that shape rule
+int conv2d_wup2_launch(const ConvArgs &orig, hipStream_t st, int prof_cls);
+bool conv_wino_shape_ok(int Cout, int Cin, int ks, int stride, int interleave);   // worth packing U for this layer
+bool conv_wino_eligible(const ConvArgs &a);               // Winograd F(2x2,3x3) form (conv_wino.hip): shape fields + w_wino decide
+int conv2d_wino_launch(const ConvArgs &a, int code, hipStream_t st);   // code 1 (64-cout tiles), 2 / 9 (conv_wino2; 9: a.ksplit slices), 12 (conv_wino3)
+int conv_wino_split(const ConvArgs &a);                   // K slices conv_wino2 would cut a K-split layer into (0: it cannot)
+bool conv_wino2_eligible(const ConvArgs &a);              // whole 128-cout tiles, 16-channel chunks, enough tiles (or a.ksplit slices)
+bool conv_wino3_eligible(const ConvArgs &a);              // conv_wino3.hip: option conv_bf16x3 + conv_wino2's whole layers
+int conv2d_wino2_launch(const ConvArgs &prepared, hipStream_t st);   // conv_wino2.hip; called by conv2d_wino_launch
+int conv2d_wino3_launch(const ConvArgs &prepared, hipStream_t st);   // conv_wino3.hip; called by conv2d_wino_launch in conv_wino2's place
+// wide 1x1 layers the barrier-free pointwise kernel takes (conv_pw.hip, code 10): by the layer alone with fused statistics, else by the launch's fill
+bool conv_pw_eligible(const ConvArgs &a, bool stats);
+int conv2d_pw_launch(const ConvArgs &a, hipStream_t st);
+// rows of ConvArgs::stats per sample each family writes (conv_up2: conv_wup2 writes the same; conv_splitk: the combine pass)
+int conv_igemm_stats_rows(const ConvArgs &a);
+int conv_direct_stats_rows(const ConvArgs &a);
+int conv_ws_stats_rows(const ConvArgs &a);
+int conv_up2_stats_rows(const ConvArgs &a);
+int conv_splitk_stats_rows(const ConvArgs &a);
+int conv_pw_stats_rows(const ConvArgs &a);
 int conv_k_chunk();   // concat inputs must split at a multiple of this many channels (3x3 kernels)
 int conv_ws_k_chunk(int ks, int interleave);   // K chunk of the kernel a (ks, weight layout) pair runs on: also its concat alignment
 
@@ -115,43 +158,14 @@ struct GnArgs {
 };
 constexpr int GN_SPLIT = 64;
 int gn_tiles_launch(const GnTileArgs &a, hipStream_t st);
-// rows of ConvArgs::stats per sample the kernel chosen for this convolution writes (0: that kernel has no fused statistics)
-int conv_stats_rows(const ConvArgs &a);
-int conv_split(const ConvArgs &a);                 // K slices the launcher would use given a split workspace (1: no split)
-size_t conv_split_ws_bytes(const ConvArgs &a);     // 0 when conv_split(a) == 1
-constexpr int SPLIT_PIX = 2048;                    // pixels per workgroup (= per statistics row) of the combine pass
-int conv_ws_stats_rows(const ConvArgs &a);
-bool conv_up2_eligible(const ConvArgs &a);         // shape fields + w_up2 + w_interleave decide (dry runs included)
-bool conv_wino_eligible(const ConvArgs &a);        // shape fields + w_wino decide
-bool conv_wup2_shape_ok(int Cout, int Cin);        // worth packing the F(2x2,2x2) image of an Upsample layer
-bool conv_wup2_eligible(const ConvArgs &a);        // conv_up2_eligible + w_wup2 + that shape rule (the layer alone)
-int conv2d_wup2_launch(const ConvArgs &orig, hipStream_t st, int prof_cls);   // conv_wup2.hip; called by conv2d_ws_launch
 // [Cin/8][Cout/128][a][b][cout quarter][position 9][k parity][cout 32][k step]
 void conv_pack_weights_wup2(const float *w, int Cout, int Cin, std::vector<float> &packed);
-bool conv_wino_shape_ok(int Cout, int Cin, int ks, int stride, int interleave);   // worth packing U for this layer
-int conv2d_wino_launch(const ConvArgs &a, hipStream_t st);
-int conv_wino_split(const ConvArgs &a);            // K slices conv_wino2 would cut a K-split layer into (0: it cannot)
-bool conv_wino2_eligible(const ConvArgs &a);       // ... of those, the layers the round-4 kernel takes (whole 128-cout tiles, 16-channel chunks)
-int conv2d_wino2_launch(const ConvArgs &prepared, hipStream_t st);   // conv_wino2.hip; called by conv2d_wino_launch
-bool conv_wino3_eligible(const ConvArgs &prepared);                    // conv_wino3.hip: option conv_bf16x3 + conv_wino2's whole layers
-int conv2d_wino3_launch(const ConvArgs &prepared, hipStream_t st);   // ... called by conv2d_wino_launch in conv_wino2's place
 // [Cin/8][Cout/64][xi 16][cout half][k parity][cout 32][k step] = the LDS image of one (chunk, cout tile)
 void conv_pack_weights_wino(const float *w, int Cout, int Cin, std::vector<float> &packed);
-bool conv_ws_planar_ok(const ConvArgs &a);
-bool conv_direct_skip_ok(const ConvArgs &a);       // this 3x3 layer can carry the block's 1x1 shortcut as extra K chunks
-bool conv_direct_up2_eligible(const ConvArgs &a);  // narrow Upsample layers: the same parity form inside conv_direct (NCHW output)
-bool conv_planar_ok(const ConvArgs &a);            // the kernel this convolution runs on can read x1 parity-planar
 // [4 parities][Cin_pad][2x2][cout_pad], each parity packed like a ks = 2 convolution of the same interleave
 void conv_pack_weights_up2(const float *w, int Cout, int Cin, int interleave, std::vector<float> &packed);
 // parity-planar [B*C][2][2][H/2][W/2] -> NCHW [B*C][H][W]
 int planar_to_linear_launch(const float *src, float *dst, long planes, int H, int W, hipStream_t st);
-int conv_ws_split(const ConvArgs &a);
-bool conv_pw_eligible(const ConvArgs &a);          // wide 1x1 layers: the barrier-free pointwise kernel (conv_pw.hip) takes THIS launch
-bool conv_pw_layer_ok(const ConvArgs &a);          // ... could take the layer (shape rule)
-bool conv_pw_stats_layer(const ConvArgs &a);       // ... takes it when the layer leaves fused statistics (a rule of the layer alone)
-int conv_pw_stats_rows(const ConvArgs &a);
-int conv2d_pw_launch(const ConvArgs &a, hipStream_t st);
-int conv_direct_stats_rows(const ConvArgs &a);
 size_t gn_partials_bytes(int B, int groups);
 int gn_stats_launch(const GnArgs &a, hipStream_t st);
 

@@ -514,6 +514,57 @@ def test_gated_edge_cases_cover_every_kernel_code():
     assert {e[2] for e in EDGE_CASES} == set(range(1, 13))
 
 
+# profile classes (ipdm_profile_begin / ipdm_profile_end) in which the launches of a kernel code may be recorded
+CODE_PROFILE_CLASSES = {1: {3}, 2: {5}, 9: {5}, 12: {5}, 5: {4, 6}, 6: {4, 6}, 3: {0, 1}, 4: {0, 1}, 8: {0, 1}, 10: {0, 1}}
+
+
+def test_kernel_code_is_the_kernel_that_ran():
+    """Ties the code the edge cases assert (ipdm_conv_kernel_code: what the plan says) to the launch that happened: under the
+    row's options, the profile classes with a non-zero launch count are the ones the asserted code's kernels record in (exactly
+    for the Winograd kernels, whose classes tell them apart); a code-11 Upsample chain records one launch in class 7."""
+    import contextlib
+    import ctypes as C
+    from ipdm_pytorch_amd import _lib
+    NC = _lib.PROF_CLASSES
+
+    def launched(run):
+        fl, ms, nl = (C.c_double * NC)(), (C.c_double * NC)(), (C.c_int64 * NC)()
+        _lib.call("ipdm_profile_begin", 64)
+        try:
+            run()
+            torch.cuda.synchronize()
+        finally:
+            _lib.call("ipdm_profile_end", C.byref(fl), C.byref(ms), C.byref(nl), NC)
+        return list(nl)
+
+    seen = set()
+    for kind, case, code, opts in EDGE_CASES:
+        key = (case, code, tuple(sorted(opts.items())))
+        if key in seen or (kind.startswith("up-") and code != 11):
+            continue
+        seen.add(key)
+        with contextlib.ExitStack() as st:
+            for k, v in opts.items():
+                st.enter_context(_lib.option(k, v))
+            if kind.startswith("up-"):
+                nl = launched(lambda: _up_conv_chain(case))
+                assert nl[7] == 1, (case, nl)
+                continue
+            B, C1, C2, Hs, Ws, H, W, Cout, ks, stride, act, res = case
+            assert stride == 1 and (H, W) == (Hs, Ws)
+            assert _lib.lib().ipdm_conv_kernel_code(B, Cout, C1 + C2, ks, stride, H, W) == code, (case, code)
+            seed = 4600 + sum(case[:8])
+            x1 = torch.from_numpy(synth.hash_normal((B, C1, Hs, Ws), seed))
+            x2 = torch.from_numpy(synth.hash_normal((B, C2, Hs, Ws), seed + 1)) if C2 else None
+            w = torch.from_numpy(synth.hash_normal((Cout, C1 + C2, ks, ks), seed + 2)) / np.sqrt((C1 + C2) * ks * ks)
+            gamma, beta = torch.ones(C1 + C2), torch.zeros(C1 + C2)
+            r = torch.from_numpy(synth.hash_normal((B, Cout, H, W), seed + 3)) if res else None
+            nl = launched(lambda: _op_conv(x1, w, torch.zeros(Cout), ks, act=act, gamma=gamma, beta=beta, res=r, x2=x2))
+            ran = {c for c in range(NC) if nl[c]}
+            allowed = CODE_PROFILE_CLASSES[code]
+            assert ran and ran <= allowed and (len(allowed) > 1 or ran == allowed), (case, code, nl)
+
+
 @pytest.mark.parametrize("T", [1, 65, 1827, 7125])
 @pytest.mark.parametrize("kind", ["one_hot", "equal_keys", "v_offset"])
 def test_attention_accuracy_edge_cases(kind, T):
