@@ -454,7 +454,7 @@ size_t attention_scratch_floats(int B, int heads, int d, int T)
     return Z > 1 ? (size_t)Z * B * heads * (d + 2) * T : 0;
 }
 
-int attention_launch(const float *qkv, float *out, int B, int heads, int d, int T, hipStream_t st, float *scratch)
+int attention_launch(const float *qkv, float *out, int B, int heads, int d, int T, hipStream_t st, float *scratch, float *planes)
 {
     IPDM_REQUIRE(qkv && out && B > 0 && heads > 0 && T > 0, "attention: bad argument");
     if (d != 64 && d != 32) { set_error("attention: head dim %d unsupported (kernel is specialised for 64 and 32)", d); return IPDM_ERR_UNSUPPORTED; }
@@ -470,7 +470,9 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
         const int Z = scratch ? attention_kv_split(B, heads, d, T) : 1;
         const long wg1 = (long)cdiv(T, 128) * B * heads;
         const bool seq = Z >= 4 && opt(OPT_ATTN_NO_ZSEQ) == 0 && wg1 >= 192;
-        attention_bx3_launch(qkv, out, B, heads, T, scale, Z, seq, scratch, st);
+        // the planes are used only where attention_planes_floats sized them (the same options, read here again: they are per call)
+        if (!attention_planes_floats(B, heads, d, T)) planes = nullptr;
+        attention_bx3_launch(qkv, out, B, heads, T, scale, Z, seq, scratch, planes, st);
         if (Z > 1 && !seq)
             hipLaunchKernelGGL((attention_combine_kernel<64>), dim3(cdiv(T, 256), B * heads, 4), dim3(256), 0, st, scratch, out, T, Z, cdiv(T, KV));
     } else if (d == 64 && !legacy) {
@@ -520,15 +522,22 @@ extern "C" int32_t ipdm_attention_kernel_code(int32_t d)
 extern "C" int ipdm_op_attention(const float *d_qkv, float *d_out, int32_t B, int32_t heads, int32_t d, int32_t T,
                                  void *stream)
 {
-    // test helper: allocates the split mode's scratch itself (the UNet executor takes it from its workspace)
-    float *scratch = nullptr;
+    // test helper: allocates the split mode's scratch and the K/V planes itself (the UNet executor takes them from its workspace).
+    // The planes start as the byte 0xFF, a NaN pattern in bf16: a tile tail the split pass failed to write shows in the output
+    float *scratch = nullptr, *planes = nullptr;
     if (ipdm::attention_scratch_floats(B, heads, d, T)) {
         IPDM_HIP_CHECK(hipMalloc((void **)&scratch, ipdm::attention_scratch_floats(B, heads, d, T) * sizeof(float)));
     }
-    const int rc = ipdm::attention_launch(d_qkv, d_out, B, heads, d, T, (hipStream_t)stream, scratch);
-    if (scratch) {
+    if (const size_t pfl = ipdm::attention_planes_floats(B, heads, d, T)) {
+        hipError_t e = hipMalloc((void **)&planes, pfl * sizeof(float));
+        if (e == hipSuccess) e = hipMemsetAsync(planes, 0xFF, pfl * sizeof(float), (hipStream_t)stream);
+        if (e != hipSuccess) { (void)hipFree(scratch); (void)hipFree(planes); IPDM_HIP_CHECK(e); }
+    }
+    const int rc = ipdm::attention_launch(d_qkv, d_out, B, heads, d, T, (hipStream_t)stream, scratch, planes);
+    if (scratch || planes) {
         (void)hipStreamSynchronize((hipStream_t)stream);
         (void)hipFree(scratch);
+        (void)hipFree(planes);
     }
     return rc;
 }

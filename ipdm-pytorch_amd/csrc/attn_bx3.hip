@@ -14,12 +14,14 @@
 // Layout, per 32-key tile:
 //   * S[s, t] = sum_c K[c, s] Q[c, t]: A = K (key on the MFMA row), B = Q (query on the lane); k-step kb of lane half h contracts
 //     channels 16 kb + 8 h + e (e = 0..7).  Q is split once per wave into registers (both d^(-1/4) factors folded in, as in attn.hip);
-//     K is split by the producer waves into three planes [s][c] (pitch KP: the 16-byte reads of 16 lanes hit 16 disjoint bank quads);
+//     K is split into three planes [s][c] (pitch KP in LDS: the 16-byte reads of 16 lanes hit 16 disjoint bank quads) -- once per
+//     layer by attention_presplit_kernel, whose planes the producer waves only copy (round 12: every query workgroup of a (sample,
+//     head) used to split the same tiles again, 56 times at T = 7125), or by the producers themselves under attn_no_presplit;
 //   * the online softmax of attn.hip (running max / sum per query, the alpha == 1 skip, the ragged last tile masked; exp(s - m) as
 //     2^((s - m) log2e) so that the maximum's P is exactly 1);
 //   * O[c, t] += sum_s V[c, s] P[s, t]: B = P straight from the score registers -- register 8 kb + e of lane half h holds key
 //     16 kb + 8 (e >> 2) + 4 h + (e & 3), which is the MFMA's k-index 8 h + e of slab kb once V's key axis is permuted the same way:
-//     the producers store key s of a tile at position s with bits 2 and 3 swapped, three planes [c][s'] (pitch VP).  P is split in
+//     key s of a tile is stored at position s with bits 2 and 3 swapped, three planes [c][s'] (pitch VP).  P is split in
 //     registers; nothing moves between lanes;
 //   * 4 consumer waves (32 queries each) + 2 producer waves, the tile double-buffered in LDS (57 KB), two workgroups per CU: two
 //     consumer waves share each SIMD (168 VGPRs each).  The producers load the next tile into registers behind each hand-over;
@@ -46,6 +48,12 @@ constexpr int KP = 72;                         // K plane pitch [s][c], bf16 (14
 constexpr int VP = 40;                         // V plane pitch [c][s'], bf16 (80 B)
 constexpr int KPLANE = KT * KP, VPLANE = D * VP;
 constexpr int STAGE = 3 * KPLANE + 3 * VPLANE; // bf16 per stage
+// The pre-split planes in memory (attention_presplit_kernel): per (sample, head) and 32-key tile the six planes UNPADDED, in 16-byte
+// chunks -- K term p: chunks 256 p + 8 s + cg (key s, channels 8 cg .. 8 cg + 7); V term p: chunks 768 + 256 p + 4 c + g (channel c,
+// positions 8 g .. 8 g + 7 of the permuted key axis).  The LDS pitches are applied on the LDS write: chunk j of a K plane goes to
+// (j >> 3) KP + 8 (j & 7), of a V plane to (j >> 2) VP + 8 (j & 3).  24 576 B per tile: 12 chunks per producer thread, lane-linear.
+constexpr int PCHUNK = 256;                    // 16-byte chunks per plane and tile
+constexpr int TILE_CHUNKS = 6 * PCHUNK;
 
 // (a, b) -> two bf16 in one dword, a in the low half, rounded to nearest even
 __device__ inline unsigned pk_bf16(float a, float b)
@@ -88,9 +96,52 @@ __device__ inline f32x16 mma6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 c
     return mma(a[0], b[0], c);
 }
 
-template <bool ZSEQ>      // ZSEQ: a workgroup walks all key slices of its queries (zseq > 1)
+// One 32-key tile of a (sample, head), split once for every query workgroup of the layer: K and V go through LDS as f32 (reads
+// coalesced along the keys, pitch 33: the transposed reads of K are conflict-free), every element through split3 -- the producers'
+// own function, so the three terms are their bits -- and out as whole 16-byte chunks, lane-linear.  Keys at or beyond T are written
+// as zeros in all planes (the workspace is recycled: a stale NaN pattern would turn P = 0 into NaN).
+__global__ void __launch_bounds__(256) attention_presplit_kernel(const float *__restrict__ qkv, u32x4 *__restrict__ planes, int heads, int T)
+{
+    constexpr int FP = KT + 1;
+    __shared__ float kf[D * FP], vf[D * FP];
+    const int bh = blockIdx.y, b = bh / heads, head = bh % heads;
+    const float *qp = qkv + ((size_t)b * heads * 3 * D + (size_t)head * 3 * D) * T;
+    const int s0 = blockIdx.x * KT, tid = threadIdx.x;
+    {
+        const int key = tid & 31, c0 = tid >> 5;
+        const bool in = s0 + key < T;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int c = c0 + 8 * r;
+            kf[c * FP + key] = in ? qp[(size_t)(D + c) * T + s0 + key] : 0.0f;
+            vf[c * FP + key] = in ? qp[(size_t)(2 * D + c) * T + s0 + key] : 0.0f;
+        }
+    }
+    __syncthreads();
+    u32x4 *pt = planes + ((size_t)bh * gridDim.x + blockIdx.x) * TILE_CHUNKS + tid;
+    const int ks = tid >> 3, kg = tid & 7, vc = tid >> 2, vg = tid & 3;
+    const int vkey = 16 * (vg >> 1) + 4 * (vg & 1);               // position 8 vg + e holds key vkey + 8 (e >> 2) + (e & 3)
+    u32x4 hk[3], hv[3];
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const Split3 sk = split3(kf[(8 * kg + e) * FP + ks], kf[(8 * kg + e + 1) * FP + ks]);
+        const Split3 sv = split3(vf[vc * FP + vkey + 8 * (e >> 2) + (e & 3)], vf[vc * FP + vkey + 8 * (e >> 2) + (e & 3) + 1]);
+#pragma unroll
+        for (int p = 0; p < 3; ++p) { hk[p][e / 2] = sk.h[p]; hv[p][e / 2] = sv.h[p]; }
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        pt[p * PCHUNK] = hk[p];
+        pt[(3 + p) * PCHUNK] = hv[p];
+    }
+}
+
+// ZSEQ: a workgroup walks all key slices of its queries (zseq > 1).  PRE: the producers copy the tile's planes from `planes`
+// (attention_presplit_kernel wrote them); else they split K and V themselves while staging (option attn_no_presplit: the bit oracle)
+template <bool ZSEQ, bool PRE>
 __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__restrict__ qkv, float *__restrict__ out, int heads, int T,
-                                                                float scale, int zsplit, float *__restrict__ part, int zseq)
+                                                                float scale, int zsplit, float *__restrict__ part, int zseq,
+                                                                const u32x4 *__restrict__ planes)
 {
     // zsplit > 1: blockIdx.z takes a slice of the key tiles and leaves its UNNORMALISED output, running maximum and sum in `part`
     // (attention_combine_kernel merges the slices); zseq > 1: this workgroup walks all zseq slices itself
@@ -106,6 +157,41 @@ __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__re
     // (a scalar branch: the producer code is not laid out behind the consumers' under an exec mask)
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= 4) {
         // ------------------------------------------------------------------ producers (2 waves)
+        if constexpr (PRE) {
+            // copy only: twelve 16-byte chunks per thread and tile, lane-linear in memory, no arithmetic on the data.  Buffer loads as in
+            // the split arm below: the tile's offset is scalar, and the resource ends with this (sample, head)'s planes
+            const int tid = threadIdx.x - 256;
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(planes + (size_t)bh * ntiles * TILE_CHUNKS), 0,
+                                                                                  ntiles * TILE_CHUNKS * 16, 0x00020000);
+            int ko[2], vo[2];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const int j = tid + 128 * n;
+                ko[n] = (j >> 3) * KP + 8 * (j & 7);
+                vo[n] = 3 * KPLANE + (j >> 2) * VP + 8 * (j & 3);
+            }
+            u32x4 r[12];
+            const auto load = [&](int it) {
+#pragma unroll
+                for (int i = 0; i < 12; ++i)
+                    r[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16, (it * TILE_CHUNKS + 128 * i) * 16, 0));
+            };
+            const auto store = [&](int it) {
+                unsigned short *st = lds + (it & 1) * STAGE;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    *reinterpret_cast<u32x4 *>(st + (i >> 1) * KPLANE + ko[i & 1]) = r[i];
+                    *reinterpret_cast<u32x4 *>(st + (i >> 1) * VPLANE + vo[i & 1]) = r[6 + i];
+                }
+            };
+            if (it0 < it1) load(it0);
+            for (int it = it0; it < it1; ++it) {
+                store(it);
+                if (it + 1 < it1) load(it + 1);
+                __syncthreads();
+            }
+            return;
+        }
         // per tile and thread: two K tasks (key ks, channels 8 kg .. 8 kg + 7) and two V tasks (channel vc, positions 8 vg .. 8 vg + 7 of
         // the permuted key axis); loads coalesced along the keys for K.  Keys beyond T exist only in the last tile: their lanes get an
         // out-of-range offset (the buffer load returns 0).
@@ -328,12 +414,25 @@ __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__re
 
 namespace ipdm {
 
+size_t attention_planes_floats(int B, int heads, int d, int T)
+{
+    if (d != D || opt(OPT_ATTN_EXACT_F32) || opt(OPT_ATTN_LEGACY) || opt(OPT_ATTN_NO_PRESPLIT)) return 0;
+    return (size_t)B * heads * cdiv(T, KT) * TILE_CHUNKS * 4;
+}
+
 void attention_bx3_launch(const float *qkv, float *out, int B, int heads, int T, float scale, int Z, bool seq, float *scratch,
-                          hipStream_t st)
+                          float *planes, hipStream_t st)
 {
     const dim3 grid(cdiv(T, 128), B * heads, seq ? 1 : Z);
-    if (seq) hipLaunchKernelGGL((attention_bx3_kernel<true>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, 1, (float *)nullptr, Z);
-    else hipLaunchKernelGGL((attention_bx3_kernel<false>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, Z, scratch, 1);
+    u32x4 *pl = reinterpret_cast<u32x4 *>(planes);
+    if (pl) hipLaunchKernelGGL(attention_presplit_kernel, dim3(cdiv(T, KT), B * heads), dim3(256), 0, st, qkv, pl, heads, T);
+    if (seq) {
+        if (pl) hipLaunchKernelGGL((attention_bx3_kernel<true, true>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, 1, (float *)nullptr, Z, pl);
+        else hipLaunchKernelGGL((attention_bx3_kernel<true, false>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, 1, (float *)nullptr, Z, pl);
+    } else {
+        if (pl) hipLaunchKernelGGL((attention_bx3_kernel<false, true>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, Z, scratch, 1, pl);
+        else hipLaunchKernelGGL((attention_bx3_kernel<false, false>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, Z, scratch, 1, pl);
+    }
 }
 
 }  // namespace ipdm

@@ -854,7 +854,12 @@ struct Fwd {
         const int heads = net->cfg.num_heads, hd = x->C / heads;
         const size_t sfl = attention_scratch_floats(net->B, heads, hd, H * W);
         Tensor *scr = sfl ? make((int)((sfl + (size_t)net->B * H * W - 1) / ((size_t)net->B * H * W)), H, W) : nullptr;
-        if (!rc && !net->dry) rc = attention_launch(ptr(qkv), wptr(a), net->B, heads, hd, H * W, net->st, scr ? wptr(scr) : nullptr);
+        // K and V of the bf16 x 3 kernel as bf16 planes, split once for all query workgroups of the layer (attn_bx3.hip)
+        const size_t pfl = attention_planes_floats(net->B, heads, hd, H * W);
+        Tensor *pl = pfl ? make((int)((pfl + (size_t)net->B * H * W - 1) / ((size_t)net->B * H * W)), H, W) : nullptr;
+        if (!rc && !net->dry)
+            rc = attention_launch(ptr(qkv), wptr(a), net->B, heads, hd, H * W, net->st, scr ? wptr(scr) : nullptr, pl ? wptr(pl) : nullptr);
+        if (pl) release(pl);
         if (scr) release(scr);
         release(qkv);
         Tensor *o = conv(a, nullptr, ap.proj, 1, 0, ap.proj.b, x, H, W, nullptr, true);
@@ -1515,18 +1520,20 @@ extern "C" int ipdm_bench_attention(int32_t B, int32_t heads, int32_t d, int32_t
     int rc = 0;
     float *d_scr = nullptr;
     if (attention_scratch_floats(B, heads, d, T)) IPDM_HIP_CHECK(hipMalloc((void **)&d_scr, attention_scratch_floats(B, heads, d, T) * 4));
-    for (int i = 0; i < 2 && !rc; ++i) rc = attention_launch(d_qkv, d_out, B, heads, d, T, nullptr, d_scr);
+    float *d_pl = nullptr;      // (the split pass runs inside every timed launch)
+    if (attention_planes_floats(B, heads, d, T)) IPDM_HIP_CHECK(hipMalloc((void **)&d_pl, attention_planes_floats(B, heads, d, T) * 4));
+    for (int i = 0; i < 2 && !rc; ++i) rc = attention_launch(d_qkv, d_out, B, heads, d, T, nullptr, d_scr, d_pl);
     hipEvent_t e0, e1;
     IPDM_HIP_CHECK(hipEventCreate(&e0));
     IPDM_HIP_CHECK(hipEventCreate(&e1));
     IPDM_HIP_CHECK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && !rc; ++i) rc = attention_launch(d_qkv, d_out, B, heads, d, T, nullptr, d_scr);
+    for (int i = 0; i < iters && !rc; ++i) rc = attention_launch(d_qkv, d_out, B, heads, d, T, nullptr, d_scr, d_pl);
     IPDM_HIP_CHECK(hipEventRecord(e1, nullptr));
     IPDM_HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0;
     IPDM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     *avg_ms = ms / iters;
-    (void)hipFree(d_qkv); (void)hipFree(d_out); (void)hipFree(d_scr); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    (void)hipFree(d_qkv); (void)hipFree(d_out); (void)hipFree(d_scr); (void)hipFree(d_pl); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return rc;
 }
 

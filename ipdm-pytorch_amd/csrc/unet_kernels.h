@@ -170,11 +170,16 @@ size_t gn_partials_bytes(int B, int groups);
 int gn_stats_launch(const GnArgs &a, hipStream_t st);
 
 // scratch: attention_scratch_floats() floats (the partial outputs of the key-slice split; null: never split)
-int attention_launch(const float *qkv, float *out, int B, int heads, int d, int T, hipStream_t st, float *scratch = nullptr);
+// planes: attention_planes_floats() floats (K and V of the bf16 x 3 kernel split once per layer into bf16 planes, written by a pass
+// launched here in front of the kernel; null: its producers split per tile themselves)
+int attention_launch(const float *qkv, float *out, int B, int heads, int d, int T, hipStream_t st, float *scratch = nullptr,
+                     float *planes = nullptr);
 size_t attention_scratch_floats(int B, int heads, int d, int T);
+// 0 when the planes are not used (d != 64, options attn_exact_f32, attn_legacy, attn_no_presplit); a rule of the layer and the options
+size_t attention_planes_floats(int B, int heads, int d, int T);
 // d = 64 on the bf16 matrix pipe (attn_bx3.hip): Z key slices (attention_kv_split), walked inside the workgroup when seq, else as a
 // split grid whose partial outputs go to scratch (the caller launches the combine pass)
-void attention_bx3_launch(const float *qkv, float *out, int B, int heads, int T, float scale, int Z, bool seq, float *scratch,
+void attention_bx3_launch(const float *qkv, float *out, int B, int heads, int T, float scale, int Z, bool seq, float *scratch, float *planes,
                           hipStream_t st);
 
 // time embedding: emb = Linear(SiLU(Linear(sinusoid(t)))) ; out = SiLU(emb)  (Model/model.py:14-32,218-222,105-108)
