@@ -240,6 +240,51 @@ int ipdm_guided_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_i
                         int32_t H, int32_t W, const int32_t *t_start, int32_t n_pass, const ipdm_reverse_args *a,
                         int64_t *draws_used, void *d_ws, size_t ws_bytes, void *stream);
 
+/* The sparse (DDIM) sampler, sample_method = "sparse" (Utils/train_test_utils.py:445-453,505-514), in the same form.
+ * IPDM_ABI_VERSION stays 5; a binder detects these entries by symbol (dlsym of ipdm_sparse_reverse).
+ *
+ * ipdm_ddim_step_rng = ipdm_randn + ipdm_ddim_step (one iteration of ddim_sample, Model/model.py:687-718) with the N(0,1)
+ * value of (seed, slice_id0 + b, draw, element) made in registers: same bits.  ddim_eta == 0 runs a form of the kernel without
+ * the generator and gives the bits of ipdm_ddim_step(d_noise = NULL); the caller still counts the draw (:716).  Tensors are
+ * [B, n_per_slice], n_per_slice > 1; the 16-byte path needs n_per_slice % 4 == 0 and 16-byte aligned pointers. */
+int ipdm_ddim_step_rng(const ipdm_schedule *s, int32_t t, int32_t t_prev, const float *d_eps_pred, const float *d_x_t,
+                       const float *d_cond, uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B,
+                       int64_t n_per_slice, double lambda_scalar, double ddim_eta, int32_t clip_denoised, void *d_ws,
+                       size_t ws_bytes, void *stream);
+
+/* The timestep sequences of ddim_sample (Model/model.py:668-681) for a caller without numpy.  Host only.  method "uniform":
+ * np.linspace(t_start - 1, 0, n + 1).astype(int)[:-1]; "quad": (np.linspace(0, sqrt(0.8 * timesteps), n) ** 2).astype(int)
+ * (t_start is not part of it, as in the reference).  seq[n]; prev[n] = seq[1:] followed by 0.  An unknown method, n <= 0 or
+ * t_start outside [1, timesteps]: IPDM_ERR_INVALID. */
+int ipdm_ddim_sequence(const char *method, int32_t timesteps, int32_t t_start, int32_t n, int32_t *seq, int32_t *prev);
+
+/* Arguments of sparse_guided_reverse_process (Model/model.py:727-737) that are not per pass. */
+#define IPDM_NOISE_COUNTER 1     /* draw k of the call is draw (seed, slice_id0 + b, draw0 + k) of ipdm_randn's generator */
+#define IPDM_NOISE_INJECTED 2    /* draw k of the call is d_noise[k] (parity mode) */
+typedef struct ipdm_sparse_args {
+    int32_t clip_denoised;
+    double ddim_eta, eta;
+    int32_t noise;           /* IPDM_NOISE_COUNTER or IPDM_NOISE_INJECTED; anything else is refused */
+    uint64_t seed;
+    int64_t slice_id0, draw0;
+    const float *d_noise;    /* injected draws [n_draws, B, H*W], used in order; B*H*W % 4 == 0 */
+} ipdm_sparse_args;
+
+/* sparse_guided_reverse_process (Model/model.py:727-759) in one call: q_sample of d_cond [B,H,W] at t_q (t_start[0], :739);
+ * then per pass p its n_steps[p] DDIM steps { UNet forward at t, step t -> t_prev under guidance lambda[p] } (ddim_sample,
+ * :687-718) over t_seq / t_prev, the passes' sequences one after another (sum(n_steps) entries each, e.g. from
+ * ipdm_ddim_sequence); after pass p, d_iters[p] = x (:758) and the condition of the next pass = eta*x + (1-eta)*d_cond (:757,
+ * the bits of ipdm_axpbypcz).  x carries over from pass to pass, not re-noised and not clamped.  lambda[n_pass] is the
+ * caller's np.arange ladder (:742-743).  Draw 0 of the call is the q_sample, every step takes the next one whatever ddim_eta
+ * (:716); *draws_used (may be NULL) receives 1 + sum(n_steps).  d_iters [n_pass, B, H, W] must not overlap d_cond.  d_ws as
+ * ipdm_reverse_workspace_bytes sizes it; no allocation, no synchronisation.  Bad arguments (NULL handles or arrays,
+ * n_pass <= 0, a step count <= 0, t_q or a timestep outside [0, T), a noise kind that is neither, a short workspace) are
+ * refused before any launch. */
+int ipdm_sparse_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_cond, float *d_iters, int32_t B, int32_t H,
+                        int32_t W, int32_t t_q, const int32_t *n_steps, int32_t n_pass, const int32_t *t_seq,
+                        const int32_t *t_prev, const double *lambda, const ipdm_sparse_args *a, int64_t *draws_used,
+                        void *d_ws, size_t ws_bytes, void *stream);
+
 /* op-level entry points (parity tests of the individual kernels against torch-CPU ops) */
 /* F.conv2d(cat(x1,x2) [upsampled to H,W by nearest], w, b, stride, padding=k/2) with optional fused
  * GroupNorm(+SiLU) prologue over the concatenated input and optional residual add.

@@ -38,6 +38,14 @@ class ReverseArgs(C.Structure):
                 ("d_noise", C.c_void_p), ("d_ldct", C.c_void_p)]
 
 
+class SparseArgs(C.Structure):
+    """ipdm_sparse_args: what is not per pass in a call of the native sparse (DDIM) sampler (ipdm_sparse_reverse)."""
+    _fields_ = [("clip_denoised", C.c_int32), ("ddim_eta", C.c_double), ("eta", C.c_double), ("noise", C.c_int32),
+                ("seed", C.c_uint64), ("slice_id0", C.c_int64), ("draw0", C.c_int64), ("d_noise", C.c_void_p)]
+
+
+NOISE_COUNTER, NOISE_INJECTED = 1, 2      # ipdm_sparse_args.noise
+
 _vp, _i32, _i64, _u64, _f32, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); restype int => status code checked by _call
@@ -92,6 +100,11 @@ PROTOTYPES = {
                                     _vp, _sz, _vp]),
     "ipdm_guided_reverse": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(ReverseArgs),
                                       C.POINTER(_i64), _vp, _sz, _vp]),
+    "ipdm_ddim_step_rng": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _u64, _i64, _i64, _vp, _i32, _i64, _f64, _f64, _i32, _vp, _sz,
+                                     _vp]),
+    "ipdm_ddim_sequence": (C.c_int, [C.c_char_p, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "ipdm_sparse_reverse": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32),
+                                      C.POINTER(_i32), C.POINTER(_f64), C.POINTER(SparseArgs), C.POINTER(_i64), _vp, _sz, _vp]),
     "ipdm_op_conv2d": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
                                  _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ipdm_op_conv_gn_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp,

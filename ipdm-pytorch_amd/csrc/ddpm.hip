@@ -358,19 +358,13 @@ __global__ void __launch_bounds__(256) ddim_apply_kernel(const float *__restrict
     }
 }
 
-extern "C" int ipdm_ddim_step(const ipdm_schedule *s, int32_t t, int32_t t_prev, const float *d_eps_pred, const float *d_x_t,
-                              const float *d_cond, const float *d_noise, float *d_out, int32_t B, int64_t n_per_slice,
-                              double lambda_scalar, double ddim_eta, int32_t clip_denoised, void *d_ws, size_t ws_bytes,
-                              void *stream)
+int ipdm::ddim_coef_fill(StepCoef &k, const char *who, const ipdm_schedule *s, int t, int t_prev, double lambda_scalar,
+                         double ddim_eta, int clip_denoised)
 {
-    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_cond && d_out && d_ws && B > 0 && n_per_slice > 1, "ddim_step: bad argument");
-    IPDM_REQUIRE(t >= 0 && t < s->T && t_prev >= 0 && t_prev < s->T, "ddim_step: timestep out of range");
-    IPDM_REQUIRE(ddim_eta == 0.0 || d_noise, "ddim_step: ddim_eta != 0 needs a noise draw");
-    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("ddim_step: workspace too small"); return IPDM_ERR_WORKSPACE; }
+    IPDM_REQUIRE(s && t >= 0 && t < s->T && t_prev >= 0 && t_prev < s->T, "%s: timestep out of range", who);
     float c[8];
     int rc = ipdm_schedule_coeffs(s, t, c);
     if (rc) return rc;
-    StepCoef k;
     k.sa = c[0]; k.s1m = c[1]; k.sr = k.srm1 = k.c1 = k.c2 = k.sigma = 0.0f;
     k.w_pred = (float)(1.0 - lambda_scalar);
     k.w_cond = (float)lambda_scalar;
@@ -383,6 +377,20 @@ extern "C" int ipdm_ddim_step(const ipdm_schedule *s, int32_t t, int32_t t_prev,
     const float sig = eta * sqrtf((1.0f - acp) / (1.0f - act) * (1.0f - act / acp));
     k.d_dir = sqrtf(1.0f - acp - sig * sig);
     k.d_sig = eta * c[7];
+    return IPDM_OK;
+}
+
+extern "C" int ipdm_ddim_step(const ipdm_schedule *s, int32_t t, int32_t t_prev, const float *d_eps_pred, const float *d_x_t,
+                              const float *d_cond, const float *d_noise, float *d_out, int32_t B, int64_t n_per_slice,
+                              double lambda_scalar, double ddim_eta, int32_t clip_denoised, void *d_ws, size_t ws_bytes,
+                              void *stream)
+{
+    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_cond && d_out && d_ws && B > 0 && n_per_slice > 1, "ddim_step: bad argument");
+    StepCoef k;
+    int rc = ddim_coef_fill(k, "ddim_step", s, t, t_prev, lambda_scalar, ddim_eta, clip_denoised);
+    if (rc) return rc;
+    IPDM_REQUIRE(ddim_eta == 0.0 || d_noise, "ddim_step: ddim_eta != 0 needs a noise draw");
+    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("ddim_step: workspace too small"); return IPDM_ERR_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
     double *ws = (double *)d_ws;
     const long n = n_per_slice;

@@ -112,4 +112,9 @@ static inline void step_coef_fill(StepCoef &k, const float c[8], int t, double l
 void step_stats_launch(const float *d_eps_pred, const float *d_x_t, const float *d_x0, const float *d_lambda_map, long n, int B,
                        const StepCoef &k, double *ws, hipStream_t st);
 
+// Host side of a DDIM step (ddpm.hip, where the schedule's tables are): the coefficient block of ipdm_ddim_step /
+// ipdm_ddim_step_rng for the update t -> t_prev.  Refuses a timestep outside the schedule (status code, error text under `who`).
+int ddim_coef_fill(StepCoef &k, const char *who, const ipdm_schedule *s, int t, int t_prev, double lambda_scalar, double ddim_eta,
+                   int clip_denoised);
+
 }  // namespace ipdm

@@ -1,23 +1,30 @@
 // The reverse loop of the guided partial-diffusion sampler inside the library: one C call per outer pass
 // (ipdm_reverse_pass) or per fixed-schedule process (ipdm_guided_reverse), and the elementwise kernels written for it --
 // q_sample and the third pass of a guided step with the N(0,1) draw made in registers instead of read from a buffer that
-// an ipdm_randn launch wrote, and a pass epilogue (clamp + guide update in one launch).
+// an ipdm_randn launch wrote, and a pass epilogue (clamp + guide update in one launch).  The sparse (DDIM) sampler has the
+// same form: one C call per process (ipdm_sparse_reverse), its step with the draw in registers (ipdm_ddim_step_rng) and
+// its timestep sequences for a caller without numpy (ipdm_ddim_sequence).
 //
 // Replaces (reference file:line): the control flow of GaussianDiffusion.guided_reverse_process with an explicit t_start
 // list (Model/model.py:517-642): q_sample (:537-541), the inner loop of p_sample_condition calls with its guidance choice
 // (:542-568), the clamp after a pass (:569-573), the guidance map after pass 0 (:574-614), the guide updates and the reset
-// of x after pass 0 (:619-635), the final average (:637-638).
+// of x after pass 0 (:619-635), the final average (:637-638).  For the sparse sampler: the timestep sequences and the step
+// loop of ddim_sample (:664-724) and all of sparse_guided_reverse_process (:727-759).
 //
 // Bits.  Every kernel here gives exactly the bits of the launches it replaces (ipdm_randn into a buffer, then ipdm_q_sample /
-// ipdm_ddpm_step / ipdm_clamp + ipdm_axpbypcz).  The noise is the same pure function of (seed, slice, draw, element)
+// ipdm_ddpm_step / ipdm_ddim_step / ipdm_clamp + ipdm_axpbypcz).  The noise is the same pure function of (seed, slice, draw, element)
 // (randn_quad, ddpm_dev.h); the statistics passes of a step are ddpm.hip's own launches; the per-element expressions are
 // written with every rounding spelled out -- `#pragma clang fp contract(off)` and explicit fmaf -- in the form the compiler
-// gives ddpm.hip's kernels (read from their gfx950 code; tests/test_gpu_native_reverse.py holds the two to torch.equal):
+// gives ddpm.hip's kernels (read from their gfx950 code; tests/test_gpu_native_reverse.py and tests/test_gpu_native_sparse.py
+// hold the two to torch.equal):
 //   q_sample_kernel     out  = fma(sa, x, s1m*z)
 //   step_apply_kernel   cond = fma(-sa, x0, x) / s1m;  mix = wp*p + wc*c;  xr = sr*x - srm1*eps   (products rounded)
 //                       mean = fma(c1, xr, c2*x);  out = mean + sigma*z                           (product rounded)
 //   axpbypcz_kernel     v = a*x + b*y (products rounded);  v = fma(c, z, v)
+//   ddim_apply_kernel   cond = fma(-sa, x0, x) / s1m;  mix = wp*p + wc*c (products rounded);  xr = fma(-d_a, eps, x) / d_b
+//                       v = d_p*xr + d_dir*eps (products rounded);  with a draw: out = fma(d_sig, z, v)
 #include <cmath>
+#include <cstring>
 #include "common.h"
 #include "ddpm_dev.h"
 
@@ -124,6 +131,62 @@ __global__ void __launch_bounds__(256) step_apply_rng_kernel(const float *__rest
     }
 }
 
+// one element of ddim_apply_kernel (ddpm.hip) up to the noise term: eps = whiten(mixed); x0_hat; clamp; sqrt(ac_prev)*x0_hat + dir*eps
+__device__ inline float ddim_apply_elem(const StepCoef &k, const SliceStats &s, float pred, float x, float x0)
+{
+#pragma clang fp contract(off)
+    const float p = (pred - s.m1) / s.s1;
+    const float c = (fmaf(-k.sa, x0, x) / k.s1m - s.m2) / s.s2;
+    const float eps = ((k.w_pred * p + k.w_cond * c) - s.m3) / s.s3;
+    float xr = fmaf(-k.d_a, eps, x) / k.d_b;
+    if (k.clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
+    return k.d_p * xr + k.d_dir * eps;
+}
+
+// the third launch of a DDIM step (ddim_sample, Model/model.py:697-716) with the draw made in registers: NOISE adds
+// d_sig * z(seed, slice_id0 + b, draw, e), one Philox quad per four consecutive elements; !NOISE (ddim_eta == 0) is
+// ddim_apply_kernel without a noise pointer -- no generator code, nothing read for it.
+template <bool NOISE>
+__global__ void __launch_bounds__(256) ddim_apply_rng_kernel(const float *__restrict__ pred, const float *__restrict__ xt,
+                                                             const float *__restrict__ x0, float *__restrict__ out, long n, StepCoef k,
+                                                             const double *__restrict__ ws, uint32_t seed_lo, uint32_t seed_hi,
+                                                             long slice_id0, long draw, int vec)
+{
+    const int b = blockIdx.y;
+    const size_t off = (size_t)b * n;
+    double t[4], u[2];
+    load_totals(ws + (size_t)b * 2 * RED_BLOCKS * 8, 4, t);
+    load_totals(ws + ((size_t)b * 2 * RED_BLOCKS + RED_BLOCKS) * 8, 2, u);
+    SliceStats s;
+    mean_std(t[0], t[1], n, s.m1, s.s1);
+    mean_std(t[2], t[3], n, s.m2, s.s2);
+    mean_std(u[0], u[1], n, s.m3, s.s3);
+    const long slice = slice_id0 + b;
+    const long nq = (n + 3) / 4;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (NOISE) randn_quad(q, slice, draw, seed_lo, seed_hi, z);
+        const long e0 = q * 4;
+        if (vec) {
+            const float4 p = *reinterpret_cast<const float4 *>(pred + off + e0);
+            const float4 x = *reinterpret_cast<const float4 *>(xt + off + e0);
+            const float4 g = *reinterpret_cast<const float4 *>(x0 + off + e0);
+            float4 v = make_float4(ddim_apply_elem(k, s, p.x, x.x, g.x), ddim_apply_elem(k, s, p.y, x.y, g.y),
+                                   ddim_apply_elem(k, s, p.z, x.z, g.z), ddim_apply_elem(k, s, p.w, x.w, g.w));
+            if (NOISE) v = make_float4(fmaf(k.d_sig, z[0], v.x), fmaf(k.d_sig, z[1], v.y), fmaf(k.d_sig, z[2], v.z), fmaf(k.d_sig, z[3], v.w));
+            *reinterpret_cast<float4 *>(out + off + e0) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (e0 + e < n) {
+                    float v = ddim_apply_elem(k, s, pred[off + e0 + e], xt[off + e0 + e], x0[off + e0 + e]);
+                    if (NOISE) v = fmaf(k.d_sig, z[e], v);
+                    out[off + e0 + e] = v;
+                }
+        }
+    }
+}
+
 struct EpiCoef { int clip, mode, want_guide, has_z; float a, b, c; };
 
 // clamp_kernel's value (mode 0: [0,1]; 1: min 0; clip == 0: a copy)
@@ -210,6 +273,32 @@ extern "C" int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float
     const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(d_x_t) && aligned16(d_x0) && aligned16(d_out);
     hipLaunchKernelGGL(step_apply_rng_kernel, dim3(quad_grid((n + 3) / 4, B), B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0,
                        d_lambda_map, d_out, n, k, ws, (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
+    IPDM_LAUNCH_CHECK();
+    return IPDM_OK;
+}
+
+extern "C" int ipdm_ddim_step_rng(const ipdm_schedule *s, int32_t t, int32_t t_prev, const float *d_eps_pred, const float *d_x_t,
+                                  const float *d_cond, uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B,
+                                  int64_t n_per_slice, double lambda_scalar, double ddim_eta, int32_t clip_denoised, void *d_ws,
+                                  size_t ws_bytes, void *stream)
+{
+    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_cond && d_out && d_ws && B > 0 && n_per_slice > 1, "ddim_step_rng: bad argument");
+    StepCoef k;
+    int rc = ddim_coef_fill(k, "ddim_step_rng", s, t, t_prev, lambda_scalar, ddim_eta, clip_denoised);
+    if (rc) return rc;
+    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("ddim_step_rng: workspace too small"); return IPDM_ERR_WORKSPACE; }
+    const long n = (long)n_per_slice;
+    hipStream_t st = (hipStream_t)stream;
+    double *ws = (double *)d_ws;
+    step_stats_launch(d_eps_pred, d_x_t, d_cond, nullptr, n, B, k, ws, st);
+    const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(d_x_t) && aligned16(d_cond) && aligned16(d_out);
+    const dim3 grid(quad_grid((n + 3) / 4, B), B);
+    if (ddim_eta == 0.0)
+        hipLaunchKernelGGL(ddim_apply_rng_kernel<false>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_cond, d_out, n, k, ws, 0u, 0u, 0L,
+                           0L, vec);
+    else
+        hipLaunchKernelGGL(ddim_apply_rng_kernel<true>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_cond, d_out, n, k, ws,
+                           (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
     IPDM_LAUNCH_CHECK();
     return IPDM_OK;
 }
@@ -435,6 +524,101 @@ extern "C" int ipdm_guided_reverse(const ipdm_schedule *s, ipdm_unet *net, const
         rc = ipdm_axpbypcz(d_iters + (size_t)(n_pass - 1) * bn, d_iters + (size_t)(n_pass - 2) * bn, nullptr,
                            d_iters + (size_t)n_pass * bn, (int64_t)bn, 0.5, 0.5, 0.0, stream);
         if (rc) return rc;
+    }
+    if (draws_used) *draws_used = draw;
+    return IPDM_OK;
+}
+
+// =============================================================================== the sparse (DDIM) sampler
+// The timestep sequences of ddim_sample (Model/model.py:668-681) by numpy's linspace rule restated in double: step =
+// (stop - start) / div, value = i * step + start, the LAST element `stop` exactly (uniform drops it, quad keeps it);
+// astype(int) truncates toward zero; ** 2 is v * v.
+extern "C" int ipdm_ddim_sequence(const char *method, int32_t timesteps, int32_t t_start, int32_t n, int32_t *seq, int32_t *prev)
+{
+#pragma clang fp contract(off)
+    IPDM_REQUIRE(method && seq && prev, "ddim_sequence: NULL method, seq or prev");
+    IPDM_REQUIRE(n > 0, "ddim_sequence: ddim_timesteps must be > 0 (got %d)", n);
+    IPDM_REQUIRE(timesteps > 0 && t_start >= 1 && t_start <= timesteps, "ddim_sequence: t_start %d outside [1, %d]", t_start, timesteps);
+    if (strcmp(method, "uniform") == 0) {            // np.linspace(t_start - 1, 0, n + 1).astype(int)[:-1]
+        const double start = (double)(t_start - 1), step = (0.0 - start) / (double)n;
+        for (int i = 0; i < n; ++i) seq[i] = (int32_t)((double)i * step + start);
+    } else if (strcmp(method, "quad") == 0) {        // (np.linspace(0, sqrt(0.8 T), n) ** 2).astype(int)
+        const double stop = sqrt((double)timesteps * .8), step = n > 1 ? stop / (double)(n - 1) : 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double v = (i == n - 1 && n > 1) ? stop : (double)i * step;
+            seq[i] = (int32_t)(v * v);
+        }
+    } else {
+        set_error("ddim_sequence: there is no ddim discretization method called \"%s\"", method);
+        return IPDM_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) prev[i] = i + 1 < n ? seq[i + 1] : 0;
+    return IPDM_OK;
+}
+
+extern "C" int ipdm_sparse_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_cond, float *d_iters, int32_t B, int32_t H,
+                                   int32_t W, int32_t t_q, const int32_t *n_steps, int32_t n_pass, const int32_t *t_seq,
+                                   const int32_t *t_prev, const double *lambda, const ipdm_sparse_args *a, int64_t *draws_used,
+                                   void *d_ws, size_t ws_bytes, void *stream)
+{
+    IPDM_REQUIRE(s && net && a, "sparse_reverse: NULL schedule, net or args");
+    IPDM_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W > 1, "sparse_reverse: bad shape %d x %d x %d", B, H, W);
+    IPDM_REQUIRE(d_cond && d_iters && d_ws && n_steps && t_seq && t_prev && lambda,
+                 "sparse_reverse: NULL condition, result, workspace, n_steps, sequence or lambda");
+    IPDM_REQUIRE(n_pass > 0, "sparse_reverse: n_pass must be > 0 (got %d)", n_pass);
+    const size_t bn = (size_t)B * H * W;
+    const bool injected = a->noise == IPDM_NOISE_INJECTED;
+    IPDM_REQUIRE(a->noise == IPDM_NOISE_COUNTER || (injected && a->d_noise),
+                 "sparse_reverse: noise must be IPDM_NOISE_COUNTER (seed, slice_id0, draw0) or IPDM_NOISE_INJECTED with d_noise");
+    IPDM_REQUIRE(!injected || (bn & 3) == 0, "sparse_reverse: injected draws need B*H*W %% 4 == 0 (ipdm_q_sample)");
+    float c[8];
+    int rc = ipdm_schedule_coeffs(s, t_q, c);      // q_sample gathers at t_q
+    if (rc) return rc;
+    long total = 0;
+    for (int it = 0; it < n_pass; ++it) {
+        IPDM_REQUIRE(n_steps[it] > 0, "sparse_reverse: pass %d has %d steps", it, n_steps[it]);
+        for (int j = 0; j < n_steps[it]; ++j, ++total) {
+            StepCoef k;
+            rc = ddim_coef_fill(k, "sparse_reverse", s, t_seq[total], t_prev[total], lambda[it], a->ddim_eta, a->clip_denoised);
+            if (rc) return rc;
+        }
+    }
+    rc = check_net("sparse_reverse", net);
+    if (rc) return rc;
+    const Carve w = carve(net, B, H, W, d_ws);
+    if (ws_bytes < w.total) { set_error("sparse_reverse: workspace too small (%zu < %zu)", ws_bytes, w.total); return IPDM_ERR_WORKSPACE; }
+
+    const long n = (long)H * W;
+    const float *nz = injected ? a->d_noise : nullptr;
+    // Model/model.py:739
+    if (nz) rc = ipdm_q_sample(s, t_q, d_cond, nz, w.xa, (int64_t)bn, stream);
+    else rc = ipdm_q_sample_rng(s, t_q, d_cond, w.xa, B, n, a->seed, a->slice_id0, a->draw0, stream);
+    if (rc) return rc;
+    const float *cur = w.xa, *guide = d_cond;
+    int64_t draw = 1;
+    for (int it = 0, q = 0; it < n_pass; ++it) {
+        float *iter = d_iters + (size_t)it * bn;
+        for (int j = 0; j < n_steps[it]; ++j, ++q, ++draw) {       // ddim_sample (:687-718): one draw per step whatever ddim_eta (:716)
+            rc = ipdm_unet_forward(net, cur, t_seq[q], w.eps, B, H, W, w.unet, w.unet_bytes, stream);
+            if (rc) return rc;
+            // the last step of a pass writes the pass's result itself; the next pass reads it from there
+            float *dst = j + 1 == n_steps[it] ? iter : (cur == w.xa ? w.xb : w.xa);
+            if (nz)
+                rc = ipdm_ddim_step(s, t_seq[q], t_prev[q], w.eps, cur, guide, nz + (size_t)draw * bn, dst, B, n, lambda[it],
+                                    a->ddim_eta, a->clip_denoised, w.step, w.step_bytes, stream);
+            else
+                rc = ipdm_ddim_step_rng(s, t_seq[q], t_prev[q], w.eps, cur, guide, a->seed, a->slice_id0, a->draw0 + draw, dst, B, n,
+                                        lambda[it], a->ddim_eta, a->clip_denoised, w.step, w.step_bytes, stream);
+            if (rc) return rc;
+            cur = dst;
+        }
+        // x carries over as it is (not re-noised, not clamped); the guide of the NEXT pass is eta*x + (1-eta)*cond0 (:757) --
+        // after the last pass the reference computes it and nobody reads it
+        if (it + 1 < n_pass) {
+            rc = ipdm_axpbypcz(iter, d_cond, nullptr, w.guide, (int64_t)bn, a->eta, 1 - a->eta, 0.0, stream);
+            if (rc) return rc;
+            guide = w.guide;
+        }
     }
     if (draws_used) *draws_used = draw;
     return IPDM_OK;

@@ -47,6 +47,14 @@ def cosine_lambda(ts, power, i):
     return out.value
 
 
+def ddim_sequence(method, timesteps, t_start, n):
+    """(seq, prev) of ddim_sample (Model/model.py:668-681) as two lists of ints, from the library (ipdm_ddim_sequence)."""
+    n = int(n)
+    seq, prev = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    call("ipdm_ddim_sequence", str(method).encode(), int(timesteps), int(t_start), n, seq, prev)
+    return list(seq[:n]), list(prev[:n])
+
+
 class NoiseSource:
     """Counter-based N(0,1) source replacing torch.randn_like (Model/model.py:440,509).
 
@@ -92,8 +100,9 @@ class GaussianDiffusion:
         call("ipdm_schedule_create", int(timesteps), float(schedule_power), C.byref(h))
         self._h = h
         self._ws = {}
-        # guided_reverse_process on the library's own loop (ipdm_guided_reverse / ipdm_reverse_pass, csrc/sampler.hip)
-        # instead of the Python one below: same bits, one C call per process (explicit t_start) or per pass (adaptive)
+        # guided_reverse_process and sparse_guided_reverse_process on the library's own loop (ipdm_guided_reverse /
+        # ipdm_reverse_pass / ipdm_sparse_reverse, csrc/sampler.hip) instead of the Python ones below: same bits, one C call per
+        # process (explicit t_start, sparse) or per pass (adaptive)
         self.native_loop = _NATIVE_REVERSE
         self._rws = {}
 
@@ -390,10 +399,14 @@ class GaussianDiffusion:
     def sparse_guided_reverse_process(self, model, condition, t_start, condition_lambda_max=0.5, condition_lambda_min=0.25,
                                       batch_size=1, ddim_timesteps=(2,), ddim_discr_method="uniform", ddim_eta=0.0,
                                       eta=0.5, clip_denoised=True, noise=None):
-        """The sparse (DDIM) sampler: same signature and return value (list of per-pass results) as the reference."""
+        """The sparse (DDIM) sampler: same signature and return value (list of per-pass results) as the reference.  Under
+        `native_loop` the library's own UNetModel runs it in one call (ipdm_sparse_reverse): same bits, same draw count."""
         import numpy as np
         noise = noise if noise is not None else NoiseSource(0)
         condition = condition.to(torch.float32).contiguous()
+        if self._sparse_native_ok(model, condition, t_start, ddim_timesteps, ddim_discr_method, noise):
+            return self._native_sparse(model, condition, t_start, condition_lambda_max, condition_lambda_min, ddim_timesteps,
+                                       ddim_discr_method, ddim_eta, eta, clip_denoised, noise)
         sample_img = self.q_sample(condition, t_start[0], noise.next_like(condition))
         condition_ = condition.clone()
         n_it = len(t_start)
@@ -411,6 +424,54 @@ class GaussianDiffusion:
             condition = nxt
             result.append(sample_img.clone())
         return result
+
+    def _sparse_native_ok(self, model, condition, t_start, ddim_timesteps, method, noise):
+        """The native sparse call serves what ipdm_sparse_reverse accepts; everything else the Python loop handles keeps the
+        Python loop, with its own behaviour and errors: an empty t_start, a pass of zero steps, an unknown method, a condition
+        that is not [B,1,H,W], injected draws whose B*H*W is no multiple of 4 (ipdm_q_sample's flat form)."""
+        n_pass = len(t_start)
+        if not (condition.dim() == 4 and condition.shape[1] == 1 and n_pass > 0 and method in ("uniform", "quad")):
+            return False
+        if len(ddim_timesteps) < n_pass or any(int(ddim_timesteps[i]) <= 0 for i in range(n_pass)):
+            return False
+        if not isinstance(noise, NoiseSource) and condition.numel() % 4 != 0:
+            return False
+        return self._use_native(model, condition, save_states=False)
+
+    def _native_sparse(self, model, condition, t_start, lambda_max, lambda_min, ddim_timesteps, method, ddim_eta, eta,
+                       clip_denoised, noise):
+        """The whole sparse process in ONE call (ipdm_sparse_reverse); the guidance ladder and the draw accounting stay here,
+        the timestep sequences come from ipdm_ddim_sequence."""
+        import numpy as np
+        step = (lambda_max - lambda_min) / len(t_start)
+        lam = np.arange(lambda_max, lambda_min - step, -step)          # Model/model.py:742-743
+        B, _, H, W = condition.shape
+        n_pass = len(t_start)
+        steps = [int(ddim_timesteps[i]) for i in range(n_pass)]
+        seq, prev = [], []
+        for t, k in zip(t_start, steps):
+            s, p = ddim_sequence(method, self.timesteps, t, k)
+            seq += s
+            prev += p
+        n_draws = 1 + sum(steps)
+        a = _lib.SparseArgs()
+        a.clip_denoised, a.ddim_eta, a.eta = (1 if clip_denoised else 0), float(ddim_eta), float(eta)
+        keep = []
+        if isinstance(noise, NoiseSource):
+            a.noise, a.seed, a.slice_id0, a.draw0 = _lib.NOISE_COUNTER, noise.seed, noise.slice_id0, noise.draw
+            noise.draw += n_draws
+        else:       # parity mode: the draws in order, stacked as _reverse_args does
+            z = torch.stack([noise.next_like(condition) for _ in range(n_draws)]).to(condition.device, torch.float32).contiguous()
+            keep.append(z)
+            a.noise, a.d_noise = _lib.NOISE_INJECTED, z.data_ptr()
+        ws = self._reverse_workspace(model, B, H, W, condition.device)
+        out = torch.empty((n_pass,) + tuple(condition.shape), dtype=torch.float32, device=condition.device)
+        used = C.c_int64()
+        _dcall(condition, "ipdm_sparse_reverse", self._h, model._ensure(), ptr(condition), ptr(out), B, H, W, int(t_start[0]),
+               (C.c_int32 * n_pass)(*steps), n_pass, (C.c_int32 * len(seq))(*seq), (C.c_int32 * len(seq))(*prev),
+               (C.c_double * n_pass)(*[float(lam[i]) for i in range(n_pass)]), C.byref(a), C.byref(used), ptr(ws), ws.numel())
+        assert used.value == n_draws
+        return [out[k] for k in range(n_pass)]
 
     def _guide_update(self, mode, eta, x, img, ldct):
         """Model/model.py:625-635."""
