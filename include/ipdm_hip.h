@@ -240,6 +240,35 @@ int ipdm_guided_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_i
                         int32_t H, int32_t W, const int32_t *t_start, int32_t n_pass, const ipdm_reverse_args *a,
                         int64_t *draws_used, void *d_ws, size_t ws_bytes, void *stream);
 
+/* Noise keyed by a TABLE of slice ids: the same generator and kernels for a sub-batch that is not a run of consecutive
+ * slices.  The reference takes its adaptive branch once per batch, from delt.max() (Model/model.py:596-613); a caller that
+ * lets every slice take its own branch (option adaptive_per_slice of the Python binding) runs the remaining passes on groups
+ * of slices such as {0, 3, 5}, and row b of such a group must draw the noise of ITS global slice.  slice_ids is a HOST array
+ * of B ids, consumed during the call (it reaches the kernel by value, in the kernel arguments): no allocation, no
+ * synchronisation, nothing to keep alive afterwards.  B above IPDM_SLICE_IDS_MAX, or a NULL table, is refused with
+ * IPDM_ERR_INVALID before any launch.  Same bits as the slice_id0 entry called once per row with slice_id0 = slice_ids[b];
+ * a table of consecutive ids gives the bits of the slice_id0 call.  IPDM_ABI_VERSION stays 5: additive entries, detected
+ * by symbol (dlsym of ipdm_reverse_pass_ids).
+ *   ipdm_randn_ids          extends ipdm_randn
+ *   ipdm_q_sample_rng_ids   extends ipdm_q_sample_rng
+ *   ipdm_ddpm_step_rng_ids  extends ipdm_ddpm_step_rng
+ *   ipdm_reverse_pass_ids   extends ipdm_reverse_pass: a->slice_id0 is not read; with injected draws (a->d_noise) the table
+ *                           is checked and otherwise unused.  ipdm_guided_reverse has no such form: a fixed schedule has
+ *                           no groups. */
+#define IPDM_SLICE_IDS_MAX 64
+int ipdm_randn_ids(float *d_out, int32_t B, int64_t n, uint64_t seed, const int64_t *slice_ids, int64_t draw,
+                   void *stream);
+int ipdm_q_sample_rng_ids(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B,
+                          int64_t n_per_slice, uint64_t seed, const int64_t *slice_ids, int64_t draw, void *stream);
+int ipdm_ddpm_step_rng_ids(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t,
+                           const float *d_x0, uint64_t seed, const int64_t *slice_ids, int64_t draw, float *d_out,
+                           int32_t B, int32_t H, int32_t W, double lambda_scalar, const float *d_lambda_map, int32_t mh,
+                           int32_t mw, int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream);
+int ipdm_reverse_pass_ids(const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
+                          const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W,
+                          int32_t ts, const ipdm_reverse_args *a, const int64_t *slice_ids, void *d_ws, size_t ws_bytes,
+                          void *stream);
+
 /* The sparse (DDIM) sampler, sample_method = "sparse" (Utils/train_test_utils.py:445-453,505-514), in the same form.
  * IPDM_ABI_VERSION stays 5; a binder detects these entries by symbol (dlsym of ipdm_sparse_reverse).
  *

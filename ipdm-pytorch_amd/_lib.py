@@ -51,6 +51,7 @@ _vp, _i32, _i64, _u64, _f32, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_u
 # name -> (restype, argtypes); restype int => status code checked by _call
 ABI_VERSION = 5          # ipdm_abi_version() of the header these prototypes were written against
 PROF_CLASSES = 8         # kernel classes of ipdm_profile_end (include/ipdm_hip.h)
+SLICE_IDS_MAX = 64       # IPDM_SLICE_IDS_MAX: entries of the id table of the _ids entry points
 
 PROTOTYPES = {
     "ipdm_last_error": (C.c_char_p, []),
@@ -100,6 +101,12 @@ PROTOTYPES = {
                                     _vp, _sz, _vp]),
     "ipdm_guided_reverse": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(ReverseArgs),
                                       C.POINTER(_i64), _vp, _sz, _vp]),
+    "ipdm_randn_ids": (C.c_int, [_vp, _i32, _i64, _u64, C.POINTER(_i64), _i64, _vp]),
+    "ipdm_q_sample_rng_ids": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _u64, C.POINTER(_i64), _i64, _vp]),
+    "ipdm_ddpm_step_rng_ids": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _u64, C.POINTER(_i64), _i64, _vp, _i32, _i32, _i32, _f64, _vp,
+                                         _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ipdm_reverse_pass_ids": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, C.POINTER(ReverseArgs),
+                                        C.POINTER(_i64), _vp, _sz, _vp]),
     "ipdm_ddim_step_rng": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _u64, _i64, _i64, _vp, _i32, _i64, _f64, _f64, _i32, _vp, _sz,
                                      _vp]),
     "ipdm_ddim_sequence": (C.c_int, [C.c_char_p, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

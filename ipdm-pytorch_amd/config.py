@@ -40,8 +40,10 @@ _FLAGS = [
     # where metric_calculate's five metrics run (no reference counterpart): "numpy" = the host functions of evaluate.py, "hip" =
     # the float64 kernels of csrc/metrics.hip, one call per scored slice.  test_batch_size (above; the reference defines the key
     # and never reads it on this path) > 1 makes test() run the denoisers on that many slices at once; in adaptive mode
-    # (t_start_proj=None) such a batch takes the branch of its maximum, as guided_reverse_process does for any batch.
-    ("metrics_backend", str, "numpy", None),
+    # (t_start_proj=None) such a batch takes the branch of its maximum, as guided_reverse_process does for any batch --
+    # unless adaptive_per_slice (no reference counterpart either): then every slice of a batch takes its own branch of the
+    # adaptive schedule, slices of one branch run together, and noise_strength is a list with one name per slice.
+    ("metrics_backend", str, "numpy", None), ("adaptive_per_slice", bool, False, None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 

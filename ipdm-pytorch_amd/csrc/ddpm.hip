@@ -105,13 +105,15 @@ extern "C" int ipdm_cosine_lambda(int32_t ts, double power, int32_t i, double *o
 
 // =============================================================================== noise
 // counter = (element/4 lo32, element/4 hi32 | draw << 8 .., slice lo, slice hi ^ draw hi): see host note.
+// IDS: row b is slice ids.v[b] of a by-value table (ipdm_randn_ids) instead of slice_id0 + b (SliceArg / slice_of, ddpm_dev.h)
+template <bool IDS>
 __global__ void __launch_bounds__(256) randn_kernel(float *__restrict__ out, long n, uint32_t seed_lo,
-                                                    uint32_t seed_hi, long slice_id0, long draw)
+                                                    uint32_t seed_hi, SliceArg<IDS> slice_id0, long draw)
 {
     const long q = (long)blockIdx.x * 256 + threadIdx.x;   // quad index inside the slice
     const long nq = (n + 3) / 4;
     if (q >= nq) return;
-    const long slice = slice_id0 + blockIdx.y;
+    const long slice = slice_of(slice_id0, blockIdx.y);
     float z[4];
     randn_quad(q, slice, draw, seed_lo, seed_hi, z);
     float *dst = out + (size_t)blockIdx.y * n + q * 4;
@@ -128,8 +130,20 @@ extern "C" int ipdm_randn(float *d_out, int32_t B, int64_t n, uint64_t seed, int
 {
     IPDM_REQUIRE(d_out && B > 0 && n > 0, "randn: bad argument");
     dim3 grid(cdiv((n + 3) / 4, 256), B);
-    hipLaunchKernelGGL(randn_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_out, (long)n, (uint32_t)seed,
+    hipLaunchKernelGGL(randn_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d_out, (long)n, (uint32_t)seed,
                        (uint32_t)(seed >> 32), (long)slice_id0, (long)draw);
+    IPDM_LAUNCH_CHECK();
+    return IPDM_OK;
+}
+
+extern "C" int ipdm_randn_ids(float *d_out, int32_t B, int64_t n, uint64_t seed, const int64_t *slice_ids, int64_t draw,
+                              void *stream)
+{
+    IPDM_REQUIRE(d_out && slice_ids && B > 0 && n > 0, "randn_ids: bad argument");
+    IPDM_REQUIRE(B <= IPDM_SLICE_IDS_MAX, "randn_ids: B = %d is above the id table's %d entries", B, IPDM_SLICE_IDS_MAX);
+    dim3 grid(cdiv((n + 3) / 4, 256), B);
+    hipLaunchKernelGGL(randn_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d_out, (long)n, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), slice_ids_fill(slice_ids, B), (long)draw);
     IPDM_LAUNCH_CHECK();
     return IPDM_OK;
 }

@@ -3,6 +3,7 @@
 // Both files must produce the same bits from them, so they live here once.
 #pragma once
 #include <cmath>
+#include <type_traits>
 #include "common.h"
 
 namespace ipdm {
@@ -41,6 +42,24 @@ __device__ inline void randn_quad(long q, long slice, long draw, uint32_t seed_l
         z[2 * h] = rad * cs;
         z[2 * h + 1] = rad * sn;
     }
+}
+
+// Which global slice row b of a launch is.  The slice_id0 form: slice_id0 + b (a batch of consecutive slices).  The table form
+// (the _ids entries, a sub-batch such as slices {0, 3, 5}): a table of IPDM_SLICE_IDS_MAX ids handed over BY VALUE in the kernel
+// arguments; b is blockIdx.y, uniform over the workgroup, so the id is one scalar load from the argument block -- no device
+// buffer, no copy, nothing to keep alive after the launch.  A kernel template <bool IDS> takes SliceArg<IDS> and asks slice_of(arg, b).
+struct SliceIds { long v[IPDM_SLICE_IDS_MAX]; };
+template <bool IDS> using SliceArg = typename std::conditional<IDS, SliceIds, long>::type;
+template <class I> __device__ inline long slice_of(long slice_id0, I b) { return slice_id0 + b; }
+template <class I> __device__ inline long slice_of(const SliceIds &ids, I b) { return ids.v[b]; }
+
+// Host side of a table launch: the caller's HOST array of B ids (consumed here, during the call) into the by-value table.
+// B above IPDM_SLICE_IDS_MAX, or a NULL array, is refused by the entry points before this is called.
+static inline SliceIds slice_ids_fill(const int64_t *slice_ids, int B)
+{
+    SliceIds t;
+    for (int b = 0; b < IPDM_SLICE_IDS_MAX; ++b) t.v[b] = b < B ? (long)slice_ids[b] : 0;
+    return t;
 }
 
 // =============================================================================== guided reverse step

@@ -50,14 +50,16 @@ __device__ inline float q_sample_elem(float sa, float s1m, float x, float z)
     return fmaf(sa, x, s1m * z);
 }
 
-// out[b, e] = sa*x[b, e] + s1m*z(seed, slice_id0 + b, draw, e); vec: n % 4 == 0 and 16-byte aligned pointers
+// out[b, e] = sa*x[b, e] + s1m*z(seed, slice_id0 + b, draw, e); vec: n % 4 == 0 and 16-byte aligned pointers.
+// IDS (the _ids entries): the slice of row b comes from a by-value id table instead (SliceArg / slice_of, ddpm_dev.h)
+template <bool IDS>
 __global__ void __launch_bounds__(256) q_sample_rng_kernel(const float *__restrict__ x, float *__restrict__ out, long n, float sa,
-                                                           float s1m, uint32_t seed_lo, uint32_t seed_hi, long slice_id0,
+                                                           float s1m, uint32_t seed_lo, uint32_t seed_hi, SliceArg<IDS> slice_id0,
                                                            long draw, int vec)
 {
     const int b = blockIdx.y;
     const size_t off = (size_t)b * n;
-    const long slice = slice_id0 + b;
+    const long slice = slice_of(slice_id0, b);
     const long nq = (n + 3) / 4;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
         float z[4];
@@ -93,12 +95,13 @@ __device__ inline float step_apply_elem(const StepCoef &k, const SliceStats &s, 
 }
 
 // pass C of a guided step with the draw made in registers: eps = whiten(mixed); x0_hat; clamp; posterior mean; + sigma*z
-// (Model/model.py:497-515).  One Philox quad per thread per four consecutive elements.
+// (Model/model.py:497-515).  One Philox quad per thread per four consecutive elements.  IDS: as q_sample_rng_kernel.
+template <bool IDS>
 __global__ void __launch_bounds__(256) step_apply_rng_kernel(const float *__restrict__ pred, const float *__restrict__ xt,
                                                              const float *__restrict__ x0, const float *__restrict__ lmap,
                                                              float *__restrict__ out, long n, StepCoef k,
                                                              const double *__restrict__ ws, uint32_t seed_lo, uint32_t seed_hi,
-                                                             long slice_id0, long draw, int vec)
+                                                             SliceArg<IDS> slice_id0, long draw, int vec)
 {
     const int b = blockIdx.y;
     const size_t off = (size_t)b * n;
@@ -110,7 +113,7 @@ __global__ void __launch_bounds__(256) step_apply_rng_kernel(const float *__rest
     mean_std(t[2], t[3], n, s.m2, s.s2);
     mean_std(u[0], u[1], n, s.m3, s.s3);
     const float *lm = k.use_map ? lmap + (size_t)b * k.mh * k.mw : nullptr;
-    const long slice = slice_id0 + b;
+    const long slice = slice_of(slice_id0, b);
     const long nq = (n + 3) / 4;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
         float z[4];
@@ -238,29 +241,58 @@ __global__ void __launch_bounds__(256) pass_epilogue_kernel(const float *__restr
 }
 
 // =============================================================================== fused ops
-extern "C" int ipdm_q_sample_rng(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B, int64_t n_per_slice,
-                                 uint64_t seed, int64_t slice_id0, int64_t draw, void *stream)
+// the slice of row b: slice_id0 + b, or ids[b] of a host table of B entries (the _ids entries)
+struct SliceSel { int64_t id0; const int64_t *ids; };
+
+static int check_ids(const char *who, const int64_t *slice_ids, int B)
 {
-    IPDM_REQUIRE(s && d_x && d_out && B > 0 && n_per_slice > 0, "q_sample_rng: bad argument");
+    IPDM_REQUIRE(slice_ids, "%s: NULL slice_ids", who);
+    IPDM_REQUIRE(B <= IPDM_SLICE_IDS_MAX, "%s: B = %d is above the id table's %d entries", who, B, IPDM_SLICE_IDS_MAX);
+    return IPDM_OK;
+}
+
+static int q_sample_rng_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B,
+                             int64_t n_per_slice, uint64_t seed, SliceSel sl, int64_t draw, void *stream)
+{
+    IPDM_REQUIRE(s && d_x && d_out && B > 0 && n_per_slice > 0, "%s: bad argument", who);
     float c[8];
     int rc = ipdm_schedule_coeffs(s, t, c);
     if (rc) return rc;
     const long n = (long)n_per_slice;
     const int vec = (n & 3) == 0 && aligned16(d_x) && aligned16(d_out);
-    hipLaunchKernelGGL(q_sample_rng_kernel, dim3(quad_grid((n + 3) / 4, B), B), dim3(256), 0, (hipStream_t)stream, d_x, d_out, n,
-                       c[0], c[1], (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
+    const dim3 grid(quad_grid((n + 3) / 4, B), B);
+    if (sl.ids)
+        hipLaunchKernelGGL(q_sample_rng_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d_x, d_out, n, c[0], c[1],
+                           (uint32_t)seed, (uint32_t)(seed >> 32), slice_ids_fill(sl.ids, B), (long)draw, vec);
+    else
+        hipLaunchKernelGGL(q_sample_rng_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d_x, d_out, n, c[0], c[1],
+                           (uint32_t)seed, (uint32_t)(seed >> 32), (long)sl.id0, (long)draw, vec);
     IPDM_LAUNCH_CHECK();
     return IPDM_OK;
 }
 
-extern "C" int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
-                                  uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B, int32_t H, int32_t W,
-                                  double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw, int32_t clip_denoised,
-                                  void *d_ws, size_t ws_bytes, void *stream)
+extern "C" int ipdm_q_sample_rng(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B, int64_t n_per_slice,
+                                 uint64_t seed, int64_t slice_id0, int64_t draw, void *stream)
 {
-    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_x0 && d_out && d_ws && B > 0 && H > 0 && W > 0, "ddpm_step_rng: bad argument");
-    IPDM_REQUIRE(!d_lambda_map || (mh > 0 && mw > 0), "ddpm_step_rng: lambda map without dims");
-    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("ddpm_step_rng: workspace too small"); return IPDM_ERR_WORKSPACE; }
+    return q_sample_rng_impl("q_sample_rng", s, t, d_x, d_out, B, n_per_slice, seed, SliceSel{slice_id0, nullptr}, draw, stream);
+}
+
+extern "C" int ipdm_q_sample_rng_ids(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B,
+                                     int64_t n_per_slice, uint64_t seed, const int64_t *slice_ids, int64_t draw, void *stream)
+{
+    int rc = check_ids("q_sample_rng_ids", slice_ids, B);
+    if (rc) return rc;
+    return q_sample_rng_impl("q_sample_rng_ids", s, t, d_x, d_out, B, n_per_slice, seed, SliceSel{0, slice_ids}, draw, stream);
+}
+
+static int ddpm_step_rng_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t,
+                              const float *d_x0, uint64_t seed, SliceSel sl, int64_t draw, float *d_out, int32_t B, int32_t H,
+                              int32_t W, double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw,
+                              int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream)
+{
+    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_x0 && d_out && d_ws && B > 0 && H > 0 && W > 0, "%s: bad argument", who);
+    IPDM_REQUIRE(!d_lambda_map || (mh > 0 && mw > 0), "%s: lambda map without dims", who);
+    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("%s: workspace too small", who); return IPDM_ERR_WORKSPACE; }
     float c[8];
     int rc = ipdm_schedule_coeffs(s, t, c);
     if (rc) return rc;
@@ -271,10 +303,35 @@ extern "C" int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float
     double *ws = (double *)d_ws;
     step_stats_launch(d_eps_pred, d_x_t, d_x0, d_lambda_map, n, B, k, ws, st);
     const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(d_x_t) && aligned16(d_x0) && aligned16(d_out);
-    hipLaunchKernelGGL(step_apply_rng_kernel, dim3(quad_grid((n + 3) / 4, B), B), dim3(256), 0, st, d_eps_pred, d_x_t, d_x0,
-                       d_lambda_map, d_out, n, k, ws, (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
+    const dim3 grid(quad_grid((n + 3) / 4, B), B);
+    if (sl.ids)
+        hipLaunchKernelGGL(step_apply_rng_kernel<true>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_lambda_map, d_out, n, k, ws,
+                           (uint32_t)seed, (uint32_t)(seed >> 32), slice_ids_fill(sl.ids, B), (long)draw, vec);
+    else
+        hipLaunchKernelGGL(step_apply_rng_kernel<false>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_lambda_map, d_out, n, k, ws,
+                           (uint32_t)seed, (uint32_t)(seed >> 32), (long)sl.id0, (long)draw, vec);
     IPDM_LAUNCH_CHECK();
     return IPDM_OK;
+}
+
+extern "C" int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
+                                  uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B, int32_t H, int32_t W,
+                                  double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw, int32_t clip_denoised,
+                                  void *d_ws, size_t ws_bytes, void *stream)
+{
+    return ddpm_step_rng_impl("ddpm_step_rng", s, t, d_eps_pred, d_x_t, d_x0, seed, SliceSel{slice_id0, nullptr}, draw, d_out, B, H, W,
+                              lambda_scalar, d_lambda_map, mh, mw, clip_denoised, d_ws, ws_bytes, stream);
+}
+
+extern "C" int ipdm_ddpm_step_rng_ids(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t,
+                                      const float *d_x0, uint64_t seed, const int64_t *slice_ids, int64_t draw, float *d_out,
+                                      int32_t B, int32_t H, int32_t W, double lambda_scalar, const float *d_lambda_map, int32_t mh,
+                                      int32_t mw, int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = check_ids("ddpm_step_rng_ids", slice_ids, B);
+    if (rc) return rc;
+    return ddpm_step_rng_impl("ddpm_step_rng_ids", s, t, d_eps_pred, d_x_t, d_x0, seed, SliceSel{0, slice_ids}, draw, d_out, B, H, W,
+                              lambda_scalar, d_lambda_map, mh, mw, clip_denoised, d_ws, ws_bytes, stream);
 }
 
 extern "C" int ipdm_ddim_step_rng(const ipdm_schedule *s, int32_t t, int32_t t_prev, const float *d_eps_pred, const float *d_x_t,
@@ -350,6 +407,7 @@ struct PassIn {
     int guidance;                        // 0 constant, 1 cosine curve, 2 map
     const float *noise;                  // injected draws of this pass, or NULL
     int64_t draw;                        // first draw number of this pass
+    const int64_t *slice_ids;            // or NULL: row b is slice a->slice_id0 + b (host table of B ids: ipdm_reverse_pass_ids)
 };
 
 // host-side checks shared by both entries: nothing here touches a device
@@ -385,9 +443,10 @@ int run_pass(const ipdm_schedule *s, ipdm_unet *net, const PassIn &p, int B, int
     const size_t bn = (size_t)B * n;
     int rc;
     const float *nz = p.noise;
+    const SliceSel sl = {a->slice_id0, p.slice_ids};
     // Model/model.py:537-541
     if (nz) rc = ipdm_q_sample(s, ts, p.x_in, nz, w.xa, (int64_t)bn, stream);
-    else rc = ipdm_q_sample_rng(s, ts, p.x_in, w.xa, B, n, a->seed, a->slice_id0, p.draw, stream);
+    else rc = q_sample_rng_impl("q_sample_rng", s, ts, p.x_in, w.xa, B, n, a->seed, sl, p.draw, stream);
     if (rc) return rc;
     const bool epilogue = a->clip || p.guide_out;     // else the last step writes the pass's result itself
     float *cur = w.xa, *nxt = w.xb;
@@ -411,8 +470,8 @@ int run_pass(const ipdm_schedule *s, ipdm_unet *net, const PassIn &p, int B, int
             rc = ipdm_ddpm_step(s, i, w.eps, cur, p.guide, nz + (size_t)k * bn, dst, B, H, W, lam, lmap, p.mh, p.mw, a->clip, w.step,
                                 w.step_bytes, stream);
         else
-            rc = ipdm_ddpm_step_rng(s, i, w.eps, cur, p.guide, a->seed, a->slice_id0, p.draw + k, dst, B, H, W, lam, lmap, p.mh, p.mw,
-                                    a->clip, w.step, w.step_bytes, stream);
+            rc = ddpm_step_rng_impl("ddpm_step_rng", s, i, w.eps, cur, p.guide, a->seed, sl, p.draw + k, dst, B, H, W, lam, lmap, p.mh,
+                                    p.mw, a->clip, w.step, w.step_bytes, stream);
         if (rc) return rc;
         nxt = cur;
         cur = dst;
@@ -440,27 +499,46 @@ extern "C" size_t ipdm_reverse_workspace_bytes(ipdm_unet *net, int32_t B, int32_
     return carve(net, B, H, W, nullptr).total;
 }
 
-extern "C" int ipdm_reverse_pass(const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
-                                 const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W,
-                                 int32_t ts, const ipdm_reverse_args *a, void *d_ws, size_t ws_bytes, void *stream)
+static int reverse_pass_impl(const char *who, const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
+                             const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W, int32_t ts,
+                             const ipdm_reverse_args *a, const int64_t *slice_ids, void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = check_common("reverse_pass", s, net, B, H, W, a);
+    int rc = check_common(who, s, net, B, H, W, a);
     if (rc) return rc;
-    IPDM_REQUIRE(d_x_in && d_guide && d_iter && d_ws, "reverse_pass: NULL image, guide, result or workspace");
-    rc = check_ts("reverse_pass", s, ts);
+    IPDM_REQUIRE(d_x_in && d_guide && d_iter && d_ws, "%s: NULL image, guide, result or workspace", who);
+    rc = check_ts(who, s, ts);
     if (rc) return rc;
     if (a->guidance == 2)
-        IPDM_REQUIRE(d_Lambda && mh > 0 && mw > 0 && mh <= H && mw <= W, "reverse_pass: guidance 2 needs a map [B, mh <= H, mw <= W]");
-    rc = check_net("reverse_pass", net);
+        IPDM_REQUIRE(d_Lambda && mh > 0 && mw > 0 && mh <= H && mw <= W, "%s: guidance 2 needs a map [B, mh <= H, mw <= W]", who);
+    rc = check_net(who, net);
     if (rc) return rc;
     const Carve w = carve(net, B, H, W, d_ws);
-    if (ws_bytes < w.total) { set_error("reverse_pass: workspace too small (%zu < %zu)", ws_bytes, w.total); return IPDM_ERR_WORKSPACE; }
+    if (ws_bytes < w.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total); return IPDM_ERR_WORKSPACE; }
     PassIn p = {};
     p.x_in = d_x_in; p.guide = d_guide; p.Lam = a->guidance == 2 ? d_Lambda : nullptr;
     p.mh = a->guidance == 2 ? mh : 0; p.mw = a->guidance == 2 ? mw : 0;
     p.iter = d_iter; p.guide_out = nullptr; p.img = nullptr; p.ldct = nullptr;
-    p.guidance = a->guidance; p.noise = a->d_noise; p.draw = a->draw0;
+    p.guidance = a->guidance; p.noise = a->d_noise; p.draw = a->draw0; p.slice_ids = slice_ids;
     return run_pass(s, net, p, B, H, W, ts, a, w, stream);
+}
+
+extern "C" int ipdm_reverse_pass(const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
+                                 const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W,
+                                 int32_t ts, const ipdm_reverse_args *a, void *d_ws, size_t ws_bytes, void *stream)
+{
+    return reverse_pass_impl("reverse_pass", s, net, d_x_in, d_guide, d_Lambda, mh, mw, d_iter, B, H, W, ts, a, nullptr, d_ws, ws_bytes,
+                             stream);
+}
+
+extern "C" int ipdm_reverse_pass_ids(const ipdm_schedule *s, ipdm_unet *net, const float *d_x_in, const float *d_guide,
+                                     const float *d_Lambda, int32_t mh, int32_t mw, float *d_iter, int32_t B, int32_t H, int32_t W,
+                                     int32_t ts, const ipdm_reverse_args *a, const int64_t *slice_ids, void *d_ws, size_t ws_bytes,
+                                     void *stream)
+{
+    int rc = check_ids("reverse_pass_ids", slice_ids, B);
+    if (rc) return rc;
+    return reverse_pass_impl("reverse_pass_ids", s, net, d_x_in, d_guide, d_Lambda, mh, mw, d_iter, B, H, W, ts, a, slice_ids, d_ws,
+                             ws_bytes, stream);
 }
 
 extern "C" int ipdm_guided_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_img, float *d_iters, int32_t B, int32_t H,

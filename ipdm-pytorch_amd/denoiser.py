@@ -230,11 +230,19 @@ class progressive_domain_denoiser(EvaluationMixin):
             model=self.proj_model, img=x.to(self.proj_device, torch.float32), t_start=o.t_start_proj, clip=o.clip_proj,
             lambda_ratio=o.lambda_ratio_proj, eta=o.eta_proj, mode="proj", constant_guidance=o.constant_guidance_proj,
             kernel_size_proj=o.kernel_size_proj, amplitude_proj=o.amplitude_proj, only_convertor=o.benchmark_test,
-            normal=o.normal, transformer=self.trans_ldproj, noise=self._noise(), rank_max=self._rank_max())
+            normal=o.normal, transformer=self.trans_ldproj, noise=self._noise(), rank_max=self._rank_max(),
+            adaptive_per_slice=self._per_slice())
+
+    def _per_slice(self):
+        """Option adaptive_per_slice: with t_start_proj / t_start_img = None every slice of a batch takes its own branch of
+        the adaptive schedule (diffusion.guided_reverse_process); noise_strength is then a list of B names, stored, returned
+        and handed to the image stage as such.  The decision needs no other rank's slices: the rank_max hook is not called."""
+        return bool(getattr(self.opt, "adaptive_per_slice", False))
 
     def _rank_max(self):
         """Adaptive pass schedule (t_start_proj=None) under slice sharding: the branch is taken on the maximum over
-        ALL ranks' slices, as the reference takes it over its whole batch (Model/model.py:596-609)."""
+        ALL ranks' slices, as the reference takes it over its whole batch (Model/model.py:596-609).  Under option
+        adaptive_per_slice every slice decides for itself and the hook is never called."""
         import torch.distributed as td
         if not (td.is_available() and td.is_initialized()
                 and (td.get_world_size() > 1 or getattr(self, "force_collectives", False))):
@@ -250,7 +258,8 @@ class progressive_domain_denoiser(EvaluationMixin):
         common = dict(model=self.img_model, clip=o.clip_img, lambda_ratio=o.lambda_ratio_img,
                       save_states=o.save_states_img, noise_strength=noise_strength, ldct=xd, mode="img",
                       kernel_size_img=o.kernel_size_img, amplitude_img=o.amplitude_img,
-                      only_convertor=o.benchmark_test, normal=o.normal, transformer=self.trans_ldimg, noise=self._noise())
+                      only_convertor=o.benchmark_test, normal=o.normal, transformer=self.trans_ldimg, noise=self._noise(),
+                      adaptive_per_slice=self._per_slice())
         if o.sample_method_img == "sparse":        # Utils/train_test_utils.py:505-514
             result = self.img_gaussian_diffusion.sparse_guided_reverse_process(
                 model=self.img_model, condition=xd, t_start=o.t_start_img, condition_lambda_max=0.5, condition_lambda_min=0.3,

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import call, lib, ptr
+from .adaptive import MAX_DRAWS, adaptive_groups, branch_names
 
 # np.polyfit coefficients of the guidance curves (Utils/train_test_utils.py:842-865), highest power
 # first; values as produced by the reference (tests/golden/misc.npz holds the same numbers).
@@ -60,25 +61,65 @@ class NoiseSource:
 
     Draw k of global slice s is a pure function of (seed, s, k): the same slice gets the same noise
     whatever the batch composition or the number of GPUs (shard invariance).  `slice_id0` is the
-    global index of the first slice of the local batch."""
+    global index of the first slice of the local batch; `slice_ids`, when given, is the list of the batch rows' global
+    indices instead (a sub-batch that is not a run of consecutive slices: ipdm_randn_ids and the other _ids entries)."""
 
-    def __init__(self, seed=0, slice_id0=0):
-        self.seed, self.slice_id0, self.draw = int(seed), int(slice_id0), 0
+    def __init__(self, seed=0, slice_id0=0, slice_ids=None, draw=0):
+        self.seed, self.slice_id0, self.draw = int(seed), int(slice_id0), int(draw)
+        self.slice_ids = None if slice_ids is None else [int(i) for i in slice_ids]
 
     def next_like(self, x):
         out = torch.empty_like(x)
         B = x.shape[0]
-        _dcall(out, "ipdm_randn", ptr(out), B, x.numel() // B, self.seed, self.slice_id0, self.draw)
+        if self.slice_ids is None:
+            _dcall(out, "ipdm_randn", ptr(out), B, x.numel() // B, self.seed, self.slice_id0, self.draw)
+        else:
+            _dcall(out, "ipdm_randn_ids", ptr(out), B, x.numel() // B, self.seed, self.ids_array(B), self.draw)
         self.draw += 1
         return out
 
+    def ids_array(self, B):
+        """The id table of a batch of B rows as the _ids entries take it (a host array, consumed during the call)."""
+        if len(self.slice_ids) != B:
+            raise ValueError("noise source for %d slices asked for a batch of %d" % (len(self.slice_ids), B))
+        return (C.c_int64 * B)(*self.slice_ids)
+
+    def for_slices(self, slice_ids, draw):
+        """A source of the same seed for the global slices `slice_ids`, whose next draw is number `draw`.  Consecutive ids
+        give a plain slice_id0 source (the same kernels as any batch), others a table source."""
+        ids = [int(i) for i in slice_ids]
+        if ids == list(range(ids[0], ids[0] + len(ids))):
+            return NoiseSource(self.seed, ids[0], draw=draw)
+        return NoiseSource(self.seed, ids[0], slice_ids=ids, draw=draw)
+
+    def child(self, rows, draw):
+        """for_slices for the batch rows `rows` of THIS source's batch."""
+        return self.for_slices([self.slice_ids[r] if self.slice_ids is not None else self.slice_id0 + r for r in rows], draw)
+
+    def skip_to(self, draw):
+        self.draw = int(draw)
+
 
 class InjectedNoise:
-    """Parity mode: hands out caller-supplied draws (an iterable of tensors shaped like x) in order."""
+    """Parity mode: hands out caller-supplied draws (an iterable of tensors shaped like x) in order.  Built from a list (or
+    tuple) it can also serve a group of batch rows from a given draw on (`child`: adaptive_per_slice)."""
 
     def __init__(self, draws):
+        self._list = draws if isinstance(draws, (list, tuple)) else None
         self._it = iter(draws)
         self.draw = 0
+
+    def child(self, rows, draw):
+        """A source whose k-th draw is draw number `draw` + k of this one, restricted to the batch rows `rows`."""
+        if self._list is None:
+            raise TypeError("InjectedNoise.child needs a source built from a list of draws")
+        rows = list(rows)
+        return InjectedNoise(d[rows] for d in self._list[int(draw):])
+
+    def skip_to(self, draw):
+        while self.draw < int(draw):
+            next(self._it, None)
+            self.draw += 1
 
     def next_like(self, x):
         z = next(self._it).to(x.device, torch.float32).contiguous()
@@ -255,16 +296,99 @@ class GaussianDiffusion:
         out = torch.empty_like(x)
         lm = Lam.contiguous() if guidance == 2 else None
         mh, mw = (lm.shape[-2], lm.shape[-1]) if lm is not None else (0, 0)
-        _dcall(x, "ipdm_reverse_pass", self._h, model._ensure(), ptr(x), ptr(guide), ptr(lm), mh, mw, ptr(out), B, H, W, int(ts),
-               C.byref(a), ptr(ws), ws.numel())
+        if getattr(noise, "slice_ids", None) is not None:       # a group of slices that is no run of consecutive ones
+            _dcall(x, "ipdm_reverse_pass_ids", self._h, model._ensure(), ptr(x), ptr(guide), ptr(lm), mh, mw, ptr(out), B, H, W,
+                   int(ts), C.byref(a), noise.ids_array(B), ptr(ws), ws.numel())
+        else:
+            _dcall(x, "ipdm_reverse_pass", self._h, model._ensure(), ptr(x), ptr(guide), ptr(lm), mh, mw, ptr(out), B, H, W, int(ts),
+                   C.byref(a), ptr(ws), ws.numel())
         return out
+
+    def _one_pass(self, native, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs,
+                  reverse_states):
+        """One outer pass (Model/model.py:537-573): q_sample at ts, ts guided steps, the clamp -- one native call, or the Python
+        loop over the op-level entries.  `reverse_states`: a list that receives every step's state (save_states), or None."""
+        if native:
+            return self._native_pass(model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs)
+        x = self.q_sample(x, ts, noise.next_like(x))
+        for i in reversed(range(ts)):
+            if constant_guidance is None:
+                if it == 0:
+                    l_s = cosine_lambda(ts, lambda_ratio, i)
+                else:
+                    l_s = self.lambda_ratio(Lam, i, ts)
+            else:
+                l_s = constant_guidance
+            x = self.p_sample_condition(model, x, guide, i, clip_denoised=clip, lambda_=l_s, noise=noise.next_like(x))
+            if reverse_states is not None:
+                reverse_states.append(x.detach().cpu().numpy())
+        if clip:
+            y = torch.empty_like(x)
+            _dcall(x, "ipdm_clamp", ptr(x), ptr(y), x.numel(), 0 if mode == "img" else 1)
+            x = y
+        return x
+
+    def _grouped_passes(self, native, model, img, Lam, ldct, groups, clip, lambda_ratio, mode, noise, draw0, kwargs):
+        """adaptive_per_slice with more than one branch in the batch: every group of slices (adaptive.adaptive_groups) runs the
+        three passes after the probe as a sub-batch of its own -- its rows of img / Lam / ldct (a view for a run of consecutive
+        rows, index_select otherwise), its own t_list and eta, and a child noise source that continues every slice's draws at
+        `draw0` -- and its iterates go into full-batch tensors.  Returns the reference's list: three passes and their average."""
+        if not hasattr(noise, "child"):
+            raise TypeError("adaptive_per_slice needs a noise source that can serve a group of slices (NoiseSource, or "
+                            "InjectedNoise built from a list), not %s" % type(noise).__name__)
+        normal = bool(kwargs.get("normal"))
+        ld = None if (ldct is None or mode != "img") else ldct.to(img.device, torch.float32).contiguous()
+        outs = [torch.empty_like(img) for _ in range(4)]
+        for g in groups:
+            rows = list(g.slices)
+            lo, hi = rows[0], rows[-1] + 1
+            idx = None if rows == list(range(lo, hi)) else torch.tensor(rows, dtype=torch.int64, device=img.device)
+
+            def take(t):
+                if idx is not None:
+                    return t.index_select(0, idx)
+                v = t[lo:hi]                 # a pointer offset; copied only where the offset breaks the 16-byte accesses
+                return v if v.data_ptr() % 16 == 0 else v.clone()
+            img_g, Lam_g = take(img), take(Lam)
+            ld_g = None if ld is None else take(ld)
+            gnoise = noise.child(rows, draw0)
+            tr = kwargs.get("transformer")
+            if normal:
+                from .normalize import SliceTransformers, yeo_johnson_inverse_transform
+                if isinstance(tr, SliceTransformers):
+                    tr = SliceTransformers([tr[r] for r in rows])
+            x, guide, iters = img_g, img_g, []       # after the probe pass: x is reset to img, the guide is still img (:619-622)
+            for k, ts in enumerate(g.t_list):
+                x = self._one_pass(native, model, x, guide, Lam_g, ts, 1 + k, clip, lambda_ratio, g.eta, mode, None, gnoise, kwargs,
+                                   None)
+                iters.append(yeo_johnson_inverse_transform(x.contiguous(), tr).to(torch.float32) if normal else x)
+                if k + 1 < len(g.t_list):
+                    guide = self._guide_update(mode, g.eta, x, img_g, ld_g)
+            avg = torch.empty_like(iters[-1])
+            _dcall(avg, "ipdm_axpbypcz", ptr(iters[-1]), ptr(iters[-2]), None, ptr(avg), avg.numel(), 0.5, 0.5, 0.0)
+            iters.append(avg)
+            for k, r in enumerate(iters):
+                if idx is None:
+                    outs[k][lo:hi].copy_(r)
+                else:
+                    outs[k].index_copy_(0, idx, r)
+        return outs
 
     # ---- Model/model.py:517-642
     @torch.no_grad()
     def guided_reverse_process(self, model, img, t_start=None, clip=True, lambda_ratio=1, eta=0.5, save_states=False,
                                mode="img", constant_guidance=None, noise=None, **kwargs):
         """Same signature and return value as the reference: (list of iterates, reverse states,
-        noise_strength).  Extra keyword: `noise` = NoiseSource / InjectedNoise (default: NoiseSource(0))."""
+        noise_strength).  Extra keyword: `noise` = NoiseSource / InjectedNoise (default: NoiseSource(0)).
+
+        Extra keyword `adaptive_per_slice` (default False; read only when t_start is None): after the probe pass every slice
+        takes its OWN branch of the adaptive schedule instead of the batch's (adaptive.py): proj mode from its own emax (one
+        device-to-host copy of B floats; `rank_max` is not called), img mode from `noise_strength`, which may then be a
+        sequence of B entries.  Slices of one branch run the remaining passes together, so slice b of the result is what a
+        call on that slice alone returns, bit for bit; `noise_strength` comes back as a list of B branch names.  The noise
+        source is left at the probe's draws + the LONGEST branch's count (adaptive.MAX_DRAWS), whatever branches were taken,
+        so that a following process draws the same numbers for a slice alone and in any batch.  save_states=True cannot be
+        reported in the reference's list shape (the groups run different numbers of steps) and is refused with the option."""
         if kwargs.get("only_convertor"):
             return [img], None, None
         normal = bool(kwargs.get("normal"))        # iterates are reported through the inverse power transform (:616-617)
@@ -278,8 +402,13 @@ class GaussianDiffusion:
         adaptive = t_start is None
         t_list = [20] if adaptive else list(t_start)
         noise_strength = None
+        per_slice = adaptive and bool(kwargs.get("adaptive_per_slice"))
+        if per_slice and save_states:
+            raise ValueError("save_states=True is not available with adaptive_per_slice: the slices of a batch run different "
+                             "numbers of steps, which the reference's flat list of states cannot hold")
+        draw_end = None         # per_slice: where the noise source is left (the probe's draws + the longest branch's)
         native = self._use_native(model, img, save_states)
-        if native and not adaptive and t_list:
+        if native and not adaptive and t_list and getattr(noise, "slice_ids", None) is None:
             raw = self._native_process(model, img, t_list, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs)
             if not normal:
                 return raw, reverse_states, noise_strength
@@ -296,31 +425,15 @@ class GaussianDiffusion:
         ldct = kwargs.get("ldct")
         while t_list:
             ts = t_list.pop(0)
-            if native:      # the adaptive schedule: one call per pass, the between-pass decisions below stay here
-                x = self._native_pass(model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise,
-                                      kwargs)
-            else:
-                x = self.q_sample(x, ts, noise.next_like(x))
-                for i in reversed(range(ts)):
-                    if constant_guidance is None:
-                        if it == 0:
-                            l_s = cosine_lambda(ts, lambda_ratio, i)
-                        else:
-                            l_s = self.lambda_ratio(Lam, i, ts)
-                    else:
-                        l_s = constant_guidance
-                    x = self.p_sample_condition(model, x, guide, i, clip_denoised=clip, lambda_=l_s,
-                                                noise=noise.next_like(x))
-                    if save_states:
-                        reverse_states.append(x.detach().cpu().numpy())
-                if clip:
-                    y = torch.empty_like(x)
-                    _dcall(x, "ipdm_clamp", ptr(x), ptr(y), n, 0 if mode == "img" else 1)
-                    x = y
+            # (native: the adaptive schedule takes one call per pass, the between-pass decisions below stay here)
+            x = self._one_pass(native, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs,
+                               reverse_states if save_states else None)
             if it == 0 and constant_guidance is None:
                 if mode == "img":
                     Lam, emax = self.guidance_map(x, img, "img", kwargs["kernel_size_img"], kwargs["amplitude_img"])
-                    if adaptive:
+                    if per_slice:
+                        groups = adaptive_groups("img", noise_strength=kwargs.get("noise_strength"), batch=B)
+                    elif adaptive:
                         ns = kwargs.get("noise_strength")
                         if ns == "high":
                             t_list, eta = [15, 15, 15], 0.6
@@ -330,7 +443,9 @@ class GaussianDiffusion:
                             t_list, eta = [10, 10, 10], 0.5
                 else:
                     Lam, emax = self.guidance_map(x, img, "proj", kwargs["kernel_size_proj"], kwargs["amplitude_proj"])
-                    if adaptive:
+                    if per_slice:       # ONE device->host copy of B floats; every slice decides for itself, no rank_max
+                        groups = adaptive_groups("proj", emax=emax.cpu().tolist(), batch=B)
+                    elif adaptive:
                         m = float(emax.max().item())       # the one device->host scalar of adaptive mode
                         # the reference decides on the whole batch's maximum (delt.max(), :596-609); when the batch is
                         # sharded over ranks the decision must not depend on the sharding: `rank_max` (a scalar MAX
@@ -343,6 +458,19 @@ class GaussianDiffusion:
                             t_list, noise_strength, eta = [20, 18, 15], "mid", 0.5
                         else:
                             t_list, noise_strength, eta = [15, 15, 15], "low", 0.5
+                if per_slice:
+                    if not hasattr(noise, "skip_to"):
+                        raise TypeError("adaptive_per_slice needs a noise source with skip_to (NoiseSource, InjectedNoise), not "
+                                        "%s" % type(noise).__name__)
+                    noise_strength = branch_names(groups)
+                    draw_end = noise.draw + MAX_DRAWS[mode]
+                    if len(groups) == 1:        # one branch for all: the batch goes on as it is, launch for launch
+                        t_list, eta = list(groups[0].t_list), groups[0].eta
+                    else:
+                        outs = self._grouped_passes(native, model, img, Lam, ldct, groups, clip, lambda_ratio, mode, noise,
+                                                    noise.draw, kwargs)
+                        noise.skip_to(draw_end)
+                        return outs, reverse_states, noise_strength
             if normal:
                 from .normalize import yeo_johnson_inverse_transform
                 iters_out.append(yeo_johnson_inverse_transform(x.contiguous(), kwargs["transformer"]).to(torch.float32))
@@ -360,6 +488,8 @@ class GaussianDiffusion:
             avg = torch.empty_like(iters_out[-1])
             _dcall(avg, "ipdm_axpbypcz", ptr(iters_out[-1]), ptr(iters_out[-2]), None, ptr(avg), n, 0.5, 0.5, 0.0)
             iters_out.append(avg)
+        if draw_end is not None:
+            noise.skip_to(draw_end)
         if adaptive:
             return iters_out[1:], reverse_states, noise_strength
         return iters_out, reverse_states, noise_strength
@@ -435,6 +565,8 @@ class GaussianDiffusion:
         if len(ddim_timesteps) < n_pass or any(int(ddim_timesteps[i]) <= 0 for i in range(n_pass)):
             return False
         if not isinstance(noise, NoiseSource) and condition.numel() % 4 != 0:
+            return False
+        if getattr(noise, "slice_ids", None) is not None:       # ipdm_sparse_reverse has no id-table form
             return False
         return self._use_native(model, condition, save_states=False)
 

@@ -627,7 +627,8 @@ class EvaluationMixin:
         writes.  Slice b of a batch draws its noise under slice id slice_id0 + b, as the pipeline does for any batch, while
         the B = 1 loop gives every sample slice_id0: a batched run is a different, equally valid realisation of the sampler's
         noise, not the bits of the unbatched run.  In adaptive mode (t_start_proj=None) a batch takes the branch of its
-        maximum, as guided_reverse_process does for any batch."""
+        maximum, as guided_reverse_process does for any batch -- unless option adaptive_per_slice is on (the denoisers read
+        it themselves): then every slice of the batch runs the schedule it would run alone."""
         o = self.opt
         ds = self.test_dataset
         for lo in range(0, len(ids), B):
