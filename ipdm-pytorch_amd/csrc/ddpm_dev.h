@@ -1,10 +1,19 @@
-// Device helpers shared by ddpm.hip (the op-level entry points) and sampler.hip (the kernels of the native reverse loop):
-// counter-based noise, the coefficient block of a guided reverse step, the per-slice statistics' fixed-order totals.
-// Both files must produce the same bits from them, so they live here once.
+// What ddpm.hip (schedule, noise, guidance maps), step.hip (q_sample and the guided steps) and sampler.hip (the native loops) share:
+// the schedule's tables, counter-based noise, the coefficient block of a guided step, the per-slice statistics' fixed-order totals,
+// and the per-element arithmetic of q_sample, the dense step and the DDIM step.  That arithmetic is defined HERE ONCE, for every
+// kernel and for every source of the N(0,1) draw, with each rounding written out (`#pragma clang fp contract(off)`, explicit fma):
+// the bits of a step do not depend on what a compiler chooses to contract or to pack.
 #pragma once
 #include <cmath>
 #include <type_traits>
+#include <vector>
 #include "common.h"
+
+// the schedule's float64 tables (ipdm_schedule_create, ddpm.hip)
+struct ipdm_schedule {
+    int T;
+    std::vector<double> sqrt_ac, sqrt_1m_ac, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, var, ac;
+};
 
 namespace ipdm {
 
@@ -101,8 +110,9 @@ __device__ inline void load_totals(const double *__restrict__ partials, int nval
 
 __device__ inline void mean_std(double sum, double sumsq, long n, float &mean, float &sd)
 {
+#pragma clang fp contract(off)
     double m = sum / (double)n;
-    double var = (sumsq - (double)n * m * m) / (double)(n - 1);   // unbiased (torch.std)
+    double var = fma(-m, (double)n * m, sumsq) / (double)(n - 1);   // unbiased (torch.std)
     mean = (float)m;
     sd = (float)sqrt(var > 0 ? var : 0.0);
 }
@@ -126,13 +136,114 @@ static inline void step_coef_fill(StepCoef &k, const float c[8], int t, double l
     k.d_a = k.d_b = k.d_p = k.d_dir = k.d_sig = 0.0f;
 }
 
-// the two statistics passes of a guided step (step_stats1/2_kernel, ddpm.hip) on `st`: their partial-sum layout and reduction
-// order define the bits of a step, so sampler.hip launches them as they are
-void step_stats_launch(const float *d_eps_pred, const float *d_x_t, const float *d_x0, const float *d_lambda_map, long n, int B,
-                       const StepCoef &k, double *ws, hipStream_t st);
+// whitening statistics of one slice: (mean, std) of eps_pred, of cond, of their mix
+struct SliceStats { float m1, s1, m2, s2, m3, s3; };
 
-// Host side of a DDIM step (ddpm.hip, where the schedule's tables are): the coefficient block of ipdm_ddim_step /
-// ipdm_ddim_step_rng for the update t -> t_prev.  Refuses a timestep outside the schedule (status code, error text under `who`).
+// The prologue of every kernel that whitens: slice b's statistics from the partial sums of the statistics passes, the same
+// value in every thread.  mixed = false (the second statistics pass itself): the mix's sums do not exist yet, m3 / s3 stay 0 / 1.
+__device__ inline SliceStats load_slice_stats(const double *__restrict__ ws, int b, long n, bool mixed = true)
+{
+    SliceStats s = {0.0f, 1.0f, 0.0f, 1.0f, 0.0f, 1.0f};
+    double t[4];
+    load_totals(ws + (size_t)b * 2 * RED_BLOCKS * 8, 4, t);
+    mean_std(t[0], t[1], n, s.m1, s.s1);
+    mean_std(t[2], t[3], n, s.m2, s.s2);
+    if (mixed) {
+        load_totals(ws + ((size_t)b * 2 * RED_BLOCKS + RED_BLOCKS) * 8, 2, t);
+        mean_std(t[0], t[1], n, s.m3, s.s3);
+    }
+    return s;
+}
+
+// ------------------------------------------------------------------------------- per-element arithmetic
+// q_sample (Model/model.py:438-445): sa*x + s1m*z, the second product rounded
+__device__ inline float q_sample_elem(float sa, float s1m, float x, float z)
+{
+#pragma clang fp contract(off)
+    return fmaf(sa, x, s1m * z);
+}
+
+// cond = (x_t - sa*x0) / s1m (:447-450), the product fused into the subtraction
+__device__ inline float cond_elem(const StepCoef &k, float x, float x0)
+{
+#pragma clang fp contract(off)
+    return fmaf(-k.sa, x0, x) / k.s1m;
+}
+
+// guidance weights of element i of a slice: the scalar pair, or (1 - lambda, lambda) from the nearest-upsampled map
+__device__ inline void guide_weights(const StepCoef &k, const float *__restrict__ lm, long i, float &wp, float &wc)
+{
+    wp = k.w_pred; wc = k.w_cond;
+    if (k.use_map) { wc = lambda_at(k, lm, i); wp = 1.0f - wc; }
+}
+
+// mixed = wp*whiten(pred) + wc*whiten(cond) (:496), both products rounded
+__device__ inline float mix_elem(const StepCoef &k, const SliceStats &s, float wp, float wc, float pred, float x, float x0)
+{
+#pragma clang fp contract(off)
+    const float p = (pred - s.m1) / s.s1;
+    const float c = (cond_elem(k, x, x0) - s.m2) / s.s2;
+    return wp * p + wc * c;
+}
+
+// the guided epsilon of a step: whiten(mixed)
+__device__ inline float eps_elem(const StepCoef &k, const SliceStats &s, float wp, float wc, float pred, float x, float x0)
+{
+#pragma clang fp contract(off)
+    return (mix_elem(k, s, wp, wc, pred, x, x0) - s.m3) / s.s3;
+}
+
+// one element of a dense step (:497-515): x0_hat = sr*x - srm1*eps (products rounded); clamp; posterior mean = fma(c1, x0_hat,
+// c2*x); + sigma*z (product rounded)
+__device__ inline float step_apply_elem(const StepCoef &k, const SliceStats &s, const float *__restrict__ lm, long i, float pred,
+                                        float x, float x0, float z)
+{
+#pragma clang fp contract(off)
+    float wp, wc;
+    guide_weights(k, lm, i, wp, wc);
+    const float eps = eps_elem(k, s, wp, wc, pred, x, x0);
+    float xr = k.sr * x - k.srm1 * eps;
+    if (k.clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
+    const float mean = fmaf(k.c1, xr, k.c2 * x);
+    return mean + k.sigma * z;
+}
+
+// one element of a DDIM step (ddim_sample, :697-716) up to the noise term, scalar guidance: x0_hat = fma(-d_a, eps, x) / d_b;
+// clamp; d_p*x0_hat + d_dir*eps (products rounded).  With a draw the kernel adds it as fma(d_sig, z, this).
+__device__ inline float ddim_apply_elem(const StepCoef &k, const SliceStats &s, float pred, float x, float x0)
+{
+#pragma clang fp contract(off)
+    const float eps = eps_elem(k, s, k.w_pred, k.w_cond, pred, x, x0);
+    float xr = fmaf(-k.d_a, eps, x) / k.d_b;
+    if (k.clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
+    return k.d_p * xr + k.d_dir * eps;
+}
+
+// ------------------------------------------------------------------------------- host side (step.hip)
+// Where the N(0,1) draw of a launch comes from.  A buffer shaped like the output (counter false), or the counter generator:
+// draw `draw` of (seed, slice); row b is slice id0 + b, or ids[b] of a host table of B entries (the _ids entries).  The
+// implementations refuse a buffer source without a buffer.
+struct NoiseSrc {
+    bool counter;
+    const float *buf;
+    uint64_t seed;
+    int64_t id0;
+    const int64_t *ids;
+    int64_t draw;
+    bool ok() const { return counter || buf; }
+};
+static inline NoiseSrc noise_buffer(const float *buf) { return NoiseSrc{false, buf, 0, 0, nullptr, 0}; }
+static inline NoiseSrc noise_counter(uint64_t seed, int64_t id0, const int64_t *ids, int64_t draw) { return NoiseSrc{true, nullptr, seed, id0, ids, draw}; }
+
+// the one implementation of each op behind its C entries; error texts carry `who`
+int q_sample_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_x, const NoiseSrc &nz, float *d_out, int32_t B,
+                  int64_t n_per_slice, void *stream);
+int ddpm_step_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
+                   const NoiseSrc &nz, float *d_out, int32_t B, int32_t H, int32_t W, double lambda_scalar, const float *d_lambda_map,
+                   int32_t mh, int32_t mw, int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream);
+int check_ids(const char *who, const int64_t *slice_ids, int B);
+
+// the coefficient block of a DDIM step t -> t_prev; refuses a timestep outside the schedule (error text under `who`)
 int ddim_coef_fill(StepCoef &k, const char *who, const ipdm_schedule *s, int t, int t_prev, double lambda_scalar, double ddim_eta,
                    int clip_denoised);
 

@@ -1,6 +1,6 @@
 // Dose noise of a low-dose acquisition, injected into clean sinograms on the device: the noise stage of the low-dose simulator
 // (simulate.py).  Two entry points over one element expression: ipdm_lowdose_noise reads its N(0,1) draws from caller buffers,
-// ipdm_lowdose_noise_rng makes them in registers (randn_quad, ddpm_dev.h: one Philox quad per four elements, as sampler.hip does)
+// ipdm_lowdose_noise_rng makes them in registers (randn_quad, ddpm_dev.h: one Philox quad per four elements, as step.hip does)
 // and gives the bits of ipdm_randn into a buffer followed by ipdm_lowdose_noise.
 //
 // Replaces (reference file:line): add_noise (Utils/Low_dose_CT_simulate.py:38-44) -- model 0 -- and the per-slice host loop

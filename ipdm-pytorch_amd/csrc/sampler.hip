@@ -1,28 +1,20 @@
-// The reverse loop of the guided partial-diffusion sampler inside the library: one C call per outer pass
-// (ipdm_reverse_pass) or per fixed-schedule process (ipdm_guided_reverse), and the elementwise kernels written for it --
-// q_sample and the third pass of a guided step with the N(0,1) draw made in registers instead of read from a buffer that
-// an ipdm_randn launch wrote, and a pass epilogue (clamp + guide update in one launch).  The sparse (DDIM) sampler has the
-// same form: one C call per process (ipdm_sparse_reverse), its step with the draw in registers (ipdm_ddim_step_rng) and
-// its timestep sequences for a caller without numpy (ipdm_ddim_sequence).
+// The reverse loops of the guided partial-diffusion sampler inside the library: one C call per outer pass (ipdm_reverse_pass),
+// per fixed-schedule process (ipdm_guided_reverse) or per sparse (DDIM) process (ipdm_sparse_reverse), the pass epilogue
+// (clamp + guide update in one launch), and the sparse sampler's timestep sequences for a caller without numpy
+// (ipdm_ddim_sequence).  The steps these loops issue are step.hip's, with the N(0,1) draw made in registers or, in parity
+// mode, read from the caller's buffer: the same kernel and the same per-element arithmetic (ddpm_dev.h) either way.
 //
 // Replaces (reference file:line): the control flow of GaussianDiffusion.guided_reverse_process with an explicit t_start
-// list (Model/model.py:517-642): q_sample (:537-541), the inner loop of p_sample_condition calls with its guidance choice
-// (:542-568), the clamp after a pass (:569-573), the guidance map after pass 0 (:574-614), the guide updates and the reset
-// of x after pass 0 (:619-635), the final average (:637-638).  For the sparse sampler: the timestep sequences and the step
-// loop of ddim_sample (:664-724) and all of sparse_guided_reverse_process (:727-759).
+// list (Model/model.py:517-642): the inner loop of p_sample_condition calls with its guidance choice (:542-568), the clamp
+// after a pass (:569-573), the guidance map after pass 0 (:574-614), the guide updates and the reset of x after pass 0
+// (:619-635), the final average (:637-638).  For the sparse sampler: the timestep sequences and the step loop of ddim_sample
+// (:664-724) and all of sparse_guided_reverse_process (:727-759).
 //
-// Bits.  Every kernel here gives exactly the bits of the launches it replaces (ipdm_randn into a buffer, then ipdm_q_sample /
-// ipdm_ddpm_step / ipdm_ddim_step / ipdm_clamp + ipdm_axpbypcz).  The noise is the same pure function of (seed, slice, draw, element)
-// (randn_quad, ddpm_dev.h); the statistics passes of a step are ddpm.hip's own launches; the per-element expressions are
-// written with every rounding spelled out -- `#pragma clang fp contract(off)` and explicit fmaf -- in the form the compiler
-// gives ddpm.hip's kernels (read from their gfx950 code; tests/test_gpu_native_reverse.py and tests/test_gpu_native_sparse.py
-// hold the two to torch.equal):
-//   q_sample_kernel     out  = fma(sa, x, s1m*z)
-//   step_apply_kernel   cond = fma(-sa, x0, x) / s1m;  mix = wp*p + wc*c;  xr = sr*x - srm1*eps   (products rounded)
-//                       mean = fma(c1, xr, c2*x);  out = mean + sigma*z                           (product rounded)
-//   axpbypcz_kernel     v = a*x + b*y (products rounded);  v = fma(c, z, v)
-//   ddim_apply_kernel   cond = fma(-sa, x0, x) / s1m;  mix = wp*p + wc*c (products rounded);  xr = fma(-d_a, eps, x) / d_b
-//                       v = d_p*xr + d_dir*eps (products rounded);  with a draw: out = fma(d_sig, z, v)
+// Bits.  A loop here gives exactly the bits of the Python loop's launches (ipdm_randn into a buffer, then ipdm_q_sample /
+// ipdm_ddpm_step / ipdm_ddim_step / ipdm_clamp + ipdm_axpbypcz): the noise is the same pure function of (seed, slice, draw,
+// element), the steps are the same code, and the epilogue spells out the roundings of the two kernels it fuses:
+//   clamp_kernel      max(v, 0), then min(., 1) in mode 0
+//   axpbypcz_kernel   v = a*x + b*y (products rounded);  v = fma(c, z, v)
 #include <cmath>
 #include <cstring>
 #include "common.h"
@@ -30,165 +22,8 @@
 
 using namespace ipdm;
 
-// =============================================================================== kernels
-// grid of a per-slice streaming kernel over nq quads: enough workgroups to fill the chip (256 CUs x 8), never more than
-// the work, the rest by a grid stride
-static inline int quad_grid(long nq, int B)
-{
-    long per = 2048 / (B < 1 ? 1 : B);
-    if (per < 1) per = 1;
-    long g = (nq + 255) / 256;
-    if (g > per) g = per;
-    return (int)(g < 1 ? 1 : g);
-}
-
+// =============================================================================== pass epilogue
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-__device__ inline float q_sample_elem(float sa, float s1m, float x, float z)
-{
-#pragma clang fp contract(off)
-    return fmaf(sa, x, s1m * z);
-}
-
-// out[b, e] = sa*x[b, e] + s1m*z(seed, slice_id0 + b, draw, e); vec: n % 4 == 0 and 16-byte aligned pointers.
-// IDS (the _ids entries): the slice of row b comes from a by-value id table instead (SliceArg / slice_of, ddpm_dev.h)
-template <bool IDS>
-__global__ void __launch_bounds__(256) q_sample_rng_kernel(const float *__restrict__ x, float *__restrict__ out, long n, float sa,
-                                                           float s1m, uint32_t seed_lo, uint32_t seed_hi, SliceArg<IDS> slice_id0,
-                                                           long draw, int vec)
-{
-    const int b = blockIdx.y;
-    const size_t off = (size_t)b * n;
-    const long slice = slice_of(slice_id0, b);
-    const long nq = (n + 3) / 4;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        float z[4];
-        randn_quad(q, slice, draw, seed_lo, seed_hi, z);
-        const long e0 = q * 4;
-        if (vec) {
-            const float4 a = *reinterpret_cast<const float4 *>(x + off + e0);
-            *reinterpret_cast<float4 *>(out + off + e0) = make_float4(q_sample_elem(sa, s1m, a.x, z[0]), q_sample_elem(sa, s1m, a.y, z[1]),
-                                                                      q_sample_elem(sa, s1m, a.z, z[2]), q_sample_elem(sa, s1m, a.w, z[3]));
-        } else {
-            for (int e = 0; e < 4; ++e)
-                if (e0 + e < n) out[off + e0 + e] = q_sample_elem(sa, s1m, x[off + e0 + e], z[e]);
-        }
-    }
-}
-
-struct SliceStats { float m1, s1, m2, s2, m3, s3; };
-
-// one element of step_apply_kernel (ddpm.hip), noise handed in
-__device__ inline float step_apply_elem(const StepCoef &k, const SliceStats &s, const float *__restrict__ lm, long i, float pred,
-                                        float x, float x0, float z)
-{
-#pragma clang fp contract(off)
-    const float p = (pred - s.m1) / s.s1;
-    const float c = (fmaf(-k.sa, x0, x) / k.s1m - s.m2) / s.s2;
-    float wp = k.w_pred, wc = k.w_cond;
-    if (k.use_map) { wc = lambda_at(k, lm, i); wp = 1.0f - wc; }
-    const float eps = ((wp * p + wc * c) - s.m3) / s.s3;
-    float xr = k.sr * x - k.srm1 * eps;
-    if (k.clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
-    const float mean = fmaf(k.c1, xr, k.c2 * x);
-    return mean + k.sigma * z;
-}
-
-// pass C of a guided step with the draw made in registers: eps = whiten(mixed); x0_hat; clamp; posterior mean; + sigma*z
-// (Model/model.py:497-515).  One Philox quad per thread per four consecutive elements.  IDS: as q_sample_rng_kernel.
-template <bool IDS>
-__global__ void __launch_bounds__(256) step_apply_rng_kernel(const float *__restrict__ pred, const float *__restrict__ xt,
-                                                             const float *__restrict__ x0, const float *__restrict__ lmap,
-                                                             float *__restrict__ out, long n, StepCoef k,
-                                                             const double *__restrict__ ws, uint32_t seed_lo, uint32_t seed_hi,
-                                                             SliceArg<IDS> slice_id0, long draw, int vec)
-{
-    const int b = blockIdx.y;
-    const size_t off = (size_t)b * n;
-    double t[4], u[2];
-    load_totals(ws + (size_t)b * 2 * RED_BLOCKS * 8, 4, t);
-    load_totals(ws + ((size_t)b * 2 * RED_BLOCKS + RED_BLOCKS) * 8, 2, u);
-    SliceStats s;
-    mean_std(t[0], t[1], n, s.m1, s.s1);
-    mean_std(t[2], t[3], n, s.m2, s.s2);
-    mean_std(u[0], u[1], n, s.m3, s.s3);
-    const float *lm = k.use_map ? lmap + (size_t)b * k.mh * k.mw : nullptr;
-    const long slice = slice_of(slice_id0, b);
-    const long nq = (n + 3) / 4;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        float z[4];
-        randn_quad(q, slice, draw, seed_lo, seed_hi, z);
-        const long e0 = q * 4;
-        if (vec) {
-            const float4 p = *reinterpret_cast<const float4 *>(pred + off + e0);
-            const float4 x = *reinterpret_cast<const float4 *>(xt + off + e0);
-            const float4 g = *reinterpret_cast<const float4 *>(x0 + off + e0);
-            *reinterpret_cast<float4 *>(out + off + e0) =
-                make_float4(step_apply_elem(k, s, lm, e0, p.x, x.x, g.x, z[0]), step_apply_elem(k, s, lm, e0 + 1, p.y, x.y, g.y, z[1]),
-                            step_apply_elem(k, s, lm, e0 + 2, p.z, x.z, g.z, z[2]), step_apply_elem(k, s, lm, e0 + 3, p.w, x.w, g.w, z[3]));
-        } else {
-            for (int e = 0; e < 4; ++e)
-                if (e0 + e < n)
-                    out[off + e0 + e] = step_apply_elem(k, s, lm, e0 + e, pred[off + e0 + e], xt[off + e0 + e], x0[off + e0 + e], z[e]);
-        }
-    }
-}
-
-// one element of ddim_apply_kernel (ddpm.hip) up to the noise term: eps = whiten(mixed); x0_hat; clamp; sqrt(ac_prev)*x0_hat + dir*eps
-__device__ inline float ddim_apply_elem(const StepCoef &k, const SliceStats &s, float pred, float x, float x0)
-{
-#pragma clang fp contract(off)
-    const float p = (pred - s.m1) / s.s1;
-    const float c = (fmaf(-k.sa, x0, x) / k.s1m - s.m2) / s.s2;
-    const float eps = ((k.w_pred * p + k.w_cond * c) - s.m3) / s.s3;
-    float xr = fmaf(-k.d_a, eps, x) / k.d_b;
-    if (k.clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
-    return k.d_p * xr + k.d_dir * eps;
-}
-
-// the third launch of a DDIM step (ddim_sample, Model/model.py:697-716) with the draw made in registers: NOISE adds
-// d_sig * z(seed, slice_id0 + b, draw, e), one Philox quad per four consecutive elements; !NOISE (ddim_eta == 0) is
-// ddim_apply_kernel without a noise pointer -- no generator code, nothing read for it.
-template <bool NOISE>
-__global__ void __launch_bounds__(256) ddim_apply_rng_kernel(const float *__restrict__ pred, const float *__restrict__ xt,
-                                                             const float *__restrict__ x0, float *__restrict__ out, long n, StepCoef k,
-                                                             const double *__restrict__ ws, uint32_t seed_lo, uint32_t seed_hi,
-                                                             long slice_id0, long draw, int vec)
-{
-    const int b = blockIdx.y;
-    const size_t off = (size_t)b * n;
-    double t[4], u[2];
-    load_totals(ws + (size_t)b * 2 * RED_BLOCKS * 8, 4, t);
-    load_totals(ws + ((size_t)b * 2 * RED_BLOCKS + RED_BLOCKS) * 8, 2, u);
-    SliceStats s;
-    mean_std(t[0], t[1], n, s.m1, s.s1);
-    mean_std(t[2], t[3], n, s.m2, s.s2);
-    mean_std(u[0], u[1], n, s.m3, s.s3);
-    const long slice = slice_id0 + b;
-    const long nq = (n + 3) / 4;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (NOISE) randn_quad(q, slice, draw, seed_lo, seed_hi, z);
-        const long e0 = q * 4;
-        if (vec) {
-            const float4 p = *reinterpret_cast<const float4 *>(pred + off + e0);
-            const float4 x = *reinterpret_cast<const float4 *>(xt + off + e0);
-            const float4 g = *reinterpret_cast<const float4 *>(x0 + off + e0);
-            float4 v = make_float4(ddim_apply_elem(k, s, p.x, x.x, g.x), ddim_apply_elem(k, s, p.y, x.y, g.y),
-                                   ddim_apply_elem(k, s, p.z, x.z, g.z), ddim_apply_elem(k, s, p.w, x.w, g.w));
-            if (NOISE) v = make_float4(fmaf(k.d_sig, z[0], v.x), fmaf(k.d_sig, z[1], v.y), fmaf(k.d_sig, z[2], v.z), fmaf(k.d_sig, z[3], v.w));
-            *reinterpret_cast<float4 *>(out + off + e0) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e0 + e < n) {
-                    float v = ddim_apply_elem(k, s, pred[off + e0 + e], xt[off + e0 + e], x0[off + e0 + e]);
-                    if (NOISE) v = fmaf(k.d_sig, z[e], v);
-                    out[off + e0 + e] = v;
-                }
-        }
-    }
-}
 
 struct EpiCoef { int clip, mode, want_guide, has_z; float a, b, c; };
 
@@ -238,126 +73,6 @@ __global__ void __launch_bounds__(256) pass_epilogue_kernel(const float *__restr
             if (k.want_guide) guide[i] = epi_guide(k, o, img[i], k.has_z ? ldct[i] : 0.0f);
         }
     }
-}
-
-// =============================================================================== fused ops
-// the slice of row b: slice_id0 + b, or ids[b] of a host table of B entries (the _ids entries)
-struct SliceSel { int64_t id0; const int64_t *ids; };
-
-static int check_ids(const char *who, const int64_t *slice_ids, int B)
-{
-    IPDM_REQUIRE(slice_ids, "%s: NULL slice_ids", who);
-    IPDM_REQUIRE(B <= IPDM_SLICE_IDS_MAX, "%s: B = %d is above the id table's %d entries", who, B, IPDM_SLICE_IDS_MAX);
-    return IPDM_OK;
-}
-
-static int q_sample_rng_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B,
-                             int64_t n_per_slice, uint64_t seed, SliceSel sl, int64_t draw, void *stream)
-{
-    IPDM_REQUIRE(s && d_x && d_out && B > 0 && n_per_slice > 0, "%s: bad argument", who);
-    float c[8];
-    int rc = ipdm_schedule_coeffs(s, t, c);
-    if (rc) return rc;
-    const long n = (long)n_per_slice;
-    const int vec = (n & 3) == 0 && aligned16(d_x) && aligned16(d_out);
-    const dim3 grid(quad_grid((n + 3) / 4, B), B);
-    if (sl.ids)
-        hipLaunchKernelGGL(q_sample_rng_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d_x, d_out, n, c[0], c[1],
-                           (uint32_t)seed, (uint32_t)(seed >> 32), slice_ids_fill(sl.ids, B), (long)draw, vec);
-    else
-        hipLaunchKernelGGL(q_sample_rng_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d_x, d_out, n, c[0], c[1],
-                           (uint32_t)seed, (uint32_t)(seed >> 32), (long)sl.id0, (long)draw, vec);
-    IPDM_LAUNCH_CHECK();
-    return IPDM_OK;
-}
-
-extern "C" int ipdm_q_sample_rng(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B, int64_t n_per_slice,
-                                 uint64_t seed, int64_t slice_id0, int64_t draw, void *stream)
-{
-    return q_sample_rng_impl("q_sample_rng", s, t, d_x, d_out, B, n_per_slice, seed, SliceSel{slice_id0, nullptr}, draw, stream);
-}
-
-extern "C" int ipdm_q_sample_rng_ids(const ipdm_schedule *s, int32_t t, const float *d_x, float *d_out, int32_t B,
-                                     int64_t n_per_slice, uint64_t seed, const int64_t *slice_ids, int64_t draw, void *stream)
-{
-    int rc = check_ids("q_sample_rng_ids", slice_ids, B);
-    if (rc) return rc;
-    return q_sample_rng_impl("q_sample_rng_ids", s, t, d_x, d_out, B, n_per_slice, seed, SliceSel{0, slice_ids}, draw, stream);
-}
-
-static int ddpm_step_rng_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t,
-                              const float *d_x0, uint64_t seed, SliceSel sl, int64_t draw, float *d_out, int32_t B, int32_t H,
-                              int32_t W, double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw,
-                              int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream)
-{
-    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_x0 && d_out && d_ws && B > 0 && H > 0 && W > 0, "%s: bad argument", who);
-    IPDM_REQUIRE(!d_lambda_map || (mh > 0 && mw > 0), "%s: lambda map without dims", who);
-    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("%s: workspace too small", who); return IPDM_ERR_WORKSPACE; }
-    float c[8];
-    int rc = ipdm_schedule_coeffs(s, t, c);
-    if (rc) return rc;
-    StepCoef k;
-    step_coef_fill(k, c, t, lambda_scalar, d_lambda_map != nullptr, H, W, mh, mw, clip_denoised);
-    const long n = (long)H * W;
-    hipStream_t st = (hipStream_t)stream;
-    double *ws = (double *)d_ws;
-    step_stats_launch(d_eps_pred, d_x_t, d_x0, d_lambda_map, n, B, k, ws, st);
-    const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(d_x_t) && aligned16(d_x0) && aligned16(d_out);
-    const dim3 grid(quad_grid((n + 3) / 4, B), B);
-    if (sl.ids)
-        hipLaunchKernelGGL(step_apply_rng_kernel<true>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_lambda_map, d_out, n, k, ws,
-                           (uint32_t)seed, (uint32_t)(seed >> 32), slice_ids_fill(sl.ids, B), (long)draw, vec);
-    else
-        hipLaunchKernelGGL(step_apply_rng_kernel<false>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_x0, d_lambda_map, d_out, n, k, ws,
-                           (uint32_t)seed, (uint32_t)(seed >> 32), (long)sl.id0, (long)draw, vec);
-    IPDM_LAUNCH_CHECK();
-    return IPDM_OK;
-}
-
-extern "C" int ipdm_ddpm_step_rng(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
-                                  uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B, int32_t H, int32_t W,
-                                  double lambda_scalar, const float *d_lambda_map, int32_t mh, int32_t mw, int32_t clip_denoised,
-                                  void *d_ws, size_t ws_bytes, void *stream)
-{
-    return ddpm_step_rng_impl("ddpm_step_rng", s, t, d_eps_pred, d_x_t, d_x0, seed, SliceSel{slice_id0, nullptr}, draw, d_out, B, H, W,
-                              lambda_scalar, d_lambda_map, mh, mw, clip_denoised, d_ws, ws_bytes, stream);
-}
-
-extern "C" int ipdm_ddpm_step_rng_ids(const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t,
-                                      const float *d_x0, uint64_t seed, const int64_t *slice_ids, int64_t draw, float *d_out,
-                                      int32_t B, int32_t H, int32_t W, double lambda_scalar, const float *d_lambda_map, int32_t mh,
-                                      int32_t mw, int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream)
-{
-    int rc = check_ids("ddpm_step_rng_ids", slice_ids, B);
-    if (rc) return rc;
-    return ddpm_step_rng_impl("ddpm_step_rng_ids", s, t, d_eps_pred, d_x_t, d_x0, seed, SliceSel{0, slice_ids}, draw, d_out, B, H, W,
-                              lambda_scalar, d_lambda_map, mh, mw, clip_denoised, d_ws, ws_bytes, stream);
-}
-
-extern "C" int ipdm_ddim_step_rng(const ipdm_schedule *s, int32_t t, int32_t t_prev, const float *d_eps_pred, const float *d_x_t,
-                                  const float *d_cond, uint64_t seed, int64_t slice_id0, int64_t draw, float *d_out, int32_t B,
-                                  int64_t n_per_slice, double lambda_scalar, double ddim_eta, int32_t clip_denoised, void *d_ws,
-                                  size_t ws_bytes, void *stream)
-{
-    IPDM_REQUIRE(s && d_eps_pred && d_x_t && d_cond && d_out && d_ws && B > 0 && n_per_slice > 1, "ddim_step_rng: bad argument");
-    StepCoef k;
-    int rc = ddim_coef_fill(k, "ddim_step_rng", s, t, t_prev, lambda_scalar, ddim_eta, clip_denoised);
-    if (rc) return rc;
-    if (ws_bytes < ipdm_ddpm_workspace_bytes(B)) { set_error("ddim_step_rng: workspace too small"); return IPDM_ERR_WORKSPACE; }
-    const long n = (long)n_per_slice;
-    hipStream_t st = (hipStream_t)stream;
-    double *ws = (double *)d_ws;
-    step_stats_launch(d_eps_pred, d_x_t, d_cond, nullptr, n, B, k, ws, st);
-    const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(d_x_t) && aligned16(d_cond) && aligned16(d_out);
-    const dim3 grid(quad_grid((n + 3) / 4, B), B);
-    if (ddim_eta == 0.0)
-        hipLaunchKernelGGL(ddim_apply_rng_kernel<false>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_cond, d_out, n, k, ws, 0u, 0u, 0L,
-                           0L, vec);
-    else
-        hipLaunchKernelGGL(ddim_apply_rng_kernel<true>, grid, dim3(256), 0, st, d_eps_pred, d_x_t, d_cond, d_out, n, k, ws,
-                           (uint32_t)seed, (uint32_t)(seed >> 32), (long)slice_id0, (long)draw, vec);
-    IPDM_LAUNCH_CHECK();
-    return IPDM_OK;
 }
 
 // =============================================================================== the loop
@@ -443,10 +158,9 @@ int run_pass(const ipdm_schedule *s, ipdm_unet *net, const PassIn &p, int B, int
     const size_t bn = (size_t)B * n;
     int rc;
     const float *nz = p.noise;
-    const SliceSel sl = {a->slice_id0, p.slice_ids};
     // Model/model.py:537-541
     if (nz) rc = ipdm_q_sample(s, ts, p.x_in, nz, w.xa, (int64_t)bn, stream);
-    else rc = q_sample_rng_impl("q_sample_rng", s, ts, p.x_in, w.xa, B, n, a->seed, sl, p.draw, stream);
+    else rc = q_sample_impl("q_sample_rng", s, ts, p.x_in, noise_counter(a->seed, a->slice_id0, p.slice_ids, p.draw), w.xa, B, n, stream);
     if (rc) return rc;
     const bool epilogue = a->clip || p.guide_out;     // else the last step writes the pass's result itself
     float *cur = w.xa, *nxt = w.xb;
@@ -466,12 +180,9 @@ int run_pass(const ipdm_schedule *s, ipdm_unet *net, const PassIn &p, int B, int
             lam = 0.0;
         }
         float *dst = (i == 0 && !epilogue) ? p.iter : nxt;
-        if (nz)
-            rc = ipdm_ddpm_step(s, i, w.eps, cur, p.guide, nz + (size_t)k * bn, dst, B, H, W, lam, lmap, p.mh, p.mw, a->clip, w.step,
-                                w.step_bytes, stream);
-        else
-            rc = ddpm_step_rng_impl("ddpm_step_rng", s, i, w.eps, cur, p.guide, a->seed, sl, p.draw + k, dst, B, H, W, lam, lmap, p.mh,
-                                    p.mw, a->clip, w.step, w.step_bytes, stream);
+        const NoiseSrc draw = nz ? noise_buffer(nz + (size_t)k * bn) : noise_counter(a->seed, a->slice_id0, p.slice_ids, p.draw + k);
+        rc = ddpm_step_impl(nz ? "ddpm_step" : "ddpm_step_rng", s, i, w.eps, cur, p.guide, draw, dst, B, H, W, lam, lmap, p.mh, p.mw,
+                            a->clip, w.step, w.step_bytes, stream);
         if (rc) return rc;
         nxt = cur;
         cur = dst;

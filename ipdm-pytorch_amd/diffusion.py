@@ -188,12 +188,11 @@ class GaussianDiffusion:
         out = torch.empty_like(x_t)
         if isinstance(lambda_, torch.Tensor) and lambda_.dim() > 0:
             lm = lambda_.to(x_t.device, torch.float32).contiguous()
-            mh, mw = lm.shape[-2], lm.shape[-1]
-            _dcall(x_t, "ipdm_ddpm_step", self._h, int(t), ptr(eps_pred), ptr(x_t), ptr(x_0), ptr(noise), ptr(out), B, H, W,
-                   0.0, ptr(lm), mh, mw, 1 if clip_denoised else 0, ptr(ws), ws.numel())
+            guide = (0.0, ptr(lm), lm.shape[-2], lm.shape[-1])
         else:
-            _dcall(x_t, "ipdm_ddpm_step", self._h, int(t), ptr(eps_pred), ptr(x_t), ptr(x_0), ptr(noise), ptr(out), B, H, W,
-                   float(lambda_), None, 0, 0, 1 if clip_denoised else 0, ptr(ws), ws.numel())
+            guide = (float(lambda_), None, 0, 0)
+        _dcall(x_t, "ipdm_ddpm_step", self._h, int(t), ptr(eps_pred), ptr(x_t), ptr(x_0), ptr(noise), ptr(out), B, H, W,
+               *guide, 1 if clip_denoised else 0, ptr(ws), ws.numel())
         return out
 
     # ---- guidance map after pass 0 (Model/model.py:574-614)
