@@ -446,6 +446,48 @@ int ipdm_lowdose_noise(const float *d_proj, const float *d_z1, const float *d_z2
 int ipdm_lowdose_noise_rng(const float *d_proj, float *d_out, int32_t B, int64_t n_per_slice, double factor, double n0,
                            double ne, int32_t model, uint64_t seed, int64_t slice_id0, int64_t draw0, void *stream);
 
+/* ------------------------------------------------------------------ power transform --------- */
+/* opt.normal on the device (csrc/yj.hip): yeo_johnson_transform / yeo_johnson_inverse_transform (Model/model.py:762-807), i.e.
+ * sklearn's PowerTransformer(method="yeo-johnson", standardize=True), per slice.  Call sites of the reference: the sample
+ * loader (Utils/train_test_utils.py:578-580 ldct, :585-587 ldproj), between the convertor and the image stage (:560-562) and
+ * every reported iterate (the inverse, Model/model.py:616-617).  IPDM_ABI_VERSION stays 5: the entries were added without
+ * touching an existing signature; a binder detects them by symbol (dlsym of ipdm_yj_fit).
+ *
+ * All arithmetic is float64 from the float32 inputs, rounded once on output.  Statistics are per slice, reduced in a fixed
+ * order: a batch is bit-equal to its slices alone.  `params` is a HOST array [B][3] of float64: lambda, mean, scale, where mean
+ * is the population mean of the transformed slice and scale its population standard deviation (StandardScaler).  NaN elements
+ * are skipped by the statistics (n counts the rest) and propagate through apply / invert. */
+size_t ipdm_yj_workspace_bytes(int32_t B);
+/* sklearn's negative log-likelihood of slice b at lambdas_host[b] (PowerTransformer._yeo_johnson_optimize):
+ *   n/2 * log(var(T_lambda(x))) - (lambda - 1) * sum(sign(x) * log1p|x|),  population variance, formed over deviations from
+ * the transform of a per-slice pivot (never as E[y^2] - E[y]^2).  A variance that is not finite or is below DBL_MIN gives +inf.
+ * d_x [B, n_per_slice] f32; lambdas_host, nll_host: HOST arrays of B doubles.  This call SYNCHRONISES `stream` before it
+ * returns (it hands back host values), as ipdm_art_reconstruct's one-launch sweeps do; it allocates nothing on the device. */
+int ipdm_yj_nll(const float *d_x, int32_t B, int64_t n_per_slice, const double *lambdas_host, double *nll_host, void *d_ws,
+                size_t ws_bytes, void *stream);
+/* The fit: per slice the minimum of that likelihood by scipy.optimize.bracket from (-2, 2) followed by scipy.optimize.brent
+ * (tol 1.48e-8, maxiter 500) -- what sklearn's fit runs --, then one more pass at the final lambda for mean and scale.  All
+ * slices advance in lockstep: one launch evaluates one lambda for every unfinished slice (64 slices per launch) and one copy
+ * of B doubles comes back per round; the lambda-independent sum is computed once.  A slice's result does not depend on its
+ * neighbours.  evals_host[b] receives the number of likelihood evaluations of slice b.  This call SYNCHRONISES `stream` once
+ * per round.  A slice that is constant (variance below DBL_MIN at the bracket), has fewer than two elements that are not NaN,
+ * or whose bracket search does not end in a valid bracket is refused with IPDM_ERR_INVALID and a message naming the slice,
+ * before any output is written. */
+int ipdm_yj_fit(const float *d_x, int32_t B, int64_t n_per_slice, double *params_host, int32_t *evals_host, void *d_ws,
+                size_t ws_bytes, void *stream);
+/* out = (T_lambda(x) - mean) / scale with the four branches of PowerTransformer._yeo_johnson_transform (the logarithmic ones at
+ * |lambda| < 2^-52 and |lambda - 2| <= 2^-52).  d_out == d_x is allowed.  Any B (the parameters travel in the kernel arguments,
+ * 64 slices per launch) and any n_per_slice; a slice whose base addresses are 16-byte aligned moves 16 bytes per access, any
+ * other goes element by element.  Parameters that are not finite, or a scale <= 0: IPDM_ERR_INVALID before any launch.
+ * Asynchronous on `stream`, allocates nothing, does not synchronise. */
+int ipdm_yj_apply(const float *d_x, float *d_out, int32_t B, int64_t n_per_slice, const double *params_host, void *stream);
+/* x = y * scale + mean, then PowerTransformer._yeo_johnson_inverse_transform; a power whose base lies outside the domain gives
+ * NaN, as numpy.power does.  Same launch rules as ipdm_yj_apply. */
+int ipdm_yj_invert(const float *d_y, float *d_out, int32_t B, int64_t n_per_slice, const double *params_host, void *stream);
+/* ipdm_yj_fit with the likelihood evaluated on the host in plain float64 C++ (same minimiser, same shifted sums), x_host a HOST
+ * array: callable without a GPU, like ipdm_fbp_table.  The oracle of the device fit. */
+int ipdm_yj_fit_host(const float *x_host, int32_t B, int64_t n_per_slice, double *params_host, int32_t *evals_host);
+
 /* ------------------------------------------------------------------ measurement ------------- */
 /* Per-launch HIP-event timing of the hot kernels on their launch stream (bench.py roofline leg; no
  * reference counterpart -- the reference has no profiling).  Classes: 0 = conv 3x3

@@ -141,6 +141,12 @@ PROTOTYPES = {
     "ipdm_metrics_table": (_i64, [_vp, _i32, _vp, _i64]),
     "ipdm_lowdose_noise": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _f64, _f64, _f64, _i32, _vp]),
     "ipdm_lowdose_noise_rng": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _f64, _f64, _i32, _u64, _i64, _i64, _vp]),
+    "ipdm_yj_workspace_bytes": (_sz, [_i32]),
+    "ipdm_yj_nll": (C.c_int, [_vp, _i32, _i64, C.POINTER(_f64), C.POINTER(_f64), _vp, _sz, _vp]),
+    "ipdm_yj_fit": (C.c_int, [_vp, _i32, _i64, C.POINTER(_f64), C.POINTER(_i32), _vp, _sz, _vp]),
+    "ipdm_yj_apply": (C.c_int, [_vp, _vp, _i32, _i64, C.POINTER(_f64), _vp]),
+    "ipdm_yj_invert": (C.c_int, [_vp, _vp, _i32, _i64, C.POINTER(_f64), _vp]),
+    "ipdm_yj_fit_host": (C.c_int, [_vp, _i32, _i64, C.POINTER(_f64), C.POINTER(_i32)]),
 }
 
 _lib = None

@@ -44,14 +44,25 @@ _FLAGS = [
     # unless adaptive_per_slice (no reference counterpart either): then every slice of a batch takes its own branch of the
     # adaptive schedule, slices of one branch run together, and noise_strength is a list with one name per slice.
     ("metrics_backend", str, "numpy", None), ("adaptive_per_slice", bool, False, None),
+    # where opt.normal's power transform is fitted, applied and inverted (no reference counterpart): "sklearn" = the host path of
+    # the reference (normalize.py copies every slice to the host), "hip" = the float64 kernels of csrc/yj.hip on the device.
+    ("normal_backend", str, "sklearn", None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
+NORMAL_BACKENDS = ("sklearn", "hip")
 
 
 def check_metrics_backend(value):
     """An unknown metrics_backend is refused (argparse `choices` for the command line; this for a JSON overlay or update_opt)."""
     if value not in METRICS_BACKENDS:
         raise ValueError("metrics_backend must be one of %s, not %r" % (METRICS_BACKENDS, value))
+    return value
+
+
+def check_normal_backend(value):
+    """An unknown normal_backend is refused (argparse `choices` for the command line; this for a JSON overlay or update_opt)."""
+    if value not in NORMAL_BACKENDS:
+        raise ValueError("normal_backend must be one of %s, not %r" % (NORMAL_BACKENDS, value))
     return value
 
 
@@ -65,6 +76,8 @@ def default_cfg(argv=None):
             kw["nargs"] = nargs
         if name == "metrics_backend":
             kw["choices"] = METRICS_BACKENDS
+        if name == "normal_backend":
+            kw["choices"] = NORMAL_BACKENDS
         parser.add_argument("--" + name, **kw)
     argv = sys.argv[1:] if argv is None else argv
     opt = parser.parse_args(argv)
@@ -72,6 +85,7 @@ def default_cfg(argv=None):
     if opt.load_option_path is not None:
         load_option(opt, opt.load_option_path, given)
     check_metrics_backend(opt.metrics_backend)
+    check_normal_backend(opt.normal_backend)
     return opt
 
 

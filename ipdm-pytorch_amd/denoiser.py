@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import cfg_load
+from .config import cfg_load, check_normal_backend
 from .diffusion import GaussianDiffusion, NoiseSource
 from .fbp import FBP, tensor_sharpen
 from .evaluate import EvaluationMixin
@@ -87,6 +87,8 @@ class progressive_domain_denoiser(EvaluationMixin):
 
     # ------------------------------------------------------------------ options (:202-211)
     def update_opt(self, ultra_cfg=None):
+        if ultra_cfg is not None and "normal_backend" in ultra_cfg:
+            check_normal_backend(ultra_cfg["normal_backend"])
         if ultra_cfg is not None:
             cfg_load(ultra_cfg, self.opt.__dict__)
         if "convertor" in ultra_cfg.keys():          # update_opt(None) raises AttributeError as the reference does
@@ -186,18 +188,26 @@ class progressive_domain_denoiser(EvaluationMixin):
             self.noise = NoiseSource(self.seed, self.slice_id0)
         return self.noise
 
+    def _normal_backend(self):
+        """opt.normal_backend ("sklearn" when the key is absent); an unknown value is refused."""
+        return check_normal_backend(getattr(self.opt, "normal_backend", "sklearn"))
+
+    def _normal_input(self, x):
+        """What the power transform is fitted on: under "hip" the tensor moves to the device first, so the fit runs there."""
+        return x.to(self.opt.device) if self._normal_backend() == "hip" else x
+
     # ------------------------------------------------------------------ data (:569-594)
     def data_sample_load(self, ldct=None, ldproj=None, fdproj=None, fdct=None):
         if ldct is not None:
             if self.opt.normal:        # :578-580
-                ldct_norm, self.trans_ldimg = yeo_johnson_transform(ldct)
+                ldct_norm, self.trans_ldimg = yeo_johnson_transform(self._normal_input(ldct), self._normal_backend())
                 self.ldct = ldct_norm.to(self.opt.device)
             else:
                 self.ldct = ldct.to(self.opt.device)
             self.ldct_np = miu2pixel(ldct.squeeze().cpu().numpy())
         if ldproj is not None:
             if self.opt.normal:        # :585-587
-                ldproj_norm, self.trans_ldproj = yeo_johnson_transform(ldproj)
+                ldproj_norm, self.trans_ldproj = yeo_johnson_transform(self._normal_input(ldproj), self._normal_backend())
                 self.ldproj = ldproj_norm.to(self.opt.device)
             else:
                 self.ldproj = ldproj.to(self.opt.device)
@@ -316,7 +326,7 @@ class progressive_domain_denoiser(EvaluationMixin):
             sharpen_num = -1
         x = tensor_sharpen(result.to(self.opt.device), sharpen_num)
         if self.opt.normal:         # :560-562
-            x, self.trans_ldimg = yeo_johnson_transform(x)
+            x, self.trans_ldimg = yeo_johnson_transform(x, self._normal_backend())
         return self.img_denoiser(x, noise_strength=n_s, save_state=self.opt.save_it_state_img)
 
     # ------------------------------------------------------------------ fast path (no host copies)
@@ -337,7 +347,7 @@ class progressive_domain_denoiser(EvaluationMixin):
         if self.opt.convertor == "FBP" and self.opt.fbp_sharpen:
             img = tensor_sharpen(img, sharpen_num)
         if self.opt.normal:
-            img, self.trans_ldimg = yeo_johnson_transform(img)
+            img, self.trans_ldimg = yeo_johnson_transform(img, self._normal_backend())
         return self._img_dense(img, n_s, self.opt.ultra_img_denoise)[-1]
 
 
