@@ -314,6 +314,48 @@ int ipdm_sparse_reverse(const ipdm_schedule *s, ipdm_unet *net, const float *d_c
                         const int32_t *t_prev, const double *lambda, const ipdm_sparse_args *a, int64_t *draws_used,
                         void *d_ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ training objective ---- */
+/* The forward half of a training step: GaussianDiffusion.train_losses (Model/model.py:645-652) as train() calls it with one
+ * timestep per sample, t = randint(0, partial_timesteps, (bs,)) (Utils/train_test_utils.py:262-266) -- the epsilon-prediction
+ * loss of a network, per slice.  No gradients, no optimiser.  IPDM_ABI_VERSION stays 5: additive entries, detected by symbol
+ * (dlsym of ipdm_eps_loss).
+ *
+ * q_sample with one timestep per row.  ts is a HOST array of B timesteps and slice_ids a HOST array of B global slice ids, both
+ * consumed during the call (they reach the kernel by value).  Row b of ipdm_q_sample_rng_ts has the bits of
+ * ipdm_q_sample_rng(s, ts[b], .., B = 1, .., slice_id0 = slice_ids[b], draw) on that row alone; ipdm_q_sample_ts reads the draw
+ * from d_noise [B, n_per_slice] instead.  A timestep outside [0, timesteps), B above IPDM_SLICE_IDS_MAX or a NULL table:
+ * IPDM_ERR_INVALID before any launch. */
+int ipdm_q_sample_rng_ts(const ipdm_schedule *s, const int32_t *ts, const float *d_x, float *d_out, int32_t B,
+                         int64_t n_per_slice, uint64_t seed, const int64_t *slice_ids, int64_t draw, void *stream);
+int ipdm_q_sample_ts(const ipdm_schedule *s, const int32_t *ts, const float *d_x, const float *d_noise, float *d_out, int32_t B,
+                     int64_t n_per_slice, void *stream);
+/* d_sse[b] = sum over the n_per_slice elements of slice b of (noise - eps_pred)^2, float64: F.mse_loss's numerator
+ * (Model/model.py:651) per slice.  Each difference is taken and squared in float64 and added with one rounding (fma); a slice
+ * is reduced by a fixed number of workgroups whose partial sums (in d_ws) a second launch folds in a fixed order, and an
+ * element's place in that order depends on its index alone: a slice's sum has the same bits alone and in any batch, through
+ * the 16-byte path (n_per_slice % 4 == 0, 16-byte aligned pointers) and element by element.  ipdm_eps_sse reads the noise from
+ * d_noise [B, n_per_slice]; ipdm_eps_sse_rng makes draw `draw` of (seed, slice_ids[b]) in registers (same bits as
+ * ipdm_randn_ids into a buffer followed by ipdm_eps_sse; no noise buffer exists).  A short workspace: IPDM_ERR_WORKSPACE. */
+size_t ipdm_eps_sse_workspace_bytes(int32_t B);
+int ipdm_eps_sse(const float *d_eps_pred, const float *d_noise, double *d_sse, int32_t B, int64_t n_per_slice, void *d_ws,
+                 size_t ws_bytes, void *stream);
+int ipdm_eps_sse_rng(const float *d_eps_pred, double *d_sse, int32_t B, int64_t n_per_slice, uint64_t seed,
+                     const int64_t *slice_ids, int64_t draw, void *d_ws, size_t ws_bytes, void *stream);
+/* The objective in one call (Model/model.py:645-652, Utils/train_test_utils.py:262-266): x_t = q_sample(d_x0 [B,H,W], ts) with
+ * one draw; eps_pred = one ipdm_unet_forward per maximal run of consecutive equal timesteps, on that run's rows (slices are
+ * independent: a row's prediction has the bits of a forward on its run alone); d_sse[b] = the squared error of row b's
+ * prediction against the same draw (B doubles; the per-slice loss is d_sse[b] / (H*W), F.mse_loss their mean over the batch).
+ * The draw is draw `draw` of (seed, slice_ids[b]) made in registers in both kernels, or -- d_noise != NULL, parity mode -- read
+ * from d_noise [B, H*W] (slice_ids may then be NULL).  Consumes ONE draw, as the randn_like at :647.  Same bits as
+ * ipdm_q_sample_rng_ts, the forwards and ipdm_eps_sse_rng issued by the caller.  x_t, eps_pred, the UNet workspace and the
+ * reduction workspace are carved from d_ws (ipdm_eps_loss_workspace_bytes): no allocation, no synchronisation.  Bad arguments
+ * (NULL handles or arrays, a timestep outside [0, timesteps), B above IPDM_SLICE_IDS_MAX, a network that is not one channel
+ * in and out) and a short workspace (IPDM_ERR_WORKSPACE) are refused before any launch. */
+size_t ipdm_eps_loss_workspace_bytes(ipdm_unet *net, int32_t B, int32_t H, int32_t W);
+int ipdm_eps_loss(const ipdm_schedule *s, ipdm_unet *net, const float *d_x0, const int32_t *ts, double *d_sse, int32_t B,
+                  int32_t H, int32_t W, uint64_t seed, const int64_t *slice_ids, int64_t draw, const float *d_noise, void *d_ws,
+                  size_t ws_bytes, void *stream);
+
 /* op-level entry points (parity tests of the individual kernels against torch-CPU ops) */
 /* F.conv2d(cat(x1,x2) [upsampled to H,W by nearest], w, b, stride, padding=k/2) with optional fused
  * GroupNorm(+SiLU) prologue over the concatenated input and optional residual add.

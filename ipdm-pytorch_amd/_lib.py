@@ -112,6 +112,14 @@ PROTOTYPES = {
     "ipdm_ddim_sequence": (C.c_int, [C.c_char_p, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "ipdm_sparse_reverse": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32),
                                       C.POINTER(_i32), C.POINTER(_f64), C.POINTER(SparseArgs), C.POINTER(_i64), _vp, _sz, _vp]),
+    "ipdm_q_sample_rng_ts": (C.c_int, [_vp, C.POINTER(_i32), _vp, _vp, _i32, _i64, _u64, C.POINTER(_i64), _i64, _vp]),
+    "ipdm_q_sample_ts": (C.c_int, [_vp, C.POINTER(_i32), _vp, _vp, _vp, _i32, _i64, _vp]),
+    "ipdm_eps_sse_workspace_bytes": (_sz, [_i32]),
+    "ipdm_eps_sse": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _sz, _vp]),
+    "ipdm_eps_sse_rng": (C.c_int, [_vp, _vp, _i32, _i64, _u64, C.POINTER(_i64), _i64, _vp, _sz, _vp]),
+    "ipdm_eps_loss_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "ipdm_eps_loss": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _vp, _i32, _i32, _i32, _u64, C.POINTER(_i64), _i64, _vp, _vp, _sz,
+                                _vp]),
     "ipdm_op_conv2d": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
                                  _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ipdm_op_conv_gn_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp,

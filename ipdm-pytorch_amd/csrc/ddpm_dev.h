@@ -238,6 +238,12 @@ static inline NoiseSrc noise_counter(uint64_t seed, int64_t id0, const int64_t *
 // the one implementation of each op behind its C entries; error texts carry `who`
 int q_sample_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_x, const NoiseSrc &nz, float *d_out, int32_t B,
                   int64_t n_per_slice, void *stream);
+// ... with one timestep per row (ts: a host array of B <= IPDM_SLICE_IDS_MAX entries)
+int q_sample_ts_impl(const char *who, const ipdm_schedule *s, const int32_t *ts, const float *d_x, const NoiseSrc &nz, float *d_out,
+                     int32_t B, int64_t n_per_slice, void *stream);
+// sse[b] = sum over slice b of (draw - eps_pred)^2, float64 (the numerator of the training objective)
+int eps_sse_impl(const char *who, const float *d_eps_pred, const NoiseSrc &nz, double *d_sse, int32_t B, int64_t n_per_slice,
+                 void *d_ws, size_t ws_bytes, void *stream);
 int ddpm_step_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_eps_pred, const float *d_x_t, const float *d_x0,
                    const NoiseSrc &nz, float *d_out, int32_t B, int32_t H, int32_t W, double lambda_scalar, const float *d_lambda_map,
                    int32_t mh, int32_t mw, int32_t clip_denoised, void *d_ws, size_t ws_bytes, void *stream);

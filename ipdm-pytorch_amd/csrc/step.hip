@@ -1,9 +1,10 @@
-// q_sample and the guided steps (dense and DDIM) of the partial-diffusion sampler for gfx950: one kernel per operation,
-// whatever the source of its N(0,1) draw -- a buffer, the counter generator in registers, or none -- and one host
-// implementation per operation behind the C entries (ipdm_q_sample[_rng[_ids]], ipdm_ddpm_step[_rng[_ids]], ipdm_ddim_step[_rng]).
+// q_sample and the guided steps (dense and DDIM) of the partial-diffusion sampler for gfx950, and the squared error of the training
+// objective: one kernel per operation, whatever the source of its N(0,1) draw -- a buffer, the counter generator in registers, or
+// none -- and one host implementation per operation behind the C entries (ipdm_q_sample[_rng[_ids]], ipdm_q_sample[_rng]_ts,
+// ipdm_ddpm_step[_rng[_ids]], ipdm_ddim_step[_rng], ipdm_eps_sse[_rng]).
 //
 // Replaces (reference file:line): q_sample (Model/model.py:438-445), p_mean_variance_condition + p_sample_condition (:492-515),
-// the update of ddim_sample (:683-716).
+// the update of ddim_sample (:683-716), F.mse_loss(noise, predicted_noise) of train_losses (:651).
 //
 // A step is three launches.  Two statistics passes reduce eps_pred, cond and their mix per slice with a fixed
 // block decomposition and fp64 partial sums combined in a fixed order: deterministic and independent of batch sharding.  The
@@ -72,12 +73,27 @@ static inline int quad_grid(long nq, int B)
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // =============================================================================== q_sample
+// Where (sa, s1m) of a row come from: one pair for the whole launch, or -- every row at its own timestep (the training
+// objective's t = randint(0, T, (bs,)), Utils/train_test_utils.py:262-266) -- a table of IPDM_SLICE_IDS_MAX pairs handed over by
+// value like the id table (SliceIds, ddpm_dev.h): b is blockIdx.y, so a row's pair is two scalar loads from the argument block.
+struct CoefOne {
+    float sa, s1m;
+    __device__ float a(int) const { return sa; }
+    __device__ float s(int) const { return s1m; }
+};
+struct CoefRows {
+    float sa[IPDM_SLICE_IDS_MAX], s1m[IPDM_SLICE_IDS_MAX];
+    __device__ float a(int b) const { return sa[b]; }
+    __device__ float s(int b) const { return s1m[b]; }
+};
+
 // out[b, e] = sa*x[b, e] + s1m*z[b, e]
-template <class NZ>
-__global__ void __launch_bounds__(256) q_sample_kernel(const float *__restrict__ x, float *__restrict__ out, long n, float sa,
-                                                       float s1m, NZ nz, int vec)
+template <class NZ, class CF>
+__global__ void __launch_bounds__(256) q_sample_kernel(const float *__restrict__ x, float *__restrict__ out, long n, CF cf, NZ nz,
+                                                       int vec)
 {
     const int b = blockIdx.y;
+    const float sa = cf.a(b), s1m = cf.s(b);
     const size_t off = (size_t)b * n;
     const long nq = (n + 3) / 4;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
@@ -96,6 +112,18 @@ __global__ void __launch_bounds__(256) q_sample_kernel(const float *__restrict__
     }
 }
 
+template <class CF>
+static int q_sample_launch(const float *d_x, const NoiseSrc &nz, float *d_out, int B, long n, const CF &cf, void *stream)
+{
+    const int vec = (n & 3) == 0 && aligned16(d_x) && aligned16(d_out) && aligned16(nz.buf);
+    const dim3 grid(quad_grid((n + 3) / 4, B), B);
+    with_noise(nz, B, [&](auto p) {
+        hipLaunchKernelGGL((q_sample_kernel<decltype(p), CF>), grid, dim3(256), 0, (hipStream_t)stream, d_x, d_out, n, cf, p, vec);
+    });
+    IPDM_LAUNCH_CHECK();
+    return IPDM_OK;
+}
+
 int ipdm::q_sample_impl(const char *who, const ipdm_schedule *s, int32_t t, const float *d_x, const NoiseSrc &nz, float *d_out,
                         int32_t B, int64_t n_per_slice, void *stream)
 {
@@ -103,14 +131,26 @@ int ipdm::q_sample_impl(const char *who, const ipdm_schedule *s, int32_t t, cons
     float c[8];
     int rc = ipdm_schedule_coeffs(s, t, c);
     if (rc) return rc;
-    const long n = (long)n_per_slice;
-    const int vec = (n & 3) == 0 && aligned16(d_x) && aligned16(d_out) && aligned16(nz.buf);
-    const dim3 grid(quad_grid((n + 3) / 4, B), B);
-    with_noise(nz, B, [&](auto p) {
-        hipLaunchKernelGGL(q_sample_kernel<decltype(p)>, grid, dim3(256), 0, (hipStream_t)stream, d_x, d_out, n, c[0], c[1], p, vec);
-    });
-    IPDM_LAUNCH_CHECK();
-    return IPDM_OK;
+    return q_sample_launch(d_x, nz, d_out, B, (long)n_per_slice, CoefOne{c[0], c[1]}, stream);
+}
+
+// every row at its own timestep: ts is a HOST array of B entries, consumed here
+int ipdm::q_sample_ts_impl(const char *who, const ipdm_schedule *s, const int32_t *ts, const float *d_x, const NoiseSrc &nz,
+                           float *d_out, int32_t B, int64_t n_per_slice, void *stream)
+{
+    IPDM_REQUIRE(s && ts && d_x && nz.ok() && d_out && B > 0 && n_per_slice > 0, "%s: bad argument", who);
+    IPDM_REQUIRE(B <= IPDM_SLICE_IDS_MAX, "%s: B = %d is above the timestep table's %d entries", who, B, IPDM_SLICE_IDS_MAX);
+    CoefRows cf;
+    for (int b = 0; b < IPDM_SLICE_IDS_MAX; ++b) {
+        float c[8] = {0.0f, 0.0f};
+        if (b < B) {
+            int rc = ipdm_schedule_coeffs(s, ts[b], c);
+            if (rc) return rc;
+        }
+        cf.sa[b] = c[0];
+        cf.s1m[b] = c[1];
+    }
+    return q_sample_launch(d_x, nz, d_out, B, (long)n_per_slice, cf, stream);
 }
 
 int ipdm::check_ids(const char *who, const int64_t *slice_ids, int B)
@@ -140,6 +180,22 @@ extern "C" int ipdm_q_sample_rng_ids(const ipdm_schedule *s, int32_t t, const fl
     int rc = check_ids("q_sample_rng_ids", slice_ids, B);
     if (rc) return rc;
     return q_sample_impl("q_sample_rng_ids", s, t, d_x, noise_counter(seed, 0, slice_ids, draw), d_out, B, n_per_slice, stream);
+}
+
+// q_sample with one timestep per row (the x_t of train_losses, Model/model.py:645-649): row b is ipdm_q_sample_rng at ts[b] for
+// slice slice_ids[b], bit for bit
+extern "C" int ipdm_q_sample_rng_ts(const ipdm_schedule *s, const int32_t *ts, const float *d_x, float *d_out, int32_t B,
+                                    int64_t n_per_slice, uint64_t seed, const int64_t *slice_ids, int64_t draw, void *stream)
+{
+    int rc = check_ids("q_sample_rng_ts", slice_ids, B);
+    if (rc) return rc;
+    return q_sample_ts_impl("q_sample_rng_ts", s, ts, d_x, noise_counter(seed, 0, slice_ids, draw), d_out, B, n_per_slice, stream);
+}
+
+extern "C" int ipdm_q_sample_ts(const ipdm_schedule *s, const int32_t *ts, const float *d_x, const float *d_noise, float *d_out,
+                                int32_t B, int64_t n_per_slice, void *stream)
+{
+    return q_sample_ts_impl("q_sample_ts", s, ts, d_x, noise_buffer(d_noise), d_out, B, n_per_slice, stream);
 }
 
 // =============================================================================== statistics passes
@@ -207,6 +263,84 @@ static void step_stats_launch(const float *d_eps_pred, const float *d_x_t, const
 extern "C" size_t ipdm_ddpm_workspace_bytes(int32_t B)
 {
     return B <= 0 ? 0 : (size_t)B * 2 * RED_BLOCKS * 8 * sizeof(double);
+}
+
+// =============================================================================== squared error of a prediction
+// sse[b] = sum_e (z[b, e] - pred[b, e])^2 in float64: the numerator of F.mse_loss(noise, predicted_noise) (Model/model.py:651),
+// per slice, against a draw that is read from a buffer or made in registers beside the prediction.  RED_BLOCKS workgroups per
+// slice; quad q belongs to thread (q % 256) of workgroup (q / 256) % RED_BLOCKS whatever the path, and a thread adds its quads
+// in ascending order, element by element: the bits of a slice's sum depend neither on the 16-byte path nor on the batch.
+template <class NZ>
+__global__ void __launch_bounds__(256) eps_sse_kernel(const float *__restrict__ pred, long n, NZ nz, int vec, double *__restrict__ ws)
+{
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    const size_t off = (size_t)b * n;
+    const long nq = (n + 3) / 4;
+    double acc = 0.0;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)RED_BLOCKS * 256) {
+        float z[4], p[4];
+        nz.quad(b, q, n, vec, z);
+        const long e0 = q * 4;
+        if (vec) {
+            const float4 v = *reinterpret_cast<const float4 *>(pred + off + e0);
+            p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) p[e] = e0 + e < n ? pred[off + e0 + e] : 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double d = (double)z[e] - (double)p[e];
+            if (vec || e0 + e < n) acc = fma(d, d, acc);
+        }
+    }
+    block_reduce_store(&acc, 1, ws + (size_t)b * RED_BLOCKS + blockIdx.x);
+}
+
+// the RED_BLOCKS partials of a slice in a fixed order (one wave per slice)
+__global__ void __launch_bounds__(64) eps_sse_fold_kernel(const double *__restrict__ ws, double *__restrict__ sse)
+{
+    const double v = wave_sum(ws[(size_t)blockIdx.x * RED_BLOCKS + threadIdx.x]);
+    if (threadIdx.x == 0) sse[blockIdx.x] = v;
+}
+
+extern "C" size_t ipdm_eps_sse_workspace_bytes(int32_t B)
+{
+    return B <= 0 ? 0 : (size_t)B * RED_BLOCKS * sizeof(double);
+}
+
+int ipdm::eps_sse_impl(const char *who, const float *d_eps_pred, const NoiseSrc &nz, double *d_sse, int32_t B, int64_t n_per_slice,
+                       void *d_ws, size_t ws_bytes, void *stream)
+{
+    static_assert(RED_BLOCKS == 64, "eps_sse_fold_kernel folds one partial per lane of a wave");
+    IPDM_REQUIRE(d_eps_pred && nz.ok() && d_sse && d_ws && B > 0 && n_per_slice > 0, "%s: bad argument", who);
+    if (ws_bytes < ipdm_eps_sse_workspace_bytes(B)) { set_error("%s: workspace too small", who); return IPDM_ERR_WORKSPACE; }
+    const long n = (long)n_per_slice;
+    hipStream_t st = (hipStream_t)stream;
+    double *ws = (double *)d_ws;
+    const int vec = (n & 3) == 0 && aligned16(d_eps_pred) && aligned16(nz.buf);
+    with_noise(nz, B, [&](auto p) {
+        hipLaunchKernelGGL(eps_sse_kernel<decltype(p)>, dim3(RED_BLOCKS, B), dim3(256), 0, st, d_eps_pred, n, p, vec, ws);
+    });
+    hipLaunchKernelGGL(eps_sse_fold_kernel, dim3(B), dim3(64), 0, st, ws, d_sse);
+    IPDM_LAUNCH_CHECK();
+    return IPDM_OK;
+}
+
+extern "C" int ipdm_eps_sse(const float *d_eps_pred, const float *d_noise, double *d_sse, int32_t B, int64_t n_per_slice, void *d_ws,
+                            size_t ws_bytes, void *stream)
+{
+    return eps_sse_impl("eps_sse", d_eps_pred, noise_buffer(d_noise), d_sse, B, n_per_slice, d_ws, ws_bytes, stream);
+}
+
+extern "C" int ipdm_eps_sse_rng(const float *d_eps_pred, double *d_sse, int32_t B, int64_t n_per_slice, uint64_t seed,
+                                const int64_t *slice_ids, int64_t draw, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = check_ids("eps_sse_rng", slice_ids, B);
+    if (rc) return rc;
+    return eps_sse_impl("eps_sse_rng", d_eps_pred, noise_counter(seed, 0, slice_ids, draw), d_sse, B, n_per_slice, d_ws, ws_bytes,
+                        stream);
 }
 
 // =============================================================================== dense step

@@ -65,7 +65,9 @@ class progressive_domain_denoiser(EvaluationMixin):
         self.result_save_path = result_save_path
         self.proj_model = self.img_model = None
         if opt.mode in ("train_proj", "train_img"):
-            raise NotImplementedError("training is out of scope of the sampling hot path")
+            raise NotImplementedError("mode %r: the optimiser (gradients, checkpoints, fit) is out of scope of this build; the "
+                                      "training objective itself can be evaluated from a test_* mode (loss_curve, "
+                                      "GaussianDiffusion.train_losses)" % (opt.mode,))
         if opt.mode in ("test_proj", "test_prog"):
             self.init_proj_model()
         self.init_convertor(opt.convertor)

@@ -1,5 +1,6 @@
-"""GaussianDiffusion: host-side mirror of the reference's Model/model.py:376-642 on the dense
-sampling path.  Control flow (passes, steps, guidance scheduling) is Python as in the reference;
+"""GaussianDiffusion: host-side mirror of the reference's Model/model.py:376-759 on the sampling
+paths and, for the training objective, its forward half (train_losses, :645-652).  Control flow
+(passes, steps, guidance scheduling) is Python as in the reference;
 every tensor operation is a libipdm_hip.so call on device-resident buffers -- nothing goes through
 the host inside the loop (the reference does a D2H/np.vectorize/numba/H2D round trip per step in
 adaptive mode, Model/model.py:554-560).
@@ -54,6 +55,23 @@ def ddim_sequence(method, timesteps, t_start, n):
     seq, prev = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
     call("ipdm_ddim_sequence", str(method).encode(), int(timesteps), int(t_start), n, seq, prev)
     return list(seq[:n]), list(prev[:n])
+
+
+def _one_timestep(t):
+    return int(t.reshape(-1)[0]) if isinstance(t, torch.Tensor) else int(t[0]) if isinstance(t, (list, tuple)) else int(t)
+
+
+def _row_timesteps(t, B):
+    """The B per-row timesteps of a tensor / list `t` whose entries differ, as a list of ints; None when `t` is one timestep
+    for the whole batch (an integer, one entry, or equal entries: the integer path serves those)."""
+    if not isinstance(t, (torch.Tensor, list, tuple)):
+        return None
+    vals = [int(v) for v in (t.reshape(-1).tolist() if isinstance(t, torch.Tensor) else t)]
+    if len(vals) == 1 or all(v == vals[0] for v in vals):
+        return None
+    if len(vals) != B:
+        raise ValueError("%d timesteps for a batch of %d" % (len(vals), B))
+    return vals
 
 
 class NoiseSource:
@@ -171,10 +189,92 @@ class GaussianDiffusion:
 
     # ---- Model/model.py:438-445
     def q_sample(self, x_start, t, noise):
+        """`t`: one integer for the whole batch, or one timestep per row (a tensor or list of B entries, as train_losses
+        hands it over: ipdm_q_sample_ts)."""
         x = x_start.contiguous()
         out = torch.empty_like(x)
-        _dcall(x, "ipdm_q_sample", self._h, int(t), ptr(x), ptr(noise), ptr(out), x.numel())
+        ts = _row_timesteps(t, x.shape[0])
+        if ts is None:
+            _dcall(x, "ipdm_q_sample", self._h, _one_timestep(t), ptr(x), ptr(noise), ptr(out), x.numel())
+            return out
+        B = x.shape[0]
+        for lo in range(0, B, _lib.SLICE_IDS_MAX):
+            k = min(B - lo, _lib.SLICE_IDS_MAX)
+            _dcall(x, "ipdm_q_sample_ts", self._h, (C.c_int32 * k)(*ts[lo:lo + k]), ptr(x[lo:lo + k]), ptr(noise[lo:lo + k]),
+                   ptr(out[lo:lo + k]), k, x.numel() // B)
         return out
+
+    # ---- Model/model.py:645-652, per slice
+    def _loss_workspace(self, model, B, H, W, device):
+        """Scratch of ipdm_eps_loss, cached by (device, B, H, W)."""
+        with torch.cuda.device(device):
+            need = lib().ipdm_eps_loss_workspace_bytes(model._ensure(), B, H, W)
+        key = ("loss", device, B, H, W)
+        w = self._rws.get(key)
+        if w is None or w.numel() < need:
+            w = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+            self._rws[key] = w
+        return w
+
+    def _loss_native(self, model, x):
+        """ipdm_eps_loss serves the library's own one-channel UNetModel on the device of x."""
+        from .unet import UNetModel
+        if not (isinstance(model, UNetModel) and x.is_cuda and x.dim() == 4 and x.shape[1] == 1 and model.in_channels == 1
+                and model.out_channels == 1):
+            return False
+        d = model._device
+        return d.type == "cuda" and (d.index is None or d.index == x.device.index)
+
+    @torch.no_grad()
+    def eps_losses(self, model, x_start, t, noise=None):
+        """The epsilon-prediction loss of train_losses (Model/model.py:645-652) per slice: a float64 device tensor [B] of
+        mean((noise - model(q_sample(x_start, t, noise), t))**2) over each slice, summed in float64.  `t`: one timestep per row
+        (tensor or list) or an integer.  `noise`: a NoiseSource (default: seed 0, slice ids 0..B-1) or an InjectedNoise; it
+        advances by ONE draw.  The library's own UNetModel runs the whole objective in one call (ipdm_eps_loss: the draw is made
+        in registers beside x_t and beside the prediction, no noise buffer exists); any other callable gets q_sample, model(x, t)
+        with a [B] tensor of timesteps, and ipdm_eps_sse."""
+        x = x_start.to(torch.float32).contiguous()
+        B = x.shape[0]
+        n = x.numel() // B
+        ts = _row_timesteps(t, B)
+        if ts is None:
+            ts = [_one_timestep(t)] * B
+        noise = noise if noise is not None else NoiseSource(0)
+        sse = torch.empty((B,), dtype=torch.float64, device=x.device)
+        counter = isinstance(noise, NoiseSource)
+        native = self._loss_native(model, x)
+        z = None
+        if counter and native:
+            ids = noise.slice_ids if noise.slice_ids is not None else [noise.slice_id0 + b for b in range(B)]
+            if len(ids) != B:
+                raise ValueError("noise source for %d slices asked for a batch of %d" % (len(ids), B))
+            draw = noise.draw
+            noise.draw += 1
+        else:
+            z = noise.next_like(x).to(x.device, torch.float32).contiguous()
+        if native:
+            H, W = x.shape[2], x.shape[3]
+            for lo in range(0, B, _lib.SLICE_IDS_MAX):
+                k = min(B - lo, _lib.SLICE_IDS_MAX)
+                ws = self._loss_workspace(model, k, H, W, x.device)
+                _dcall(x, "ipdm_eps_loss", self._h, model._ensure(), ptr(x[lo:lo + k]), (C.c_int32 * k)(*ts[lo:lo + k]),
+                       ptr(sse[lo:lo + k]), k, H, W, noise.seed if z is None else 0,
+                       (C.c_int64 * k)(*ids[lo:lo + k]) if z is None else None, draw if z is None else 0,
+                       None if z is None else ptr(z[lo:lo + k]), ptr(ws), ws.numel())
+        else:
+            x_t = self.q_sample(x, ts, z)
+            pred = model(x_t, torch.tensor(ts, dtype=torch.long, device=x.device)).to(torch.float32).contiguous()
+            if pred.shape != x.shape:
+                raise ValueError("eps_losses: the model returned %s for an input of %s" % (tuple(pred.shape), tuple(x.shape)))
+            ws = self._workspace("sse", lib().ipdm_eps_sse_workspace_bytes(B), x.device)
+            _dcall(x, "ipdm_eps_sse", ptr(pred), ptr(z), ptr(sse), B, n, ptr(ws), ws.numel())
+        return sse / float(n)
+
+    def train_losses(self, model, x_start, t, noise=None):
+        """The reference's train_losses(model, x_start, t) (Model/model.py:645-652): F.mse_loss(noise, model(x_noisy, t)) as a
+        0-dim float32 device tensor -- the mean of eps_losses over the batch, taken in float64 and rounded once.  The forward
+        half of a training step only: no graph is recorded, there is nothing to call .backward() on."""
+        return self.eps_losses(model, x_start, t, noise=noise).mean().to(torch.float32)
 
     # ---- Model/model.py:492-515 (per-slice statistics)
     def p_sample_condition(self, model, x_t, x_0, t, clip_denoised=True, lambda_=1.0, noise=None, eps_pred=None):

@@ -615,7 +615,8 @@ class EvaluationMixin:
     def init_data_loader(self):
         o = self.opt
         if "train" in o.mode:
-            raise NotImplementedError("training is out of scope of this build (DESIGN.md section 7)")
+            raise NotImplementedError("the optimiser is out of scope of this build (DESIGN.md section 7); the training objective "
+                                      "can be evaluated from a test_* mode (loss_curve, GaussianDiffusion.train_losses)")
         self.test_dataset = Siemens_dataset_npz(ldimg_path=o.test_dataset_path_LD_img, fdimg_path=o.test_dataset_path_FD_img,
                                                 ldproj_path=o.test_dataset_path_LD_proj,
                                                 fdproj_path=o.test_dataset_path_FD_proj, proj_clip=o.clip_proj,
@@ -708,4 +709,57 @@ class EvaluationMixin:
     def fit(self):
         if "test" in self.opt.mode:
             return self.test(0)
-        raise NotImplementedError("training is out of scope of this build (DESIGN.md section 7)")
+        raise NotImplementedError("the optimiser is out of scope of this build (DESIGN.md section 7); the training objective can "
+                                  "be evaluated (loss_curve, GaussianDiffusion.train_losses)")
+
+    # ---- the training objective over the dataset (Utils/train_test_utils.py:253-266, Model/model.py:645-652)
+    @torch.no_grad()
+    def loss_curve(self, domain, timesteps=None, numbers=None, batch_size=8, seed=0):
+        """The epsilon-prediction loss of the loaded `domain` ("img" / "proj") network per timestep, over the full-dose side of
+        the test dataset: the number train() optimises and logs as train/loss, at one network evaluation per slice and
+        timestep.  Slices go through train()'s preprocessing (:260-264): the dataset's /10 under clip_proj, .clamp(min=0),
+        and under opt.normal the power transform of the configured normal_backend.  The first `numbers` slices of the
+        dataset (all when None) are evaluated in batches of `batch_size` at every t of `timesteps` (default
+        range(partial_timesteps_<domain>)).  Slice k draws its noise under slice id k and the j-th timestep uses draw j of
+        NoiseSource(seed): a slice's curve does not depend on the batching.  A batch's calls are issued without a host
+        synchronisation; its [n_t, B] doubles are copied back once.
+
+        Returns (curve, per_slice): curve = {t: {"mean", "std" (population), "n"}} over the slices, per_slice the float64
+        matrix [n_t, n_slices].  With a result tree, both are written to <save_test_results>/loss_curve_<domain>.json."""
+        from .diffusion import NoiseSource
+        from .normalize import yeo_johnson_transform
+        if domain not in ("img", "proj"):
+            raise ValueError('loss_curve: domain should be one of "img", "proj"')
+        model = getattr(self, domain + "_model", None)
+        gd = getattr(self, domain + "_gaussian_diffusion", None)
+        if model is None or gd is None:
+            raise ValueError("loss_curve: mode %r builds no %s network (test_%s or test_prog does)" % (self.opt.mode, domain, domain))
+        o = self.opt
+        if self.test_dataset is None:
+            self.init_data_loader()
+        ds = self.test_dataset
+        col = 2 if domain == "img" else 1            # fd_img / fd_proj of a dataset item
+        ts = [int(t) for t in (range(getattr(o, "partial_timesteps_" + domain)) if timesteps is None else timesteps)]
+        total = len(ds) if numbers is None or numbers <= 0 else min(int(numbers), len(ds))
+        B = max(1, int(batch_size))
+        cols = []
+        for lo in range(0, total, B):
+            ids = list(range(lo, min(lo + B, total)))
+            items = [ds[k][col] for k in ids]
+            if any(it is None for it in items):
+                raise ValueError("loss_curve: the test dataset has no full-dose %s tree" % domain)
+            x = torch.stack(items, 0).float().to(o.device).clamp(min=0)
+            if o.normal:
+                x, _ = yeo_johnson_transform(self._normal_input(x), self._normal_backend())
+                x = x.to(o.device, torch.float32)
+            rows = [gd.eps_losses(model, x, [t] * len(ids), noise=NoiseSource(seed).for_slices(ids, j)) for j, t in enumerate(ts)]
+            cols.append(torch.stack(rows, 0).cpu().numpy().astype(np.float64))
+        per_slice = np.concatenate(cols, axis=1) if cols else np.zeros((len(ts), 0))
+        curve = {t: {"mean": float(per_slice[j].mean()) if total else float("nan"),
+                     "std": float(per_slice[j].std()) if total else float("nan"), "n": int(total)} for j, t in enumerate(ts)}
+        if self.save_root_path is not None:
+            os.makedirs(self.save_root_path, exist_ok=True)
+            with open(os.path.join(self.save_root_path, "loss_curve_%s.json" % domain), "w") as f:
+                json.dump({"domain": domain, "seed": int(seed), "timesteps": ts, "slices": list(range(total)),
+                           "curve": {str(t): v for t, v in curve.items()}, "per_slice": per_slice.tolist()}, f, indent=1)
+        return curve, per_slice

@@ -48,7 +48,7 @@ def param_shapes(cfg):
 
 
 class UNetModel:
-    """Drop-in for the reference's UNetModel on the sampling path (inference only)."""
+    """Drop-in for the reference's UNetModel: the forward only (sampling, and the training objective's prediction)."""
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2,
                  attention_resolutions=(8, 16), dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True,
@@ -152,12 +152,16 @@ class UNetModel:
         return out
 
     def __call__(self, x, timesteps):
-        """UNetModel.forward(x, timesteps) (Model/model.py:283): one timestep for the whole batch."""
+        """UNetModel.forward(x, timesteps) (Model/model.py:283): an integer, or a tensor / list of timesteps.  Equal entries are
+        one timestep for the whole batch (the sampler's torch.full((1,), i), :564).  Differing entries -- one per row, as
+        train() draws them (Utils/train_test_utils.py:265) -- run one forward per maximal run of consecutive equal timesteps, each
+        on its rows, into one output tensor: slices are independent, so a row gets the bits of a forward on its run alone.  That
+        path is eager (no graph replay)."""
         t = timesteps
-        if isinstance(t, torch.Tensor):
-            vals = t.reshape(-1).tolist()
+        if isinstance(t, (torch.Tensor, list, tuple)):
+            vals = [int(v) for v in (t.reshape(-1).tolist() if isinstance(t, torch.Tensor) else t)]
             if any(v != vals[0] for v in vals):
-                raise NotImplementedError("per-sample timesteps: the sampling path always passes one t (model.py:564)")
+                return self._forward_runs(x, vals)
             t = int(vals[0])
         x = x.to(self._device, torch.float32).contiguous()
         if self.use_graph:
@@ -165,6 +169,20 @@ class UNetModel:
         out = torch.empty((x.shape[0], self.out_channels, x.shape[2], x.shape[3]), dtype=torch.float32,
                           device=self._device)
         return self.forward_into(x, t, out)
+
+    def _forward_runs(self, x, ts):
+        x = x.to(self._device, torch.float32).contiguous()
+        if len(ts) != x.shape[0]:
+            raise ValueError("UNetModel: %d timesteps for a batch of %d" % (len(ts), x.shape[0]))
+        out = torch.empty((x.shape[0], self.out_channels, x.shape[2], x.shape[3]), dtype=torch.float32, device=self._device)
+        lo = 0
+        while lo < len(ts):
+            hi = lo + 1
+            while hi < len(ts) and ts[hi] == ts[lo]:
+                hi += 1
+            self.forward_into(x[lo:hi], ts[lo], out[lo:hi])
+            lo = hi
+        return out
 
     def _forward_graph(self, x, t):
         """The forward replayed from a hipGraph: x is copied into a static buffer, the captured launches write a static
