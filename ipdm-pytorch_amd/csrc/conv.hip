@@ -29,6 +29,7 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "conv_layer.h"
 
 using namespace ipdm;
 
@@ -447,7 +448,7 @@ void conv_pack_weights(const float *w, int Cout, int Cin, int ks, int interleave
     const int group = interleave ? 32 * interleave : 64;
     const int kc = conv_ws_k_chunk(ks, interleave);           // channels per K chunk of the kernel that will read the slab
     cin_pad = (Cin + kc - 1) / kc * kc;
-    cout_pad = (Cout + group - 1) / group * group;
+    cout_pad = conv_cout_pad(Cout, interleave);
     const int taps = ks * ks;
     packed.assign((size_t)cin_pad * taps * cout_pad, 0.0f);
     for (int co = 0; co < Cout; ++co) {

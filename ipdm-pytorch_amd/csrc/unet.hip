@@ -15,7 +15,7 @@
 #include <string>
 #include <tuple>
 #include <vector>
-#include "unet_kernels.h"
+#include "conv_layer.h"
 
 using namespace ipdm;
 
@@ -306,13 +306,9 @@ extern "C" int ipdm_unet_param_info(const ipdm_unet_cfg *cfg, int32_t idx, char 
 // ------------------------------------------------------------------------------------ the net
 namespace {
 
-// w_t: the same weights with the two kernel axes swapped (3x3 only): what the convolution needs when the executor runs
+// img[1]: the layer with the two kernel axes swapped (3x3 only, else img[0] again): what the convolution needs when the executor runs
 // a forward on spatially TRANSPOSED activations (run_forward: orientation)
-// w_up2 / w_up2_t: the Upsample convolutions' parity form (conv_pack_weights_up2), null elsewhere
-struct ConvP { float *w = nullptr; float *w_t = nullptr; float *b = nullptr; int cin = 0, cout = 0, ks = 0, cout_pad = 0, interleave = 0;
-               float *w_up2 = nullptr, *w_up2_t = nullptr;
-               float *w_wup2 = nullptr, *w_wup2_t = nullptr;      // ... in the F(2x2,2x2) domain (conv_pack_weights_wup2), wide layers
-               float *w_wino = nullptr, *w_wino_t = nullptr; };      // Winograd-domain weights (conv_pack_weights_wino), both orientations
+struct ConvP { ConvImages img[2]; float *b = nullptr; int cin = 0, cout = 0, ks = 0, cout_pad = 0, interleave = 0; };
 struct NormP { float *g = nullptr, *b = nullptr; int ch = 0, groups = 0; };
 struct ResP { NormP n1, n2; ConvP c1, c2, sc; bool has_sc = false; int bias_off = 0;      // bias_off into bias_eff
               float *b2sc = nullptr; };      // conv2's bias + the shortcut's (the fused form of the narrow levels: conv_direct_skip_ok)
@@ -491,48 +487,28 @@ int make_conv(ipdm_unet *net, const WeightMap &wm, const std::string &wname, con
 {
     const float *w = wm.get(wname);
     IPDM_REQUIRE(w, "unet_create: missing parameter %s", wname.c_str());
-    std::vector<float> packed;
-    int cin_pad, cout_pad;
-    out.interleave = conv_weight_interleave(cout, ks, stride);
-    conv_pack_weights(w, cout, cin, ks, out.interleave, packed, cin_pad, cout_pad);
-    out.cin = cin; out.cout = cout; out.ks = ks; out.cout_pad = cout_pad;
-    int rc = upload(net, packed.data(), packed.size(), &out.w);
-    if (rc) return rc;
-    out.w_t = out.w;
-    if (ks == 3) {
-        std::vector<float> wt((size_t)cout * cin * 9);
-        for (size_t oc = 0; oc < (size_t)cout * cin; ++oc)
-            for (int ky = 0; ky < 3; ++ky)
-                for (int kx = 0; kx < 3; ++kx) wt[oc * 9 + ky * 3 + kx] = w[oc * 9 + kx * 3 + ky];
-        conv_pack_weights(wt.data(), cout, cin, ks, out.interleave, packed, cin_pad, cout_pad);
-        rc = upload(net, packed.data(), packed.size(), &out.w_t);
+    out.cin = cin; out.cout = cout; out.ks = ks;
+    const std::vector<float> wt = ks == 3 ? conv_transpose_taps(w, cout, cin) : std::vector<float>();
+    for (int o = 0; o < (ks == 3 ? 2 : 1); ++o) {
+        PackedConv L;
+        conv_pack_layer(o ? wt.data() : w, cout, cin, ks, stride, up, L);
+        out.interleave = L.interleave; out.cout_pad = L.cout_pad;
+        const int rc = conv_upload_images(L, out.img[o], [&](const std::vector<float> &v, const float **dev) {
+            float *d = nullptr;
+            const int r = upload(net, v.data(), v.size(), &d);
+            *dev = d;
+            return r;
+        });
         if (rc) return rc;
-        if (!up && conv_wino_shape_ok(cout, cin, ks, stride, out.interleave)) {
-            conv_pack_weights_wino(w, cout, cin, packed);
-            if ((rc = upload(net, packed.data(), packed.size(), &out.w_wino))) return rc;
-            conv_pack_weights_wino(wt.data(), cout, cin, packed);
-            if ((rc = upload(net, packed.data(), packed.size(), &out.w_wino_t))) return rc;
-        }
-        if (up && (out.interleave == 2 || out.interleave == 4 || (out.interleave == 0 && cout <= 16))) {      // Upsample: the parity form of both orientations
-            conv_pack_weights_up2(w, cout, cin, out.interleave, packed);
-            if ((rc = upload(net, packed.data(), packed.size(), &out.w_up2))) return rc;
-            conv_pack_weights_up2(wt.data(), cout, cin, out.interleave, packed);
-            if ((rc = upload(net, packed.data(), packed.size(), &out.w_up2_t))) return rc;
-            if (out.interleave && conv_wup2_shape_ok(cout, cin)) {
-                conv_pack_weights_wup2(w, cout, cin, packed);
-                if ((rc = upload(net, packed.data(), packed.size(), &out.w_wup2))) return rc;
-                conv_pack_weights_wup2(wt.data(), cout, cin, packed);
-                if ((rc = upload(net, packed.data(), packed.size(), &out.w_wup2_t))) return rc;
-            }
-        }
     }
+    if (ks != 3) out.img[1] = out.img[0];
     out.b = nullptr;
     if (!bname.empty()) {
         const float *b = wm.get(bname);
         IPDM_REQUIRE(b, "unet_create: missing parameter %s", bname.c_str());
-        rc = upload(net, b, cout, &out.b);
+        return upload(net, b, cout, &out.b);
     }
-    return rc;
+    return IPDM_OK;
 }
 
 int make_norm(ipdm_unet *net, const WeightMap &wm, const std::string &p, int ch, NormP &out)
@@ -742,8 +718,8 @@ struct Fwd {
                  const Tensor *res, int H, int W, float *ext_out = nullptr, bool want_stats = false,
                  const Tensor *sk_x1 = nullptr, const Tensor *sk_x2 = nullptr, const ConvP *sk = nullptr)
     {
-        const int pad = cp.ks / 2;
-        const int Ho = (H + 2 * pad - cp.ks) / stride + 1, Wo = (W + 2 * pad - cp.ks) / stride + 1;
+        ConvArgs a = conv_args(net->B, x1->C, x2 ? x2->C : 0, x1->H, x1->W, H, W, cp.cout, cp.ks, stride, cp.interleave, cp.cout_pad);
+        const int Ho = a.Ho, Wo = a.Wo;
         Tensor *o;
         if (ext_out) { o = new Tensor(); o->C = cp.cout; o->H = Ho; o->W = Wo; o->external = true; o->ext = ext_out; o->refs = 1; net->live.push_back(o); }
         else o = make(cp.cout, Ho, Wo);
@@ -751,16 +727,10 @@ struct Fwd {
         Tensor *lin1 = nullptr, *lin2 = linear_copy(x2), *linr = linear_copy(res);
         if (lin2) x2 = lin2;
         if (linr) res = linr;
-        ConvArgs a;
-        a.C1 = x1->C; a.C2 = x2 ? x2->C : 0; a.B = net->B; a.Hs = x1->H; a.Ws = x1->W; a.H = H; a.W = W;
-        a.upsample = (H != x1->H || W != x1->W); a.scale_y = (float)x1->H / (float)H; a.scale_x = (float)x1->W / (float)W;
-        a.w = net->transposed ? cp.w_t : cp.w; a.cout_pad = cp.cout_pad; a.w_interleave = cp.interleave; a.bias = bias; a.Cout = cp.cout; a.ksize = cp.ks; a.stride = stride;
-        a.Ho = Ho; a.Wo = Wo; a.act = act; a.gn_scale = net->gn_scale; a.gn_shift = net->gn_shift;
-        a.w_up2 = (ext_out && cp.interleave) ? nullptr : net->transposed ? cp.w_up2_t : cp.w_up2;      // (an external output is NCHW: no parity-planar form)
-        a.w_wup2 = net->transposed ? cp.w_wup2_t : cp.w_wup2;
-        a.w_wino = net->transposed ? cp.w_wino_t : cp.w_wino;
+        conv_set_images(a, cp.img[net->transposed ? 1 : 0]);
+        if (ext_out && cp.interleave) a.w_up2 = nullptr;      // (an external output is NCHW: no parity-planar form)
+        a.bias = bias; a.act = act; a.gn_scale = net->gn_scale; a.gn_shift = net->gn_shift;
         a.res = res ? (const float *)(uintptr_t)256 : nullptr;      // (the plan only asks whether it is null; addresses: below, not in dry runs)
-        a.x1 = a.x2 = nullptr; a.out = nullptr; a.tiles_x = a.tiles_y = a.co_tiles = 0;
         if (x1->planar && !conv_planar_ok(a)) x1 = lin1 = linear_copy(x1);
         a.x1_planar = x1->planar ? 1 : 0;
         Tensor *lins = sk ? linear_copy(sk_x2) : nullptr;
@@ -769,7 +739,7 @@ struct Fwd {
             lin_guard{*this, lin1, lin2, linr, lins};
         if (sk) {
             a.sk_C1 = sk_x1->C; a.sk_C2 = sk_x2 ? sk_x2->C : 0; a.sk_cout_pad = sk->cout_pad; a.sk_planar = sk_x1->planar ? 1 : 0;
-            a.sk_w = sk->w;
+            a.sk_w = sk->img[0].plain;
         }
         // the one decision: kernel, K split (layers with too few tiles to fill the chip, summed through a scratch buffer), statistics rows
         const ConvPlan plan = conv_plan(a, want_stats && !ext_out && !net->no_fused_stats, true);
@@ -812,10 +782,8 @@ struct Fwd {
         // narrow levels: the 1x1 shortcut rides on conv2 as extra K chunks over the block input (conv_direct.hip)
         bool fuse = false;
         if (rp.has_sc && rp.b2sc && rp.sc.interleave == 0 && (!x2 || !x2->planar)) {
-            ConvArgs q;
-            q.C1 = rp.c2.cin; q.C2 = 0; q.B = net->B; q.Cout = rp.c2.cout; q.ksize = 3; q.stride = 1; q.Ho = H; q.Wo = W; q.Hs = H; q.Ws = W; q.H = H; q.W = W;
-            q.upsample = 0; q.act = 2; q.res = nullptr; q.w_interleave = rp.c2.interleave; q.cout_pad = rp.c2.cout_pad; q.x1_planar = 0;
-            q.w_up2 = nullptr; q.w_wino = nullptr;
+            ConvArgs q = conv_args(net->B, rp.c2.cin, 0, H, W, H, W, rp.c2.cout, 3, 1, rp.c2.interleave, rp.c2.cout_pad);
+            q.act = 2;
             q.sk_C1 = x1->C; q.sk_C2 = x2 ? x2->C : 0; q.sk_cout_pad = rp.sc.cout_pad;
             fuse = conv_direct_skip_ok(q);
         }
@@ -1124,417 +1092,6 @@ extern "C" int ipdm_unet_forward_graph(ipdm_unet *net, const float *d_x, int32_t
     }
     IPDM_HIP_CHECK(hipGraphLaunch(exec, st));
     return IPDM_OK;
-}
-
-// the Winograd-domain weights of a test / benchmark layer, when its shape can use them (device pointer in *out, else null)
-static int upload_wino(const float *w_host, int Cout, int Cin, int ks, int stride, int interleave, float **out)
-{
-    *out = nullptr;
-    if (!conv_wino_shape_ok(Cout, Cin, ks, stride, interleave)) return IPDM_OK;
-    std::vector<float> u;
-    conv_pack_weights_wino(w_host, Cout, Cin, u);
-    IPDM_HIP_CHECK(hipMalloc((void **)out, u.size() * sizeof(float)));
-    IPDM_HIP_CHECK(hipMemcpy(*out, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice));
-    return IPDM_OK;
-}
-
-// ------------------------------------------------------------------------------------ op-level entry (tests)
-extern "C" int ipdm_op_conv2d(const float *d_x1, int32_t C1, const float *d_x2, int32_t C2, int32_t B, int32_t Hs, int32_t Ws,
-                              int32_t H, int32_t W, const float *w_host, const float *b_host, int32_t Cout, int32_t ksize,
-                              int32_t stride, int32_t act, int32_t groups, const float *gamma_host, const float *beta_host,
-                              const float *d_res, float *d_out, void *stream)
-{
-    IPDM_REQUIRE(d_x1 && w_host && d_out, "op_conv2d: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int Cin = C1 + C2;
-    std::vector<float> packed;
-    int cin_pad, cout_pad;
-    const int interleave = conv_weight_interleave(Cout, ksize, stride);
-    conv_pack_weights(w_host, Cout, Cin, ksize, interleave, packed, cin_pad, cout_pad);
-    float *d_w = nullptr, *d_b = nullptr, *d_g = nullptr, *d_be = nullptr, *d_sc = nullptr, *d_sh = nullptr, *d_split = nullptr, *d_wino = nullptr;
-    double *d_part = nullptr;
-    if (int rcw = upload_wino(w_host, Cout, Cin, ksize, stride, interleave, &d_wino)) return rcw;
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_w, packed.size() * sizeof(float)));
-    IPDM_HIP_CHECK(hipMemcpy(d_w, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (b_host) {
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_b, Cout * sizeof(float)));
-        IPDM_HIP_CHECK(hipMemcpy(d_b, b_host, Cout * sizeof(float), hipMemcpyHostToDevice));
-    }
-    int rc = IPDM_OK;
-    if (act) {
-        IPDM_REQUIRE(gamma_host && beta_host && groups > 0, "op_conv2d: GN prologue needs gamma/beta/groups");
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_g, Cin * sizeof(float)));
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_be, Cin * sizeof(float)));
-        IPDM_HIP_CHECK(hipMemcpy(d_g, gamma_host, Cin * sizeof(float), hipMemcpyHostToDevice));
-        IPDM_HIP_CHECK(hipMemcpy(d_be, beta_host, Cin * sizeof(float), hipMemcpyHostToDevice));
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_sc, ((size_t)B * Cin + 64) * sizeof(float)));      // (+ a K chunk of read-ahead,
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_sh, ((size_t)B * Cin + 64) * sizeof(float)));      //  zeroed: NaN * 0 weight = NaN)
-        IPDM_HIP_CHECK(hipMemsetAsync(d_sc + (size_t)B * Cin, 0, 64 * sizeof(float), st));
-        IPDM_HIP_CHECK(hipMemsetAsync(d_sh + (size_t)B * Cin, 0, 64 * sizeof(float), st));
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_part, gn_partials_bytes(B, groups)));
-        GnArgs g;
-        g.x1 = d_x1; g.x2 = d_x2; g.C1 = C1; g.C2 = C2; g.B = B; g.HW = (long)Hs * Ws; g.groups = groups;
-        g.gamma = d_g; g.beta = d_be; g.eps = 1e-5f; g.partials = d_part; g.scale = d_sc; g.shift = d_sh;
-        rc = gn_stats_launch(g, st);
-    }
-    if (!rc) {
-        const int pad = ksize / 2;
-        ConvArgs a;
-        a.x1 = d_x1; a.x2 = d_x2; a.C1 = C1; a.C2 = C2; a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W;
-        a.upsample = (H != Hs || W != Ws);
-        a.scale_y = (float)Hs / (float)H; a.scale_x = (float)Ws / (float)W;
-        a.w = d_w; a.w_wino = d_wino; a.cout_pad = cout_pad; a.w_interleave = interleave; a.bias = d_b; a.Cout = Cout; a.ksize = ksize; a.stride = stride;
-        a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
-        a.act = act; a.gn_scale = d_sc; a.gn_shift = d_sh; a.res = d_res; a.out = d_out;
-        a.tiles_x = a.tiles_y = a.co_tiles = 0;
-        if (const size_t bytes = conv_plan(a, false, true).split_ws_bytes) IPDM_HIP_CHECK(hipMalloc((void **)&d_split, bytes));
-        a.split_ws = d_split;
-        rc = conv2d_launch(a, st);
-    }
-    IPDM_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(d_split);
-    (void)hipFree(d_w); (void)hipFree(d_b); (void)hipFree(d_g); (void)hipFree(d_be); (void)hipFree(d_sc); (void)hipFree(d_sh); (void)hipFree(d_wino);
-    (void)hipFree(d_part);
-    return rc;
-}
-
-// x -> convA (+bias, +residual) -> GroupNorm(+SiLU) from convA's FUSED per-tile statistics -> convB 3x3: the
-// statistics hand-over between a producing convolution and the GroupNorm that follows it, as the executor wires it.
-// Test entry: Upsample (nearest 2x + 3x3 conv, in its parity form when eligible) -> GroupNorm(+SiLU) over cat(mid, skip)
-// -> conv B reading mid as stored (parity-planar after an up2 convolution).  d_mid receives mid as NCHW for checking.
-extern "C" int ipdm_op_up_conv_chain(const float *d_x, int32_t C, int32_t B, int32_t Hs, int32_t Ws, const float *wA_host,
-                                     const float *bA_host, int32_t CA, const float *d_skip, int32_t C2, int32_t groups,
-                                     const float *gamma_host, const float *beta_host, int32_t act, const float *wB_host,
-                                     const float *bB_host, int32_t CB, int32_t ksB, float *d_mid, float *d_out,
-                                     int32_t *used_up2, void *stream)
-{
-    IPDM_REQUIRE(d_x && wA_host && wB_host && gamma_host && beta_host && d_mid && d_out && groups > 0 && (C2 == 0 || d_skip),
-                 "op_up_conv_chain: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int H = 2 * Hs, W = 2 * Ws, Cc = CA + C2;
-    std::vector<float> pA, pU, pB, pW;
-    int cinp, coutpA, coutpB;
-    const int ilA = conv_weight_interleave(CA, 3, 1), ilB = conv_weight_interleave(CB, ksB, 1);
-    conv_pack_weights(wA_host, CA, C, 3, ilA, pA, cinp, coutpA);
-    if (ilA == 2 || ilA == 4 || (ilA == 0 && CA <= 16)) conv_pack_weights_up2(wA_host, CA, C, ilA, pU);
-    if (ilA && conv_wup2_shape_ok(CA, C)) conv_pack_weights_wup2(wA_host, CA, C, pW);
-    conv_pack_weights(wB_host, CB, Cc, ksB, ilB, pB, cinp, coutpB);
-    std::vector<void *> tofree;
-    auto dev = [&](const void *h, size_t bytes, void **out) -> int {
-        void *d = nullptr;
-        IPDM_HIP_CHECK(hipMalloc(&d, bytes ? bytes : 4));
-        if (h) IPDM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
-        else IPDM_HIP_CHECK(hipMemset(d, 0, bytes ? bytes : 4));      // (scale / shift read-ahead padding must not hold NaNs)
-        tofree.push_back(d);
-        *out = d;
-        return IPDM_OK;
-    };
-    float *d_wW = nullptr;
-    float *d_wA, *d_wU = nullptr, *d_wB, *d_bA = nullptr, *d_bB = nullptr, *d_g, *d_be, *d_sc, *d_sh, *d_stats = nullptr, *d_pl = nullptr, *d_lin = nullptr;
-    double *d_part;
-    int rc = dev(pA.data(), pA.size() * 4, (void **)&d_wA);
-    if (!rc && !pU.empty()) rc = dev(pU.data(), pU.size() * 4, (void **)&d_wU);
-    if (!rc && !pW.empty()) rc = dev(pW.data(), pW.size() * 4, (void **)&d_wW);
-    if (!rc) rc = dev(pB.data(), pB.size() * 4, (void **)&d_wB);
-    if (!rc && bA_host) rc = dev(bA_host, CA * 4, (void **)&d_bA);
-    if (!rc && bB_host) rc = dev(bB_host, CB * 4, (void **)&d_bB);
-    if (!rc) rc = dev(gamma_host, Cc * 4, (void **)&d_g);
-    if (!rc) rc = dev(beta_host, Cc * 4, (void **)&d_be);
-    if (!rc) rc = dev(nullptr, ((size_t)B * Cc + 64) * 4, (void **)&d_sc);
-    if (!rc) rc = dev(nullptr, ((size_t)B * Cc + 64) * 4, (void **)&d_sh);
-    if (!rc) rc = dev(nullptr, gn_partials_bytes(B, groups), (void **)&d_part);
-    if (!rc) rc = dev(nullptr, (size_t)B * CA * H * W * 4, (void **)&d_pl);
-    ConvArgs a;
-    a.x1 = d_x; a.x2 = nullptr; a.C1 = C; a.C2 = 0; a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.upsample = 1;
-    a.scale_y = (float)Hs / (float)H; a.scale_x = (float)Ws / (float)W; a.w = d_wA; a.w_up2 = d_wU; a.w_wup2 = d_wW; a.cout_pad = coutpA; a.w_interleave = ilA;
-    a.bias = d_bA; a.Cout = CA; a.ksize = 3; a.stride = 1; a.Ho = H; a.Wo = W; a.act = 0; a.gn_scale = a.gn_shift = nullptr; a.res = nullptr;
-    a.out = d_pl; a.tiles_x = a.tiles_y = a.co_tiles = 0;
-    const ConvPlan planA = conv_plan(a, C2 == 0, false);      // fused statistics when the GroupNorm covers mid alone
-    const bool up2 = planA.out_planar;
-    const int rows = planA.stats_rows;
-    // 1: four parity convolutions (conv_ws.hip); 2: the direct kernel's parity form (NCHW output); 3: the F(2x2,2x2) form of the wide layers (conv_wup2.hip)
-    if (used_up2) *used_up2 = !planA.up2 ? 0 : !up2 ? 2 : planA.code == 11 ? 3 : 1;
-    if (!rc && rows > 0) {
-        rc = dev(nullptr, (size_t)B * rows * CA * 2 * 4, (void **)&d_stats);
-        if (!rc) IPDM_HIP_CHECK(hipMemsetAsync(d_stats, 0xff, (size_t)B * rows * CA * 2 * 4, st));     // NaN: unwritten rows show
-        a.stats = d_stats; a.stats_rows = rows;
-    }
-    if (!rc) rc = conv2d_launch(a, st);
-    if (!rc && up2) rc = planar_to_linear_launch(d_pl, d_mid, (long)B * CA, H, W, st);
-    else if (!rc) IPDM_HIP_CHECK(hipMemcpyAsync(d_mid, d_pl, (size_t)B * CA * H * W * 4, hipMemcpyDeviceToDevice, st));
-    if (!rc && rows > 0) {
-        GnTileArgs g;
-        g.nsrc = 1; g.src[0].stats = d_stats; g.src[0].rows = rows; g.src[0].C = CA; g.B = B; g.HW = (long)H * W; g.groups = groups;
-        g.gamma = d_g; g.beta = d_be; g.eps = 1e-5f; g.partials = d_part; g.scale = d_sc; g.shift = d_sh;
-        rc = gn_tiles_launch(g, st);
-    } else if (!rc) {
-        GnArgs g;       // (sums over a plane: the parity-planar order of mid does not matter)
-        g.x1 = d_pl; g.x2 = d_skip; g.C1 = CA; g.C2 = C2; g.B = B; g.HW = (long)H * W; g.groups = groups; g.gamma = d_g; g.beta = d_be;
-        g.eps = 1e-5f; g.partials = d_part; g.scale = d_sc; g.shift = d_sh;
-        rc = gn_stats_launch(g, st);
-    }
-    if (!rc) {
-        ConvArgs b;
-        b.x1 = d_pl; b.x2 = d_skip; b.C1 = CA; b.C2 = C2; b.B = B; b.Hs = H; b.Ws = W; b.H = H; b.W = W; b.upsample = 0;
-        b.scale_y = b.scale_x = 1.f; b.w = d_wB; b.cout_pad = coutpB; b.w_interleave = ilB; b.bias = d_bB; b.Cout = CB; b.ksize = ksB;
-        b.stride = 1; b.Ho = H; b.Wo = W; b.act = act; b.gn_scale = d_sc; b.gn_shift = d_sh; b.res = nullptr; b.out = d_out;
-        b.tiles_x = b.tiles_y = b.co_tiles = 0;
-        float *d_wino = nullptr;
-        if (!rc) rc = upload_wino(wB_host, CB, Cc, ksB, 1, ilB, &d_wino);
-        if (d_wino) tofree.push_back(d_wino);
-        b.w_wino = d_wino;
-        if (up2 && !conv_planar_ok(b)) {      // a reader that takes NCHW only: convert, as the executor does
-            rc = dev(nullptr, (size_t)B * CA * H * W * 4, (void **)&d_lin);
-            if (!rc) rc = planar_to_linear_launch(d_pl, d_lin, (long)B * CA, H, W, st);
-            b.x1 = d_lin;
-        } else b.x1_planar = up2 ? 1 : 0;
-        const size_t split_bytes = conv_plan(b, false, true).split_ws_bytes;
-        if (!rc && split_bytes) { float *d_sp; rc = dev(nullptr, split_bytes, (void **)&d_sp); if (!rc) b.split_ws = d_sp; }
-        if (!rc) rc = conv2d_launch(b, st);
-    }
-    (void)hipStreamSynchronize(st);
-    for (void *d : tofree) (void)hipFree(d);
-    return rc;
-}
-
-extern "C" int ipdm_op_conv_gn_conv(const float *d_x, int32_t C, int32_t B, int32_t H, int32_t W, const float *wA_host,
-                                    const float *bA_host, int32_t CA, int32_t ksA, int32_t strideA, const float *d_resA,
-                                    int32_t groups, const float *gamma_host, const float *beta_host, int32_t act,
-                                    const float *wB_host, const float *bB_host, int32_t CB, float *d_mid, float *d_out,
-                                    int32_t *fused_rows, void *stream)
-{
-    IPDM_REQUIRE(d_x && wA_host && wB_host && gamma_host && beta_host && d_mid && d_out && groups > 0, "op_conv_gn_conv: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int padA = ksA / 2;
-    const int Hm = (H + 2 * padA - ksA) / strideA + 1, Wm = (W + 2 * padA - ksA) / strideA + 1;
-    std::vector<float> pA, pB;
-    int cinp, coutpA, coutpB;
-    const int ilA = conv_weight_interleave(CA, ksA, strideA), ilB = conv_weight_interleave(CB, 3, 1);
-    conv_pack_weights(wA_host, CA, C, ksA, ilA, pA, cinp, coutpA);
-    conv_pack_weights(wB_host, CB, CA, 3, ilB, pB, cinp, coutpB);
-    std::vector<void *> tofree;
-    auto dev = [&](const void *h, size_t bytes, void **out) -> int {
-        void *d = nullptr;
-        IPDM_HIP_CHECK(hipMalloc(&d, bytes ? bytes : 4));
-        if (h) IPDM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
-        else IPDM_HIP_CHECK(hipMemset(d, 0, bytes ? bytes : 4));      // (scale / shift read-ahead padding must not hold NaNs)
-        tofree.push_back(d);
-        *out = d;
-        return IPDM_OK;
-    };
-    float *d_wA, *d_wB, *d_bA = nullptr, *d_bB = nullptr, *d_g, *d_be, *d_sc, *d_sh, *d_stats = nullptr;
-    double *d_part;
-    int rc = dev(pA.data(), pA.size() * 4, (void **)&d_wA);
-    if (!rc) rc = dev(pB.data(), pB.size() * 4, (void **)&d_wB);
-    if (!rc && bA_host) rc = dev(bA_host, CA * 4, (void **)&d_bA);
-    if (!rc && bB_host) rc = dev(bB_host, CB * 4, (void **)&d_bB);
-    if (!rc) rc = dev(gamma_host, CA * 4, (void **)&d_g);
-    if (!rc) rc = dev(beta_host, CA * 4, (void **)&d_be);
-    if (!rc) rc = dev(nullptr, ((size_t)B * CA + 64) * 4, (void **)&d_sc);
-    if (!rc) rc = dev(nullptr, ((size_t)B * CA + 64) * 4, (void **)&d_sh);
-    if (!rc) rc = dev(nullptr, gn_partials_bytes(B, groups), (void **)&d_part);
-    ConvArgs a;
-    a.x1 = d_x; a.x2 = nullptr; a.C1 = C; a.C2 = 0; a.B = B; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.upsample = 0;
-    a.scale_y = a.scale_x = 1.f; a.w = d_wA; a.cout_pad = coutpA; a.w_interleave = ilA; a.bias = d_bA; a.Cout = CA; a.ksize = ksA;
-    a.stride = strideA; a.Ho = Hm; a.Wo = Wm; a.act = 0; a.gn_scale = a.gn_shift = nullptr; a.res = d_resA; a.out = d_mid;
-    a.tiles_x = a.tiles_y = a.co_tiles = 0;
-    float *d_winoA = nullptr, *d_winoB = nullptr;
-    if (!rc) rc = upload_wino(wA_host, CA, C, ksA, strideA, ilA, &d_winoA);
-    if (d_winoA) tofree.push_back(d_winoA);
-    if (!rc) rc = upload_wino(wB_host, CB, CA, 3, 1, ilB, &d_winoB);
-    if (d_winoB) tofree.push_back(d_winoB);
-    a.w_wino = d_winoA;
-    const ConvPlan planA = conv_plan(a, true, true);
-    if (!rc && planA.split_ws_bytes) { float *d_sp; rc = dev(nullptr, planA.split_ws_bytes, (void **)&d_sp); if (!rc) a.split_ws = d_sp; }
-    const int rows = planA.stats_rows;
-    if (fused_rows) *fused_rows = rows;
-    if (!rc && rows > 0) {
-        rc = dev(nullptr, (size_t)B * rows * CA * 2 * 4, (void **)&d_stats);
-        if (!rc) IPDM_HIP_CHECK(hipMemsetAsync(d_stats, 0xff, (size_t)B * rows * CA * 2 * 4, st));     // NaN: unwritten rows show
-        a.stats = d_stats; a.stats_rows = rows;
-    }
-    if (!rc) rc = conv2d_launch(a, st);
-    if (!rc && rows > 0) {
-        GnTileArgs g;
-        g.nsrc = 1; g.src[0].stats = d_stats; g.src[0].rows = rows; g.src[0].C = CA; g.B = B; g.HW = (long)Hm * Wm; g.groups = groups;
-        g.gamma = d_g; g.beta = d_be; g.eps = 1e-5f; g.partials = d_part; g.scale = d_sc; g.shift = d_sh;
-        rc = gn_tiles_launch(g, st);
-    } else if (!rc) {
-        GnArgs g;
-        g.x1 = d_mid; g.x2 = nullptr; g.C1 = CA; g.C2 = 0; g.B = B; g.HW = (long)Hm * Wm; g.groups = groups; g.gamma = d_g; g.beta = d_be;
-        g.eps = 1e-5f; g.partials = d_part; g.scale = d_sc; g.shift = d_sh;
-        rc = gn_stats_launch(g, st);
-    }
-    if (!rc) {
-        ConvArgs b;
-        b.x1 = d_mid; b.x2 = nullptr; b.C1 = CA; b.C2 = 0; b.B = B; b.Hs = Hm; b.Ws = Wm; b.H = Hm; b.W = Wm; b.upsample = 0;
-        b.scale_y = b.scale_x = 1.f; b.w = d_wB; b.cout_pad = coutpB; b.w_interleave = ilB; b.bias = d_bB; b.Cout = CB; b.ksize = 3;
-        b.stride = 1; b.Ho = Hm; b.Wo = Wm; b.act = act; b.gn_scale = d_sc; b.gn_shift = d_sh; b.res = nullptr; b.out = d_out;
-        b.tiles_x = b.tiles_y = b.co_tiles = 0;
-        b.w_wino = d_winoB;
-        rc = conv2d_launch(b, st);
-    }
-    (void)hipStreamSynchronize(st);
-    for (void *d : tofree) (void)hipFree(d);
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------ micro-benchmark entry
-// Times `iters` launches of one conv configuration on random data (kernel tuning; not on the product path).
-extern "C" int ipdm_bench_conv2d(int32_t B, int32_t C1, int32_t C2, int32_t H, int32_t W, int32_t Cout, int32_t ksize,
-                                 int32_t stride, int32_t act, int32_t with_res, int32_t iters, float *avg_ms)
-{
-    IPDM_REQUIRE(avg_ms && iters > 0, "bench_conv2d: bad argument");
-    const bool x1_planar = (act & 256) != 0;          // tuning aid: time the kernel's parity-planar reader path (x1 as an up2 output)
-    const bool up = (act & 512) != 0;                 // tuning aid: an Upsample layer (nearest 2x + 3x3) whose SOURCE is H x W
-    act &= 255;
-    IPDM_REQUIRE(!up || (ksize == 3 && stride == 1 && !C2 && !with_res && !act && !x1_planar), "bench_conv2d: bad Upsample configuration");
-    const int Cin = C1 + C2, pad = ksize / 2;
-    const int Hv = up ? 2 * H : H, Wv = up ? 2 * W : W;
-    const int Ho = (Hv + 2 * pad - ksize) / stride + 1, Wo = (Wv + 2 * pad - ksize) / stride + 1;
-    std::vector<float> w((size_t)Cout * Cin * ksize * ksize), packed;
-    for (size_t i = 0; i < w.size(); ++i) w[i] = (float)((i * 2654435761u) % 2001) / 1000.0f - 1.0f;
-    int cin_pad, cout_pad;
-    const int interleave = conv_weight_interleave(Cout, ksize, stride);
-    conv_pack_weights(w.data(), Cout, Cin, ksize, interleave, packed, cin_pad, cout_pad);
-    float *d_w, *d_x1, *d_x2 = nullptr, *d_out, *d_res = nullptr, *d_sc, *d_sh, *d_b, *d_wino = nullptr;
-    if (int rcw = upload_wino(w.data(), Cout, Cin, ksize, stride, interleave, &d_wino)) return rcw;
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_w, packed.size() * 4));
-    IPDM_HIP_CHECK(hipMemcpy(d_w, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_x1, (size_t)B * C1 * H * W * 4));
-    ipdm_randn(d_x1, B, (int64_t)C1 * H * W, 1, 0, 0, nullptr);
-    if (C2) { IPDM_HIP_CHECK(hipMalloc((void **)&d_x2, (size_t)B * C2 * H * W * 4)); ipdm_randn(d_x2, B, (int64_t)C2 * H * W, 2, 0, 0, nullptr); }
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_out, (size_t)B * Cout * Ho * Wo * 4));
-    if (with_res) { IPDM_HIP_CHECK(hipMalloc((void **)&d_res, (size_t)B * Cout * Ho * Wo * 4)); ipdm_randn(d_res, B, (int64_t)Cout * Ho * Wo, 3, 0, 0, nullptr); }
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_sc, ((size_t)B * Cin + 64) * 4));
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_sh, ((size_t)B * Cin + 64) * 4));
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_b, (size_t)Cout * 4));
-    IPDM_HIP_CHECK(hipMemset(d_sc + (size_t)B * Cin, 0, 64 * 4));
-    IPDM_HIP_CHECK(hipMemset(d_sh + (size_t)B * Cin, 0, 64 * 4));
-    ipdm_randn(d_sc, 1, (int64_t)B * Cin, 4, 0, 0, nullptr);
-    ipdm_randn(d_sh, 1, (int64_t)B * Cin, 5, 0, 0, nullptr);
-    ipdm_randn(d_b, 1, Cout, 6, 0, 0, nullptr);
-    float *d_wU = nullptr, *d_wW = nullptr;
-    if (up) {
-        std::vector<float> pk;
-        if (interleave == 2 || interleave == 4) {
-            conv_pack_weights_up2(w.data(), Cout, Cin, interleave, pk);
-            IPDM_HIP_CHECK(hipMalloc((void **)&d_wU, pk.size() * 4));
-            IPDM_HIP_CHECK(hipMemcpy(d_wU, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-            if (conv_wup2_shape_ok(Cout, Cin)) {
-                conv_pack_weights_wup2(w.data(), Cout, Cin, pk);
-                IPDM_HIP_CHECK(hipMalloc((void **)&d_wW, pk.size() * 4));
-                IPDM_HIP_CHECK(hipMemcpy(d_wW, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-            }
-        }
-    }
-    ConvArgs a;
-    a.x1 = d_x1; a.x2 = d_x2; a.C1 = C1; a.C2 = C2; a.B = B; a.Hs = H; a.Ws = W; a.H = Hv; a.W = Wv; a.upsample = up ? 1 : 0;
-    a.w_up2 = d_wU; a.w_wup2 = d_wW;
-    a.scale_y = a.scale_x = up ? 0.5f : 1.f; a.w = d_w; a.w_wino = d_wino; a.cout_pad = cout_pad; a.w_interleave = interleave; a.bias = d_b; a.Cout = Cout; a.ksize = ksize; a.stride = stride;
-    a.Ho = Ho; a.Wo = Wo; a.act = act; a.gn_scale = d_sc; a.gn_shift = d_sh; a.res = d_res; a.out = d_out;
-    a.tiles_x = a.tiles_y = a.co_tiles = 0;
-    if (x1_planar) { IPDM_REQUIRE(conv_planar_ok(a), "bench_conv2d: this shape has no parity-planar reader"); a.x1_planar = 1; }
-    float *d_split = nullptr, *d_stats = nullptr;
-    const ConvPlan plan = conv_plan(a, up, true);      // (every Upsample of the networks feeds a GroupNorm: timed with its fused statistics)
-    if (plan.split_ws_bytes) IPDM_HIP_CHECK(hipMalloc((void **)&d_split, plan.split_ws_bytes));
-    a.split_ws = d_split;
-    if (plan.stats_rows > 0) {
-        a.stats_rows = plan.stats_rows;
-        IPDM_HIP_CHECK(hipMalloc((void **)&d_stats, (size_t)B * a.stats_rows * Cout * 2 * 4));
-        a.stats = d_stats;
-    }
-    int rc = 0;
-    const bool stamps = (opt(OPT_CONV_DBG) & 24) != 0;
-    if (stamps) { IPDM_HIP_CHECK(hipMalloc((void **)&a.dbg_buf, 4096 * 8 * 8)); IPDM_HIP_CHECK(hipMemset(a.dbg_buf, 0, 4096 * 8 * 8)); }
-    for (int i = 0; i < 3 && !rc; ++i) rc = conv2d_launch(a, nullptr);
-    hipEvent_t e0, e1;
-    IPDM_HIP_CHECK(hipEventCreate(&e0));
-    IPDM_HIP_CHECK(hipEventCreate(&e1));
-    IPDM_HIP_CHECK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && !rc; ++i) rc = conv2d_launch(a, nullptr);
-    IPDM_HIP_CHECK(hipEventRecord(e1, nullptr));
-    IPDM_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    IPDM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    if (stamps) {   // consumer wave 0 of every workgroup: cycles in MFMA section / epilogue / barrier wait / total (last launch)
-        std::vector<unsigned long long> h(4096 * 8);
-        IPDM_HIP_CHECK(hipMemcpy(h.data(), a.dbg_buf, h.size() * 8, hipMemcpyDeviceToHost));
-        double s4[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nz = 0;
-        for (int g = 0; g < 4096; ++g) if (h[g * 8 + 3]) { for (int k = 0; k < 8; ++k) s4[k] += (double)h[g * 8 + k]; ++nz; }
-        if (nz) fprintf(stderr, "  stamps over %d workgroups (s_memtime ticks, avg): consumer mfma %.0f epilogue %.0f barrier %.0f total %.0f | "
-                        "producer issue %.0f wait %.0f math %.0f store %.0f\n", nz, s4[0] / nz, s4[1] / nz, s4[2] / nz, s4[3] / nz,
-                        s4[4] / nz, s4[5] / nz, s4[6] / nz, s4[7] / nz);
-        (void)hipFree(a.dbg_buf);
-    }
-    (void)hipFree(d_split);
-    (void)hipFree(d_wino);
-    (void)hipFree(d_wU); (void)hipFree(d_wW); (void)hipFree(d_stats);
-    (void)hipFree(d_w); (void)hipFree(d_x1); (void)hipFree(d_x2); (void)hipFree(d_out); (void)hipFree(d_res); (void)hipFree(d_sc);
-    (void)hipFree(d_sh); (void)hipFree(d_b); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
-}
-
-extern "C" int32_t ipdm_conv_layout_code(int32_t Cout, int32_t ksize, int32_t stride)
-{
-    return conv_weight_interleave(Cout, ksize, stride);
-}
-
-static int32_t conv_kernel_code_impl(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W, bool with_stats)
-{
-    if (B <= 0 || Cout <= 0 || Cin <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) || stride < 1 || stride > 2) return -1;
-    static float dummy;                    // (only tested for null by the eligibility rules)
-    const int pad = ksize / 2;
-    ConvArgs a;
-    a.x1 = &dummy; a.x2 = nullptr; a.C1 = Cin; a.C2 = 0; a.B = B; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.upsample = 0;
-    a.scale_y = a.scale_x = 1.f; a.w = &dummy; a.bias = nullptr; a.Cout = Cout; a.ksize = ksize; a.stride = stride;
-    a.w_interleave = conv_weight_interleave(Cout, ksize, stride);
-    const int group = a.w_interleave ? 32 * a.w_interleave : 64;      // (conv_pack_weights)
-    a.cout_pad = (Cout + group - 1) / group * group;
-    a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
-    a.act = 0; a.gn_scale = a.gn_shift = nullptr; a.res = nullptr; a.out = &dummy;
-    a.tiles_x = a.tiles_y = a.co_tiles = 0;
-    a.w_wino = conv_wino_shape_ok(Cout, Cin, ksize, stride, a.w_interleave) ? &dummy : nullptr;
-    return conv_plan(a, with_stats, true).code;
-}
-
-extern "C" int32_t ipdm_conv_kernel_code(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W)
-{
-    return conv_kernel_code_impl(B, Cout, Cin, ksize, stride, H, W, false);
-}
-// ... for a layer whose output feeds a GroupNorm (the executor asks it for fused statistics): the kernel rule of such a layer
-// looks at the layer alone, never at the batch (conv_pw.hip), so the answer can differ from the plain query's
-extern "C" int32_t ipdm_conv_kernel_code_stats(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W)
-{
-    return conv_kernel_code_impl(B, Cout, Cin, ksize, stride, H, W, true);
-}
-
-extern "C" int ipdm_bench_attention(int32_t B, int32_t heads, int32_t d, int32_t T, int32_t iters, float *avg_ms)
-{
-    IPDM_REQUIRE(avg_ms && iters > 0, "bench_attention: bad argument");
-    float *d_qkv, *d_out;
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_qkv, (size_t)B * heads * 3 * d * T * 4));
-    IPDM_HIP_CHECK(hipMalloc((void **)&d_out, (size_t)B * heads * d * T * 4));
-    ipdm_randn(d_qkv, B, (int64_t)heads * 3 * d * T, 9, 0, 0, nullptr);
-    int rc = 0;
-    float *d_scr = nullptr;
-    if (attention_scratch_floats(B, heads, d, T)) IPDM_HIP_CHECK(hipMalloc((void **)&d_scr, attention_scratch_floats(B, heads, d, T) * 4));
-    float *d_pl = nullptr;      // (the split pass runs inside every timed launch)
-    if (attention_planes_floats(B, heads, d, T)) IPDM_HIP_CHECK(hipMalloc((void **)&d_pl, attention_planes_floats(B, heads, d, T) * 4));
-    for (int i = 0; i < 2 && !rc; ++i) rc = attention_launch(d_qkv, d_out, B, heads, d, T, nullptr, d_scr, d_pl);
-    hipEvent_t e0, e1;
-    IPDM_HIP_CHECK(hipEventCreate(&e0));
-    IPDM_HIP_CHECK(hipEventCreate(&e1));
-    IPDM_HIP_CHECK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && !rc; ++i) rc = attention_launch(d_qkv, d_out, B, heads, d, T, nullptr, d_scr, d_pl);
-    IPDM_HIP_CHECK(hipEventRecord(e1, nullptr));
-    IPDM_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    IPDM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipFree(d_qkv); (void)hipFree(d_out); (void)hipFree(d_scr); (void)hipFree(d_pl); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
 }
 
 #if IPDM_UNET_TRACE == 2

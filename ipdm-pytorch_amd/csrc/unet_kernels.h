@@ -19,24 +19,26 @@ struct GnTileArgs {
     float *scale = nullptr, *shift = nullptr;        // [B, C1+C2]
 };
 
+// Every member has a default (null / 0 / scale 1), so a partially filled ConvArgs is a defined object; build one with conv_args()
+// (conv_layer.h), which derives the shape fields, then set the pointers.  The layout is ABI between the two libraries (optin.hip).
 struct ConvArgs {
-    const float *x1, *x2;        // sources [B,C1,Hs,Ws], [B,C2,Hs,Ws] (x2 may be null)
-    int C1, C2, B;
-    int Hs, Ws;                  // source spatial size
-    int H, W;                    // (virtual) conv-input size; != (Hs,Ws) => nearest up-sampling
-    int upsample;
-    float scale_y, scale_x;      // Hs/H, Ws/W in float32 (ATen's nearest rule)
-    const float *w;              // packed [Cin_pad][k*k][cout_pad]
-    int cout_pad;
+    const float *x1 = nullptr, *x2 = nullptr;        // sources [B,C1,Hs,Ws], [B,C2,Hs,Ws] (x2 may be null)
+    int C1 = 0, C2 = 0, B = 0;
+    int Hs = 0, Ws = 0;          // source spatial size
+    int H = 0, W = 0;            // (virtual) conv-input size; != (Hs,Ws) => nearest up-sampling
+    int upsample = 0;
+    float scale_y = 1.f, scale_x = 1.f;      // Hs/H, Ws/W in float32 (ATen's nearest rule)
+    const float *w = nullptr;    // packed [Cin_pad][k*k][cout_pad]
+    int cout_pad = 0;
     int w_interleave = 0;        // weight-slab layout chosen at pack time: 0 plain [cout], MB>0: cout-interleaved [32][MB] per 32*MB group
-    const float *bias;           // [Cout] or null
-    int Cout, ksize, stride;
-    int Ho, Wo;
-    int act;                     // 0 none, 1 GroupNorm, 2 GroupNorm+SiLU (prologue on the input)
-    const float *gn_scale, *gn_shift;   // [B, C1+C2]
-    const float *res;            // [B,Cout,Ho,Wo] or null
-    float *out;
-    int tiles_x, tiles_y, co_tiles;     // filled by the launcher
+    const float *bias = nullptr; // [Cout] or null
+    int Cout = 0, ksize = 0, stride = 0;
+    int Ho = 0, Wo = 0;
+    int act = 0;                 // 0 none, 1 GroupNorm, 2 GroupNorm+SiLU (prologue on the input)
+    const float *gn_scale = nullptr, *gn_shift = nullptr;   // [B, C1+C2]
+    const float *res = nullptr;  // [B,Cout,Ho,Wo] or null
+    float *out = nullptr;
+    int tiles_x = 0, tiles_y = 0, co_tiles = 0;     // filled by the launcher
     // Fused GroupNorm statistics of the OUTPUT (for the GroupNorm that follows this convolution): when non-null, every
     // (tile, consumer wave) / workgroup writes one row of per-channel partial sums {sum, sum of squares} of the final
     // output values it produced: stats[((n * stats_rows + row) * Cout + c) * 2 + {0,1}] (float32 partials over <= a few
