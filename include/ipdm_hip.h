@@ -43,7 +43,7 @@ int ipdm_abi_version(void);
  * as a debug alias) and changes only through this call afterwards.  Switches that shape packed weights or kernel choice
  * are recorded by ipdm_unet_create: a forward on a handle created under other values fails with IPDM_ERR_INVALID instead
  * of running on a mismatched layout; per-call switches (conv_no_up2, conv_no_wup2, conv_no_wino, conv_bf16x3, conv_no_pw, pw_item, pw_force, wino_v1, wino2_min_tiles, conv1x1_no_quarter, conv_nm, direct_no_skip_fuse, gn_unfused,
- * gn_two_stage, unet_transpose, attn_no_zseq, attn_exact_f32, attn_no_presplit, conv_dbg, art_per_view: every weight form they choose between is packed, the workspace
+ * gn_two_stage, unet_transpose, attn_no_zseq, attn_exact_f32, attn_no_presplit, attn_no_pipeline, conv_dbg, art_per_view: every weight form they choose between is packed, the workspace
  * need is re-queried per forward) may change under a live handle.  Returns IPDM_ERR_INVALID for an unknown name. */
 int ipdm_set_option(const char *name, int value);
 int ipdm_get_option(const char *name, int *value);

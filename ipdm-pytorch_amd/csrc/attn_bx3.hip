@@ -8,8 +8,14 @@
 // bf16 x bf16 product is exact in f32); the dropped terms a2b3 + a3b2 + a3b3 are below ~2^-23 |a b| and of either sign.
 //
 // Why: the f32 MFMA holds its SIMD's vector ALU for all its 64 cycles.  The 32x32x16 bf16 MFMA does 16x its work in 32
-// cycles and holds vector issue for 8 of them, so six of them cost 6/16 of the f32 MFMA time, and the softmax and the split of one
-// wave issue under the MFMAs of the other consumer wave on its SIMD.
+// cycles and holds vector issue for 8 of them, so six of them cost 6/16 of the f32 MFMA time, and vector work can issue in the other
+// 24.  The first loop (PIPE = false, kept as the bit oracle: option attn_no_pipeline) left that to chance: S, softmax + split and
+// P.V run one behind the other inside a wave, and the only vector work under an MFMA is that of the other consumer wave on the SIMD,
+// which belongs to another workgroup with nothing to align the two -- the counters of round 12 show more than 700 of 3380 SIMD cycles
+// per wave and tile in which neither pipe runs.  The pipelined loop (PIPE = true, the default with the planes) gives a wave its own
+// filler: the 24 MFMAs of S(it + 1) are issued with the softmax and the split of tile it in their gaps, then the 24 of P.V(it); K runs
+// one tile ahead of V through the LDS ring (attn_pipe_schedule.h).  Only independent instruction streams are interleaved: every
+// accumulator chain and every per-query operation keeps its order, so both loops give the same bits.
 //
 // Layout, per 32-key tile:
 //   * S[s, t] = sum_c K[c, s] Q[c, t]: A = K (key on the MFMA row), B = Q (query on the lane); k-step kb of lane half h contracts
@@ -31,6 +37,8 @@
 // the build refuses a packed f32 instruction whose low result reads a source's high half (tools/check_pk_cross_half.py).
 #include "unet_kernels.h"
 #include "attn_common.h"
+#include "attn_pipe_schedule.h"
+#include <type_traits>
 
 using namespace ipdm;
 using namespace ipdm::attn;
@@ -96,6 +104,16 @@ __device__ inline f32x16 mma6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 c
     return mma(a[0], b[0], c);
 }
 
+// f(integral_constant<int, I>) for I = FROM .. TO - 1, in order: the pipelined loop writes out its gaps with it
+template <int FROM, int TO, class F>
+__device__ inline void static_for(F &&f)
+{
+    if constexpr (FROM < TO) {
+        f(std::integral_constant<int, FROM>{});
+        static_for<FROM + 1, TO>(f);
+    }
+}
+
 // One 32-key tile of a (sample, head), split once for every query workgroup of the layer: K and V go through LDS as f32 (reads
 // coalesced along the keys, pitch 33: the transposed reads of K are conflict-free), every element through split3 -- the producers'
 // own function, so the three terms are their bits -- and out as whole 16-byte chunks, lane-linear.  Keys at or beyond T are written
@@ -138,13 +156,18 @@ __global__ void __launch_bounds__(256) attention_presplit_kernel(const float *__
 
 // ZSEQ: a workgroup walks all key slices of its queries (zseq > 1).  PRE: the producers copy the tile's planes from `planes`
 // (attention_presplit_kernel wrote them); else they split K and V themselves while staging (option attn_no_presplit: the bit oracle)
-template <bool ZSEQ, bool PRE>
+// PIPE (with PRE and without ZSEQ only): the pipelined loop of the header -- S(it + 1) with the softmax and split of tile it in its gaps, then P.V(it)
+template <bool ZSEQ, bool PRE, bool PIPE>
 __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__restrict__ qkv, float *__restrict__ out, int heads, int T,
                                                                 float scale, int zsplit, float *__restrict__ part, int zseq,
                                                                 const u32x4 *__restrict__ planes)
 {
     // zsplit > 1: blockIdx.z takes a slice of the key tiles and leaves its UNNORMALISED output, running maximum and sum in `part`
     // (attention_combine_kernel merges the slices); zseq > 1: this workgroup walks all zseq slices itself
+    static_assert(PRE || !PIPE, "the pipelined loop copies planes");
+    // (a workgroup that walks its slices holds their fold, 32 registers more: beside the next tile's scores that is 49 spilled
+    //  registers at 168, so the slice walk keeps the first loop)
+    static_assert(!ZSEQ || !PIPE, "the pipelined loop does not fit the slice walk's registers");
     __shared__ __attribute__((aligned(16))) unsigned short lds[2 * STAGE];
     const int bh = blockIdx.y;                      // sample*heads + head
     const int b = bh / heads, head = bh % heads;
@@ -153,6 +176,7 @@ __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__re
     const int nslice = ZSEQ ? zseq : zsplit;
     const int tps = 2 * (((T + 63) / 64 + nslice - 1) / nslice);      // tiles per slice (slices end where attn.hip's 64-key tiles do)
     const int it0 = ZSEQ ? 0 : blockIdx.z * tps, it1 = ZSEQ ? ntiles : min(ntiles, it0 + tps);
+    const int npipe = max(it1 - it0, 0);            // PIPE: the tiles of this walk (0: a slice with no tile behind its first boundary)
 
     // (a scalar branch: the producer code is not laid out behind the consumers' under an exec mask)
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= 4) {
@@ -184,6 +208,35 @@ __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__re
                     *reinterpret_cast<u32x4 *>(st + (i >> 1) * VPLANE + vo[i & 1]) = r[6 + i];
                 }
             };
+            if constexpr (PIPE) {
+                // K one tile ahead of V (attn_pipe_schedule.h): r[0..5] hold the K chunks, r[6..11] the V chunks of the NEXT hand-over
+                const auto load_half = [&](int it, int h) {
+#pragma unroll
+                    for (int i = 6 * h; i < 6 * h + 6; ++i)
+                        r[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16, (it * TILE_CHUNKS + 128 * i) * 16, 0));
+                };
+                const auto store_k = [&](int it) {
+                    unsigned short *st = lds + attn_pipe::slot(it) * STAGE;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) *reinterpret_cast<u32x4 *>(st + (i >> 1) * KPLANE + ko[i & 1]) = r[i];
+                };
+                const auto store_v = [&](int it) {
+                    unsigned short *st = lds + attn_pipe::slot(it) * STAGE;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) *reinterpret_cast<u32x4 *>(st + (i >> 1) * VPLANE + vo[i & 1]) = r[6 + i];
+                };
+                if (npipe > 0) load_half(attn_pipe::k_stored(it0, npipe, 0), 0);
+                for (int b = 0; b < attn_pipe::barriers(npipe); ++b) {
+                    const int ks = attn_pipe::k_stored(it0, npipe, b), vs = attn_pipe::v_stored(it0, npipe, b);
+                    if (ks != attn_pipe::NONE) store_k(ks);
+                    if (vs != attn_pipe::NONE) store_v(vs);
+                    const int kl = attn_pipe::k_loaded(it0, npipe, b), vl = attn_pipe::v_loaded(it0, npipe, b);
+                    if (kl != attn_pipe::NONE) load_half(kl, 0);
+                    if (vl != attn_pipe::NONE) load_half(vl, 1);
+                    __syncthreads();
+                }
+                return;
+            }
             if (it0 < it1) load(it0);
             for (int it = it0; it < it1; ++it) {
                 store(it);
@@ -298,7 +351,160 @@ __global__ void __launch_bounds__(384, 3) attention_bx3_kernel(const float *__re
         asm volatile("" ::"v"(v[0][0]), "v"(v[0][1]), "v"(v[0][2]), "v"(v[1][0]), "v"(v[1][1]), "v"(v[1][2]), "v"(pp[1][0]), "v"(pp[1][1]), "v"(pp[1][2]));
     };
 
-    for (int it = it0; it < it1; ++it) {
+    if constexpr (PIPE) {
+        // Interval b (behind barrier b): phase A, the 24 MFMAs of S(k_read) with the softmax of tile v_read and the split of its first
+        // slab in their gaps (the scores of v_read were phase A of interval b - 1); phase B, the 24 MFMAs of P.V(v_read), the split of
+        // the second slab under the first of them (all of it in phase A does not fit 168 registers beside the next scores and the K
+        // terms).  The first interval has phase A's MFMAs only, the last one no S.  The arithmetic of a tile is the first loop's,
+        // operation for operation.  The order is written out gap by gap and pinned (sched_barrier): left to itself the compiler issues
+        // the MFMAs of a phase in one bunch, and it drops a sched_group_barrier placement that raises its register estimate.
+        f32x16 sacc = {};                          // the scores of tile v_read
+        float mx_c = 0.0f, m_new_c = 0.0f, alpha_c = 1.0f;      // ... their row maximum, the running maximum with it, and the rescale factor
+        // (found one interval early, under the P.V MFMAs: the rescale of o is a branch, and it stands in front of the interval's block)
+        const auto row_max_alpha = [&]() {
+            mx_c = sacc[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mx_c = fmaxf(mx_c, sacc[r]);
+            mx_c = halves_max(mx_c);
+            m_new_c = fmaxf(m_run, mx_c);
+            // exactly 1 while the running max stands; m_run = -inf on the first tile -> 0
+            alpha_c = __builtin_amdgcn_exp2f((m_run - m_new_c) * LOG2E);
+        };
+        // The fillers are VALU writes right behind MFMAs, and a dead operand's registers are the first the allocator hands them: the
+        // 128-bit sources of the last two MFMAs stay reserved until two later MFMAs have been issued, or to the next barrier
+        // (tools/check_mfma_war.py; the precaution of conv_wino3.hip).  q never dies; ka: the K or V operands, pb: the P operands of
+        // MFMAs g - 1 and g - 2
+        u32x4 ka[2] = {}, pb[2] = {};
+        const auto interval = [&](auto has_s, auto has_pv, int b) {
+            constexpr bool HAS_S = decltype(has_s)::value, HAS_PV = decltype(has_pv)::value;
+            constexpr bool PIN = HAS_PV;
+            const int it = attn_pipe::v_read(it0, npipe, b), s0 = it * KT;
+            f32x16 snext;
+            u32x4 k[3], k0n;                       // the K terms of a slab; term 0 of the next one (read one slab early)
+            // (behind the barrier: no copy on the way from the last interval's MFMAs to it lands in their operands)
+            if constexpr (HAS_PV) asm volatile("" ::"v"(ka[0]), "v"(ka[1]), "v"(pb[0]), "v"(pb[1]));
+            const unsigned short *krow = lds + (HAS_S ? attn_pipe::slot(attn_pipe::k_read(it0, npipe, b)) : 0) * STAGE + l31 * KP + 8 * lh;
+            const auto kterm = [&](int p, int kb) { return *reinterpret_cast<const u32x4 *>(krow + p * KPLANE + 16 * kb); };
+            float rs0 = 0.0f, rs1 = 0.0f;
+            float ra[4], rb[4];                    // split3's first remainders of a slab's four pairs
+            unsigned h0[4];
+            // split3 in two steps (the same operations in the same order): pair i of slab kb
+            const auto split_a = [&](int kb, int i) {
+                const float x = sacc[8 * kb + 2 * i], y = sacc[8 * kb + 2 * i + 1];
+                h0[i] = pk_bf16(x, y);
+                ra[i] = x - __builtin_bit_cast(float, h0[i] << 16);
+                rb[i] = y - __builtin_bit_cast(float, h0[i] & 0xffff0000u);
+            };
+            const auto split_b = [&](int kb, int i) {
+                const unsigned h1 = pk_bf16(ra[i], rb[i]);
+                const float qa = ra[i] - __builtin_bit_cast(float, h1 << 16), qb = rb[i] - __builtin_bit_cast(float, h1 & 0xffff0000u);
+                pp[kb][0][i] = h0[i];
+                pp[kb][1][i] = h1;
+                pp[kb][2][i] = pk_bf16(qa, qb);
+            };
+            if constexpr (HAS_PV && !HAS_S) if (s0 + KT > T) {      // the ragged tile is the last of its walk: no S beside it
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (s0 + crow(r, lh) >= T) sacc[r] = -INFINITY;
+                row_max_alpha();                   // (again, of the masked scores)
+            }
+            const float m_new = m_new_c, alpha = alpha_c;
+            if constexpr (HAS_PV) {
+                // the running max settles after the first few tiles: skip the 32 multiplies by exactly 1.0 (wave-uniform)
+                if (__any(alpha != 1.0f)) {
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) o[cb][r] *= alpha;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (HAS_S) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p) k[p] = kterm(p, 0);
+            }
+            // ---- phase A, gap g: MFMA g of S (slab g / 6, product g % 6 of mma6's order), then a step of the online softmax
+            static_for<0, 24>([&](auto gc) {
+                constexpr int g = decltype(gc)::value, kb = g / 6, j = g % 6;
+                if constexpr (HAS_S) {
+                    constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
+                    if constexpr (g == 0) {
+                        const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                        snext = mma(k[0], q[0][2], zero);
+                        asm volatile("" ::"v"(k[0]), "v"(q[0][2]));
+                    } else {
+                        snext = mma(k[TA[j]], q[kb][TB[j]], snext);
+                    }
+                    if constexpr (g >= 2) asm volatile("" ::"v"(ka[g % 2]));
+                    ka[g % 2] = k[TA[j]];
+                    // the next slab's terms, each behind the last MFMA that reads the register it lands in
+                    if constexpr (kb < 3 && j == 1) { k[2] = kterm(2, kb + 1); k0n = kterm(0, kb + 1); }
+                    if constexpr (kb < 3 && j == 4) k[1] = kterm(1, kb + 1);
+                    if constexpr (kb < 3 && j == 5) k[0] = k0n;
+                }
+                if constexpr (HAS_PV) {
+                    if constexpr (g < 16) {                        // one exponential per gap
+                        sacc[g] = __builtin_amdgcn_exp2f((sacc[g] - m_new) * LOG2E);
+                        if constexpr (g % 2 == 0) rs0 += sacc[g]; else rs1 += sacc[g];
+                    } else if constexpr (g == 16) {
+                        const float rs = halves_sum(rs0 + rs1);
+                        l_run = l_run * alpha + rs;
+                        m_run = m_new;
+                    }
+                    // the first slab's split: pair i behind its second exponential (gap 2 i + 1)
+                    if constexpr (g >= 2 && g < 10 && g % 2 == 0) split_a(0, (g - 2) / 2);
+                    if constexpr (g >= 3 && g < 11 && g % 2 == 1) split_b(0, (g - 3) / 2);
+                }
+                if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+            });
+            if constexpr (HAS_PV) {
+                // ---- phase B, gap g: MFMA g of O[c, t] += sum_s V[c, s] P[s, t] -- slab g / 12, channel block (g / 6) % 2: slab 0 of
+                //      both blocks first, each block's chain keeps its slab order -- then a step of the second slab's split, or the next
+                //      tile's row maximum
+                const unsigned short *vt = lds + attn_pipe::slot(it) * STAGE + 3 * KPLANE + l31 * VP + 8 * lh;
+                const auto vterms = [&](int cb, int kb) {
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) v[cb][p] = *reinterpret_cast<const u32x4 *>(vt + cb * 32 * VP + p * VPLANE + 16 * kb);
+                };
+                vterms(0, 0);
+
+                static_for<0, 24>([&](auto gc) {
+                    constexpr int g = decltype(gc)::value, kb = g / 12, cb = (g / 6) % 2, j = g % 6;
+                    constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
+                    o[cb] = mma(v[cb][TA[j]], pp[kb][TB[j]], o[cb]);
+                    if constexpr (HAS_S || g >= 2) asm volatile("" ::"v"(ka[g % 2]));      // (g < 2: the last two K operands of phase A)
+                    if constexpr (g >= 2) asm volatile("" ::"v"(pb[g % 2]));
+                    ka[g % 2] = v[cb][TA[j]];
+                    pb[g % 2] = pp[kb][TB[j]];
+                    if constexpr (g == 2) vterms(1, 0);
+                    if constexpr (kb == 0 && j == 5) vterms(cb, 1);          // this block's second slab, behind its first one's last MFMA
+                    if constexpr (g < 8 && g % 2 == 0) split_a(1, g / 2);
+                    if constexpr (g < 8 && g % 2 == 1) split_b(1, g / 2);
+                    if constexpr (HAS_S && g == 12) { sacc = snext; row_max_alpha(); }
+                    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+                });
+                // (v and pp need no reserve here: the next thing is the barrier, or the epilogue's own reserve)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (HAS_S && !HAS_PV) {
+                sacc = snext;
+                row_max_alpha();
+            }
+        };
+        // attn_pipe::barriers(npipe) barriers, as the producers take: the first interval, the steady ones, the last.  (One loop that
+        // picks the interval's form behind a single barrier statement costs 32 spilled registers: the forms share no register plan.)
+        if (attn_pipe::barriers(npipe) > 0) {
+            __syncthreads();                       // hand-over 0: K(it0)
+            interval(std::true_type{}, std::false_type{}, 0);
+            for (int b = 1; b <= attn_pipe::steady(npipe); ++b) {
+                __syncthreads();                   // hand-over b: K(it0 + b) and V(it0 + b - 1)
+                interval(std::true_type{}, std::true_type{}, b);
+            }
+            __syncthreads();                       // the last hand-over: V(it1 - 1)
+            interval(std::false_type{}, std::true_type{}, attn_pipe::barriers(npipe) - 1);
+        }
+    } else
+    for (int it = it0; it < it1; ++it) {           // the first loop (PIPE = false)
         const int s0 = it * KT;
         __syncthreads();                           // hand-over: stage (it&1) is complete
         reserve();
@@ -426,12 +632,18 @@ void attention_bx3_launch(const float *qkv, float *out, int B, int heads, int T,
     const dim3 grid(cdiv(T, 128), B * heads, seq ? 1 : Z);
     u32x4 *pl = reinterpret_cast<u32x4 *>(planes);
     if (pl) hipLaunchKernelGGL(attention_presplit_kernel, dim3(cdiv(T, KT), B * heads), dim3(256), 0, st, qkv, pl, heads, T);
+    // (the planes path without the slice walk only: the in-kernel split and the walk keep the first loop)
+    const bool pipe = pl && !seq && !opt(OPT_ATTN_NO_PIPELINE);
+    const auto launch = [&](auto kernel, int zsplit, float *part, int zseq) {
+        hipLaunchKernelGGL(kernel, grid, dim3(384), 0, st, qkv, out, heads, T, scale, zsplit, part, zseq, pl);
+    };
     if (seq) {
-        if (pl) hipLaunchKernelGGL((attention_bx3_kernel<true, true>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, 1, (float *)nullptr, Z, pl);
-        else hipLaunchKernelGGL((attention_bx3_kernel<true, false>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, 1, (float *)nullptr, Z, pl);
+        if (pl) launch(attention_bx3_kernel<true, true, false>, 1, nullptr, Z);
+        else launch(attention_bx3_kernel<true, false, false>, 1, nullptr, Z);
     } else {
-        if (pl) hipLaunchKernelGGL((attention_bx3_kernel<false, true>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, Z, scratch, 1, pl);
-        else hipLaunchKernelGGL((attention_bx3_kernel<false, false>), grid, dim3(384), 0, st, qkv, out, heads, T, scale, Z, scratch, 1, pl);
+        if (pipe) launch(attention_bx3_kernel<false, true, true>, Z, scratch, 1);
+        else if (pl) launch(attention_bx3_kernel<false, true, false>, Z, scratch, 1);
+        else launch(attention_bx3_kernel<false, false, false>, Z, scratch, 1);
     }
 }
 

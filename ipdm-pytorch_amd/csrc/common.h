@@ -54,6 +54,7 @@ enum Opt {
     OPT_CONV_BF16X3,         // opt-in (round 6): conv_wino2's layers with the channel contraction on the bf16 matrix pipe, error-free 3-way split (conv_wino3.hip; per call)
     OPT_ATTN_EXACT_F32,      // d = 64 attention on the exact-f32 kernel (attention_ws_kernel) instead of the bf16 x 3 one (attn_bx3.hip; per call)
     OPT_ATTN_NO_PRESPLIT,    // attn_bx3's producers split K and V per tile themselves instead of copying the planes split once per layer (per call: the bit oracle)
+    OPT_ATTN_NO_PIPELINE,    // attn_bx3 on its first loop (S, softmax + split, P.V one behind the other) instead of the pipelined one (per call: the bit oracle)
     OPT_COUNT
 };
 int opt(Opt o);

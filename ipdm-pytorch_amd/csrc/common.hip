@@ -42,6 +42,7 @@ const OptDef g_opt_def[OPT_COUNT] = {
     {"conv_bf16x3", 0, true},
     {"attn_exact_f32", 0, true},
     {"attn_no_presplit", 0, true},
+    {"attn_no_pipeline", 0, true},
 };
 bool opt_value_ok(int i, int v)
 {
@@ -138,7 +139,7 @@ int device_cu_count()
 extern "C" const char *ipdm_last_error(void) { return ipdm::g_err; }
 extern "C" int ipdm_abi_version(void) { return IPDM_ABI_VERSION; }      // 2: ipdm_profile_end takes its array length; ipdm_conv_kernel_code  3: ipdm_profile_begin_classes  4: profile class 6 (IPDM_PROF_CLASSES 7); the split-bf16 switches are gone  5: profile class 7 (conv_wup2; IPDM_PROF_CLASSES 8), kernel code 11, option conv_no_wup2
 // (still 5: option attn_exact_f32 and attention kernel code 2 (attn_bx3.hip, the d = 64 default) changed no signature and no entry point;
-//  neither did option attn_no_presplit)
+//  neither did options attn_no_presplit and attn_no_pipeline)
 
 extern "C" int ipdm_set_option(const char *name, int value)
 {
