@@ -356,6 +356,37 @@ int ipdm_eps_loss(const ipdm_schedule *s, ipdm_unet *net, const float *d_x0, con
                   int32_t H, int32_t W, uint64_t seed, const int64_t *slice_ids, int64_t draw, const float *d_noise, void *d_ws,
                   size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ training convolutions ---- */
+/* nn.Conv2d under autograd (Model/model.py:40-45,100-118,139-143,160-187,224-281: every conv of the UNet; the backward is what
+ * loss.backward() runs at Utils/train_test_utils.py:268): the forward from DEVICE weights in the reference layout
+ * [Cout,Cin,k,k] -- they change every optimiser step, nothing is packed on the host --, the input gradient and the weight / bias
+ * gradient, NCHW float32, exact f32 on the f32 MFMA (csrc/conv_grad.hip).  ksize 1 or 3 with padding ksize/2; stride 1, or
+ * stride 2 with ksize 3 (Downsample); any Cin, Cout, H, W >= 1.  H and W are the INPUT's size; the output is
+ * Ho = (H + 2 (ksize/2) - ksize) / stride + 1 by Wo alike.  Every pointer is a device pointer.  IPDM_ABI_VERSION stays 5:
+ * additive entries, detected by symbol.
+ *
+ * Row b of ipdm_conv2d_fprop / ipdm_conv2d_dgrad depends on row b of the input alone and has the same bits for every B.
+ * ipdm_conv2d_wgrad cuts K = B*Ho*Wo into ipdm_conv2d_wgrad_slabs(B, Ho, Wo) slabs -- a function of those three numbers alone,
+ * never of the device -- whose float32 partial sums (in d_ws) a second launch folds in float64 in slab order, rounding once; the
+ * bias gradient (d_db, may be NULL) is a float64 sum in a fixed order.  No atomics: two calls give the same bits.
+ *
+ * d_ws: ipdm_conv2d_grad_workspace_bytes (the maximum over the three calls of one layer; 0 for arguments a call would refuse).
+ * Bad arguments -- a NULL pointer (d_b and d_db excepted), ksize not in {1,3}, stride not in {1,2}, stride 2 with ksize 1, a
+ * size < 1 -- return IPDM_ERR_INVALID, a short workspace IPDM_ERR_WORKSPACE, both before any launch. */
+size_t ipdm_conv2d_grad_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
+                                        int32_t stride);
+/* host-only plan query: the slab count of ipdm_conv2d_wgrad (>= 1; IPDM_ERR_INVALID for a size < 1) */
+int32_t ipdm_conv2d_wgrad_slabs(int32_t B, int32_t Ho, int32_t Wo);
+/* F.conv2d(x, w, b, stride, padding=ksize/2): d_x [B,Cin,H,W], d_w [Cout,Cin,k,k], d_b [Cout] or NULL -> d_y [B,Cout,Ho,Wo] */
+int ipdm_conv2d_fprop(const float *d_x, const float *d_w, const float *d_b, float *d_y, int32_t B, int32_t Cin, int32_t Cout,
+                      int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+/* the gradient w.r.t. the input: d_dy [B,Cout,Ho,Wo], d_w [Cout,Cin,k,k] -> d_dx [B,Cin,H,W] (every element written) */
+int ipdm_conv2d_dgrad(const float *d_dy, const float *d_w, float *d_dx, int32_t B, int32_t Cin, int32_t Cout, int32_t H,
+                      int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+/* the gradients w.r.t. weight and bias: d_x [B,Cin,H,W], d_dy [B,Cout,Ho,Wo] -> d_dw [Cout,Cin,k,k], d_db [Cout] or NULL */
+int ipdm_conv2d_wgrad(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
+                      int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+
 /* op-level entry points (parity tests of the individual kernels against torch-CPU ops) */
 /* F.conv2d(cat(x1,x2) [upsampled to H,W by nearest], w, b, stride, padding=k/2) with optional fused
  * GroupNorm(+SiLU) prologue over the concatenated input and optional residual add.

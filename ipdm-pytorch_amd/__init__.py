@@ -6,6 +6,7 @@ sampling hot path, behind the reference's own call surface.
   UNetModel.forward                                                  (Model/model.py:283-310)
   FBP.convert                                                        (Recon/FBP_kernel.py:86-122)
   add_noise / init_convertor / ldct_simulate                         (Utils/Low_dose_CT_simulate.py; simulate.py)
+  progressive_domain_denoiser.train                                  (Utils/train_test_utils.py:253-272; train.py: Trainer)
 
 All arithmetic runs in libipdm_hip.so (hand-written HIP, C ABI in include/ipdm_hip.h); torch is
 used for device memory, streams and torch.distributed only.  There is no CPU fallback.
@@ -21,6 +22,7 @@ _LAZY = {
     "GaussianDiffusion": "diffusion", "NoiseSource": "diffusion", "InjectedNoise": "diffusion",
     "UNetModel": "unet", "FBP": "fbp", "tensor_sharpen": "fbp",
     "add_noise": "simulate", "init_convertor": "simulate", "ldct_simulate": "simulate", "LowDoseSimulator": "simulate",
+    "conv2d": "train", "TrainUNet": "train", "Trainer": "train",
 }
 __all__ += list(_LAZY)
 

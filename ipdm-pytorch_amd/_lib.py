@@ -120,6 +120,11 @@ PROTOTYPES = {
     "ipdm_eps_loss_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "ipdm_eps_loss": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _vp, _i32, _i32, _i32, _u64, C.POINTER(_i64), _i64, _vp, _vp, _sz,
                                 _vp]),
+    "ipdm_conv2d_grad_workspace_bytes": (_sz, [_i32] * 7),
+    "ipdm_conv2d_wgrad_slabs": (_i32, [_i32, _i32, _i32]),
+    "ipdm_conv2d_fprop": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "ipdm_conv2d_dgrad": (C.c_int, [_vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "ipdm_conv2d_wgrad": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
     "ipdm_op_conv2d": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
                                  _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ipdm_op_conv_gn_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
