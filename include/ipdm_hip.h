@@ -614,6 +614,16 @@ int32_t ipdm_conv_kernel_code_stats(int32_t B, int32_t Cout, int32_t Cin, int32_
  * 1 = wave-specialised exact-f32 MFMA (d = 64 under the per-call option attn_exact_f32),
  * 2 = bf16 matrix pipe through an error-free 3-way split of every operand, f32 accumulate (attn_bx3.hip; the default for d = 64). */
 int32_t ipdm_attention_kernel_code(int32_t d);
+/* Everything the attention dispatcher decides for a launch of this shape NOW (options read at the call, the key-slice scratch
+ * buffer assumed present, as ipdm_op_attention and the UNet executor provide it); host code, answers without a device:
+ *   out[0] kernel family: 0 = attention_kernel (4 waves), 1 = attention_ws_kernel (exact f32), 2 = attention_bx3_kernel
+ *   out[1] 32-query tiles per wave (1 or 2)
+ *   out[2] key slices Z as launched (1 = none)
+ *   out[3] 0 = no slices, 1 = split grid + combine pass, 2 = a workgroup walks all slices of its queries
+ *   out[4] 64-key tiles per slice (the whole sequence when there are no slices)
+ *   out[5] empty slices: those z with z * out[4] >= ceil(T / 64)
+ * IPDM_ERR_UNSUPPORTED for a head dim other than 64 and 32.  Test aid: a test asserts the instantiation and form it covers. */
+int ipdm_attention_plan(int32_t B, int32_t heads, int32_t d, int32_t T, int32_t out[6]);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,7 @@ PROTOTYPES = {
     "ipdm_conv_kernel_code": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "ipdm_conv_kernel_code_stats": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "ipdm_attention_kernel_code": (_i32, [_i32]),
+    "ipdm_attention_plan": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32 * 6)]),
     "ipdm_art_plan_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "ipdm_art_plan_destroy": (C.c_int, [_vp]),
     "ipdm_art_workspace_bytes": (C.c_size_t, [_vp, _i32]),

@@ -39,7 +39,8 @@ constexpr int KV = 64;         // keys per LDS tile
 constexpr int KP = 68;         // K pitch  [s][c]  (16-byte aligned rows, conflict-free b128 reads)
 constexpr int VP = 68;         // V pitch  [c][s]
 
-template <int D, int QT>   // D: head dim C/heads (64 in both reference configs, 32 for reduced test nets); QT: 32-query tiles per wave
+template <int D, int QT>   // D: head dim C/heads (64 in both reference configs; 32 is what a network of 64 channels and 2 heads
+                           // has: unet_create accepts it, so a trained network can reach it); QT: 32-query tiles per wave
 __global__ void __launch_bounds__(256, 2) attention_kernel(const float *__restrict__ qkv, float *__restrict__ out,
                                                            int heads, int T, float scale)
 {
@@ -444,6 +445,48 @@ int attention_kv_split(int B, int heads, int d, int T)
     return Z < 2 ? 1 : Z;
 }
 
+// Everything attention_launch decides about a launch, in one place: the launch below and the query ipdm_attention_plan both read it,
+// so a test can assert the kernel and the form a shape takes.  (What attention_bx3_launch decides on its own -- planes, pipelined
+// loop -- changes no bit and is not part of it.)  d is 64 or 32 here.
+struct AttnPlan {
+    int family;     // 0 = attention_kernel, 1 = attention_ws_kernel, 2 = attention_bx3_kernel
+    int qt;         // 32-query tiles per wave
+    int Z;          // key slices as launched (1: none)
+    int form;       // 0 = no slices, 1 = split grid + combine pass, 2 = in-workgroup walk
+    int tps;        // 64-key tiles per slice
+    int empty;      // slices z with z * tps >= ntiles
+};
+
+AttnPlan attention_plan(int B, int heads, int d, int T, bool have_scratch)
+{
+    const int ntiles = cdiv(T, KV);
+    AttnPlan p = {0, 1, 1, 0, ntiles, 0};
+    if (d != 64) return p;                                   // attention_kernel<32, 1>
+    const long wg2 = (long)cdiv(T, 256) * B * heads, wg1 = (long)cdiv(T, 128) * B * heads;
+    if (opt(OPT_ATTN_LEGACY) != 0) {
+        p.qt = wg2 >= 512 && (wg2 % 512 == 0 || wg2 >= 4 * 512) ? 2 : 1;
+        return p;
+    }
+    const bool exact = opt(OPT_ATTN_EXACT_F32) != 0;
+    p.family = exact ? 1 : 2;
+    p.Z = have_scratch ? attention_kv_split(B, heads, d, T) : 1;
+    if (exact) {
+        // 64 queries per consumer wave (K/V operand reads shared by two query tiles) when the 256-query workgroups come in whole
+        // rounds of the CUs, else 32 (the key-slice form exists for 32-query waves)
+        const auto eff = [](long wg) { return (double)wg / (double)(((wg + 255) / 256) * 256); };    // round quantisation
+        if (p.Z == 1 && wg2 >= 256 && eff(wg2) >= eff(wg1) - 0.03) p.qt = 2;
+    }
+    if (p.Z > 1) {
+        // a sliced layer whose query workgroups fill the chip anyway (8 slices per GPU) walks its key slices inside the
+        // workgroup: same arithmetic as the split grid + combine pass, no partial outputs in memory
+        // (2 slices: the split grid + combine pass measured 3 % faster)
+        p.form = p.Z >= 4 && opt(OPT_ATTN_NO_ZSEQ) == 0 && wg1 >= 192 ? 2 : 1;
+        p.tps = cdiv(ntiles, p.Z);
+        p.empty = p.Z - cdiv(ntiles, p.tps);
+    }
+    return p;
+}
+
 }  // namespace
 
 namespace ipdm {
@@ -462,43 +505,30 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
     const float scale = (float)(1.0 / sqrt(sqrt((double)d)));
     const bool prof = prof_enabled();
     if (prof) prof_before(2, st);
-    const bool legacy = opt(OPT_ATTN_LEGACY) != 0;
-    const bool exact = opt(OPT_ATTN_EXACT_F32) != 0;
-    if (d == 64 && !legacy && !exact) {
+    const AttnPlan p = attention_plan(B, heads, d, T, scratch != nullptr);
+    const int Z = p.Z;
+    const bool seq = p.form == 2, q2 = p.qt == 2;
+    if (p.family == 2) {
         // bf16 matrix pipe, error-free 3-way split (attn_bx3.hip): the same key slices, and the same choice between the split grid +
         // combine pass and the in-workgroup walk, as the exact kernel below
-        const int Z = scratch ? attention_kv_split(B, heads, d, T) : 1;
-        const long wg1 = (long)cdiv(T, 128) * B * heads;
-        const bool seq = Z >= 4 && opt(OPT_ATTN_NO_ZSEQ) == 0 && wg1 >= 192;
         // the planes are used only where attention_planes_floats sized them (the same options, read here again: they are per call)
         if (!attention_planes_floats(B, heads, d, T)) planes = nullptr;
         attention_bx3_launch(qkv, out, B, heads, T, scale, Z, seq, scratch, planes, st);
-        if (Z > 1 && !seq)
+        if (p.form == 1)
             hipLaunchKernelGGL((attention_combine_kernel<64>), dim3(cdiv(T, 256), B * heads, 4), dim3(256), 0, st, scratch, out, T, Z, cdiv(T, KV));
-    } else if (d == 64 && !legacy) {
-        // wave-specialised kernel, one 512-thread workgroup per CU.  64 queries per consumer wave (K/V operand reads
-        // shared by two query tiles) when the 256-query workgroups come in whole rounds of the CUs, else 32
+    } else if (p.family == 1) {
+        // wave-specialised kernel, one 512-thread workgroup per CU
         constexpr size_t lds = (size_t)2 * (KV * KP + 64 * VP) * sizeof(float);
         if (int rc = ensure_dynamic_lds((const void *)attention_ws_kernel<64, 1>, lds)) return rc;
         if (int rc = ensure_dynamic_lds((const void *)attention_ws_kernel<64, 2>, lds)) return rc;
         if (int rc = ensure_dynamic_lds((const void *)attention_ws_kernel<64, 1, true>, lds)) return rc;
-        const long wg2 = (long)cdiv(T, 256) * B * heads, wg1 = (long)cdiv(T, 128) * B * heads;
-        const auto eff = [](long wg) { return (double)wg / (double)(((wg + 255) / 256) * 256); };    // round quantisation
-        const int Z = scratch ? attention_kv_split(B, heads, d, T) : 1;
-        const bool q2 = Z == 1 && wg2 >= 256 && eff(wg2) >= eff(wg1) - 0.03;     // (the key-slice form exists for 32-query waves)
-        // a sliced layer whose query workgroups fill the chip anyway (8 slices per GPU) walks its key slices inside the
-        // workgroup: same arithmetic as the split grid + combine pass, no partial outputs in memory
-        const bool no_seq = opt(OPT_ATTN_NO_ZSEQ) != 0;
-        const bool seq = Z >= 4 && !no_seq && wg1 >= 192;     // (2 slices: the split grid + combine pass measured 3 % faster)
         dim3 grid(cdiv(T, q2 ? 256 : 128), B * heads, seq ? 1 : Z);
         if (q2) hipLaunchKernelGGL((attention_ws_kernel<64, 2>), grid, dim3(512), lds, st, qkv, out, heads, T, scale, 1, (float *)nullptr, 1);
         else if (seq) hipLaunchKernelGGL((attention_ws_kernel<64, 1, true>), grid, dim3(512), lds, st, qkv, out, heads, T, scale, 1, (float *)nullptr, Z);
         else hipLaunchKernelGGL((attention_ws_kernel<64, 1>), grid, dim3(512), lds, st, qkv, out, heads, T, scale, Z, scratch, 1);
-        if (Z > 1 && !seq)
+        if (p.form == 1)
             hipLaunchKernelGGL((attention_combine_kernel<64>), dim3(cdiv(T, 256), B * heads, 4), dim3(256), 0, st, scratch, out, T, Z, cdiv(T, KV));
     } else if (d == 64) {
-        const long wg2 = (long)cdiv(T, 256) * B * heads;
-        const bool q2 = wg2 >= 512 && (wg2 % 512 == 0 || wg2 >= 4 * 512);
         dim3 grid(cdiv(T, q2 ? 256 : 128), B * heads);
         if (q2) hipLaunchKernelGGL((attention_kernel<64, 2>), grid, dim3(256), 0, st, qkv, out, heads, T, scale);
         else hipLaunchKernelGGL((attention_kernel<64, 1>), grid, dim3(256), 0, st, qkv, out, heads, T, scale);
@@ -515,8 +545,16 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
 
 extern "C" int32_t ipdm_attention_kernel_code(int32_t d)
 {
-    if (d != 64 || ipdm::opt(ipdm::OPT_ATTN_LEGACY)) return 0;
-    return ipdm::opt(ipdm::OPT_ATTN_EXACT_F32) ? 1 : 2;
+    return d == 64 ? attention_plan(1, 1, d, 1, true).family : 0;      // (the family looks at d and the options alone)
+}
+
+extern "C" int ipdm_attention_plan(int32_t B, int32_t heads, int32_t d, int32_t T, int32_t out[6])
+{
+    IPDM_REQUIRE(out && B > 0 && heads > 0 && T > 0, "attention_plan: bad argument");
+    if (d != 64 && d != 32) { ipdm::set_error("attention: head dim %d unsupported (kernel is specialised for 64 and 32)", d); return IPDM_ERR_UNSUPPORTED; }
+    const AttnPlan p = attention_plan(B, heads, d, T, true);
+    out[0] = p.family; out[1] = p.qt; out[2] = p.Z; out[3] = p.form; out[4] = p.tps; out[5] = p.empty;
+    return IPDM_OK;
 }
 
 extern "C" int ipdm_op_attention(const float *d_qkv, float *d_out, int32_t B, int32_t heads, int32_t d, int32_t T,
