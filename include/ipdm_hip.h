@@ -44,7 +44,9 @@ int ipdm_abi_version(void);
  * are recorded by ipdm_unet_create: a forward on a handle created under other values fails with IPDM_ERR_INVALID instead
  * of running on a mismatched layout; per-call switches (conv_no_up2, conv_no_wup2, conv_no_wino, conv_bf16x3, conv_no_pw, pw_item, pw_force, wino_v1, wino2_min_tiles, conv1x1_no_quarter, conv_nm, direct_no_skip_fuse, gn_unfused,
  * gn_two_stage, unet_transpose, attn_no_zseq, attn_exact_f32, attn_no_presplit, attn_no_pipeline, conv_dbg, art_per_view: every weight form they choose between is packed, the workspace
- * need is re-queried per forward) may change under a live handle.  Returns IPDM_ERR_INVALID for an unknown name. */
+ * need is re-queried per forward) may change under a live handle.  "gn_train_one_pass_max" (per call, 0 .. 16384, default 0 = the
+ * plan's own rule) is the largest group, in floats per sample and group, that the training normalisations (ipdm_gn_act_*) run in
+ * their one-pass form; no handle depends on it.  Returns IPDM_ERR_INVALID for an unknown name. */
 int ipdm_set_option(const char *name, int value);
 int ipdm_get_option(const char *name, int *value);
 
@@ -386,6 +388,47 @@ int ipdm_conv2d_dgrad(const float *d_dy, const float *d_w, float *d_dx, int32_t 
 /* the gradients w.r.t. weight and bias: d_x [B,Cin,H,W], d_dy [B,Cout,Ho,Wo] -> d_dw [Cout,Cin,k,k], d_db [Cout] or NULL */
 int ipdm_conv2d_wgrad(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
                       int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------ training normalisations ---- */
+/* GroupNorm (+ a per-(sample, channel) shift in front) (+ SiLU) under autograd, one fused operation with its backward
+ * (csrc/gn_grad.hip).  Replaces norm_layer (Model/model.py:69-90: nn.GroupNorm, eps 1e-5, affine) where the training step uses
+ * it: in front of both 3x3 convolutions of ResidualBlock -- the second one's input is conv1(x) + time_emb[:, :, None, None],
+ * the shift -- and in AttentionBlock (act = 0) (Model/model.py:95-155), and in front of `out` (Model/model.py:190-310); the
+ * backward is what loss.backward() runs through them.  NCHW float32, HW = H * W; group g holds the cpg = C / groups
+ * consecutive channels g cpg .., N = cpg HW.  IPDM_ABI_VERSION stays 5: additive entries, detected by symbol.
+ *
+ *   h = x + shift[b,c]   mean = sum h / N   var = sum h^2 / N - mean^2 (biased, clamped at 0)   rstd = 1 / sqrt(var + eps)
+ *   xhat = (h - mean) rstd   z = gamma[c] xhat + beta[c]   y = act ? z sigmoid(z) : z
+ *   gz = act ? dy s (1 + z (1 - s)) : dy   dx = rstd (gamma gz - mean_group(gamma gz) - xhat mean_group(gamma gz xhat))
+ *   dgamma[c] = sum_{b,pixels} gz xhat   dbeta[c] = sum_{b,pixels} gz   dshift[b,c] = sum_pixels dx
+ *
+ * Every sum over more than a wave's elements is float64 in a fixed order (no atomics: two calls give the same bits); h - mean
+ * is formed from the float64 mean.  ipdm_gn_act_fprop leaves (mean, rstd) per (sample, group) as float64 in d_stats
+ * [B][groups][2]; ipdm_gn_act_bgrad reads them and recomputes xhat, z and s from x, so x is the only tensor of the
+ * activation's size a caller keeps for the backward.  Row b of y, dx, dshift and stats depends on row b of the inputs alone and
+ * has the same bits for every B; dgamma / dbeta fold the per-sample totals in sample order.
+ *
+ * Two forms, chosen by ipdm_gn_act_plan from (C, groups, HW) alone: one pass (a workgroup keeps one (sample, group) in LDS; x,
+ * and in the backward x and dy, are read once) up to N = 8192, or up to the option gn_train_one_pass_max when it is not 0;
+ * above it the group is cut into `split` contiguous slices of 4 ceil(ceil(N / 4) / split) floats, one workgroup each, with
+ * float64 partials in d_ws.
+ *
+ * d_shift [B,C] may be NULL (no shift).  In ipdm_gn_act_bgrad a NULL d_dx / d_dgamma / d_dbeta / d_dshift means "not asked
+ * for" and what only feeds it is not launched.  d_ws: ipdm_gn_act_workspace_bytes under the options of the call (0 for
+ * arguments a call would refuse).  Bad arguments -- a NULL pointer otherwise, C % groups != 0, a size < 1, act not 0 or 1,
+ * d_dshift without d_shift -- return IPDM_ERR_INVALID, a short workspace IPDM_ERR_WORKSPACE, both before any launch. */
+size_t ipdm_gn_act_workspace_bytes(int32_t B, int32_t C, int32_t groups, int32_t HW);
+/* host-only plan query: 0 = one pass, 1 = split; *split (may be NULL) receives the slice count (1 for one pass, else 2..64);
+ * IPDM_ERR_INVALID for arguments a call would refuse */
+int32_t ipdm_gn_act_plan(int32_t C, int32_t groups, int32_t HW, int32_t *split);
+/* d_x [B,C,HW], d_shift [B,C] or NULL, d_gamma [C], d_beta [C] -> d_y [B,C,HW], d_stats [B,groups,2] (float64) */
+int ipdm_gn_act_fprop(const float *d_x, const float *d_shift, const float *d_gamma, const float *d_beta, float *d_y,
+                      double *d_stats, int32_t B, int32_t C, int32_t groups, int32_t HW, double eps, int32_t act, void *d_ws,
+                      size_t ws_bytes, void *stream);
+/* the forward's inputs and d_stats, d_dy [B,C,HW] -> d_dx [B,C,HW], d_dgamma [C], d_dbeta [C], d_dshift [B,C] (each or NULL) */
+int ipdm_gn_act_bgrad(const float *d_x, const float *d_shift, const float *d_gamma, const float *d_beta, const double *d_stats,
+                      const float *d_dy, float *d_dx, float *d_dgamma, float *d_dbeta, float *d_dshift, int32_t B, int32_t C,
+                      int32_t groups, int32_t HW, double eps, int32_t act, void *d_ws, size_t ws_bytes, void *stream);
 
 /* op-level entry points (parity tests of the individual kernels against torch-CPU ops) */
 /* F.conv2d(cat(x1,x2) [upsampled to H,W by nearest], w, b, stride, padding=k/2) with optional fused

@@ -55,6 +55,7 @@ enum Opt {
     OPT_ATTN_EXACT_F32,      // d = 64 attention on the exact-f32 kernel (attention_ws_kernel) instead of the bf16 x 3 one (attn_bx3.hip; per call)
     OPT_ATTN_NO_PRESPLIT,    // attn_bx3's producers split K and V per tile themselves instead of copying the planes split once per layer (per call: the bit oracle)
     OPT_ATTN_NO_PIPELINE,    // attn_bx3 on its first loop (S, softmax + split, P.V one behind the other) instead of the pipelined one (per call: the bit oracle)
+    OPT_GN_TRAIN_ONE_PASS_MAX,   // the largest group (floats per sample and group) the one-pass form of gn_grad.hip takes; 0 = the plan's own rule (per call)
     OPT_COUNT
 };
 int opt(Opt o);

@@ -2,13 +2,18 @@
 
   conv2d      nn.Conv2d's arithmetic under torch.autograd on the kernels of csrc/conv_grad.hip: the forward from device weights
               (ipdm_conv2d_fprop), the input gradient (ipdm_conv2d_dgrad) and the weight / bias gradient (ipdm_conv2d_wgrad).
+  group_norm_act   GroupNorm (+ the time-embedding add in front) (+ SiLU) as one operation under torch.autograd on the kernels
+              of csrc/gn_grad.hip (ipdm_gn_act_fprop / ipdm_gn_act_bgrad): it keeps x and two float64 numbers per (sample,
+              group) for the backward, where the torch ops keep three tensors of the activation's size.
   TrainUNet   the reference's UNetModel as a torch.nn.Module with the reference's state_dict() layout.  Every convolution goes
-              through conv2d (conv_backend="hip"); GroupNorm, SiLU, the time-embedding Linears, the attention core, the nearest
-              resize and the concatenations are torch ops for now.  conv_backend="torch" sends the convolutions through
-              F.conv2d as well: the A/B arm, and the only arm that runs on the CPU.
+              through conv2d (conv_backend="hip"); with norm_backend="hip" every GroupNorm (+SiLU) goes through group_norm_act
+              and the time embedding enters conv2's norm as its shift.  The time-embedding Linears, the attention core, the
+              nearest resize, the concatenations and, with norm_backend="torch" (the default), GroupNorm and SiLU are torch
+              ops.  conv_backend="torch" sends the convolutions through F.conv2d as well: the A/B arm, and with
+              norm_backend="torch" the only arm that runs on the CPU.
   Trainer     train() of the reference harness: q_sample at per-row timesteps, the epsilon loss, backward, Adam.
 
-A missing kernel is an error: conv_backend="hip" never falls back to F.conv2d.  The dataloader, fit(), tensorboard and EMA are not
+A missing kernel is an error: conv_backend="hip" never falls back to F.conv2d, norm_backend="hip" never to F.group_norm.  The dataloader, fit(), tensorboard and EMA are not
 here."""
 import collections
 import math
@@ -24,6 +29,7 @@ from ._lib import IpdmError, call, lib, ptr
 from .unet import UNetModel, make_cfg, param_shapes
 
 CONV_BACKENDS = ("hip", "torch")
+NORM_BACKENDS = ("torch", "hip")
 
 
 # ------------------------------------------------------------------------------------------------ convolution under autograd
@@ -90,6 +96,67 @@ def conv2d(x, w, b=None, stride=1):
     return _Conv2d.apply(x, w, b, int(stride))
 
 
+# ------------------------------------------------------------------------------------------------ GroupNorm (+SiLU) under autograd
+def _gn_workspace(geo, device):
+    need = lib().ipdm_gn_act_workspace_bytes(*geo)
+    if need == 0:
+        raise IpdmError("group_norm_act: %s" % lib().ipdm_last_error().decode())
+    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
+
+
+class _GroupNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, shift, groups, act, eps):
+        tensors = [t for t in (x, gamma, beta, shift) if t is not None]
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            raise IpdmError("group_norm_act runs on float32 GPU tensors only (no CPU fallback); got %s" %
+                            ", ".join("%s %s" % (t.device, t.dtype) for t in tensors))
+        if x.dim() < 2 or gamma.shape != (x.shape[1],) or beta.shape != (x.shape[1],) or \
+                (shift is not None and tuple(shift.shape) != tuple(x.shape[:2])):
+            raise ValueError("group_norm_act: x %s does not go with gamma %s, beta %s, shift %s" %
+                             (tuple(x.shape), tuple(gamma.shape), tuple(beta.shape), None if shift is None else tuple(shift.shape)))
+        x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
+        shift = None if shift is None else shift.contiguous()
+        B, C = int(x.shape[0]), int(x.shape[1])
+        geo = (B, C, int(groups), x.numel() // max(1, B * C))
+        y = torch.empty_like(x)
+        stats = torch.empty((B, max(1, int(groups)), 2), dtype=torch.float64, device=x.device)
+        with torch.cuda.device(x.device):
+            ws = _gn_workspace(geo, x.device)
+            call("ipdm_gn_act_fprop", ptr(x), ptr(shift), ptr(gamma), ptr(beta), ptr(y), ptr(stats), *geo, float(eps), int(act),
+                 ptr(ws), ws.numel(), _lib.current_stream())
+        ctx.save_for_backward(x, shift, gamma, beta, stats)
+        ctx.geo, ctx.act, ctx.eps = geo, int(act), float(eps)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, shift, gamma, beta, stats = ctx.saved_tensors
+        B, C = ctx.geo[:2]
+        dy = dy.contiguous()
+        need_x, need_g, need_b = ctx.needs_input_grad[:3]
+        need_s = shift is not None and ctx.needs_input_grad[3]
+        dx = torch.empty_like(x) if need_x else None
+        dg = torch.empty_like(gamma) if need_g else None
+        db = torch.empty_like(beta) if need_b else None
+        ds = torch.empty_like(shift) if need_s else None
+        if need_x or need_g or need_b or need_s:
+            with torch.cuda.device(x.device):
+                ws = _gn_workspace(ctx.geo, x.device)
+                call("ipdm_gn_act_bgrad", ptr(x), ptr(shift), ptr(gamma), ptr(beta), ptr(stats), ptr(dy), ptr(dx), ptr(dg), ptr(db),
+                     ptr(ds), *ctx.geo, ctx.eps, ctx.act, ptr(ws), ws.numel(), _lib.current_stream())
+        return dx, dg, db, ds, None, None, None
+
+
+def group_norm_act(x, gamma, beta, groups, shift=None, act=True, eps=1e-5):
+    """act(F.group_norm(x + shift[:, :, None, None], groups, gamma, beta, eps)) with act = SiLU or the identity, differentiable
+    once: one fused forward and one fused backward on torch's current stream (csrc/gn_grad.hip).  x [B, C, ...], shift [B, C]
+    or None (the ResidualBlock's time embedding: the sum is never formed).  Saved for the backward: x, shift, gamma, beta and
+    (mean, rstd) per (sample, group) in float64.  Only the gradients autograd asks for are computed."""
+    return _GroupNormAct.apply(x, gamma, beta, shift, int(groups), bool(act), float(eps))
+
+
 # ------------------------------------------------------------------------------------------------ the network
 def gn_groups(channels):
     """norm_layer's group count, Model/model.py:69-90: 32 when it divides, one group per channel below 32, else the divisor
@@ -142,17 +209,28 @@ def _norm(channels):
     return nn.GroupNorm(gn_groups(channels), channels)
 
 
+def _norm_act_conv(seq, x, shift=None):
+    """An nn.Sequential(GroupNorm, SiLU, Conv) with the first two as one group_norm_act call (the GroupNorm module holds the
+    parameters at its state_dict position)."""
+    gn = seq[0]
+    return seq[2](group_norm_act(x, gn.weight, gn.bias, gn.num_groups, shift=shift, act=True, eps=gn.eps))
+
+
 class ResBlock(nn.Module):
     """ResidualBlock, Model/model.py:95-130."""
 
-    def __init__(self, cin, cout, ted, backend):
+    def __init__(self, cin, cout, ted, backend, norm_backend="torch"):
         super().__init__()
+        self.norm_backend = norm_backend
         self.conv1 = nn.Sequential(_norm(cin), nn.SiLU(), Conv(cin, cout, 3, backend=backend))
         self.time_emb = nn.Sequential(nn.SiLU(), nn.Linear(ted, cout))
         self.conv2 = nn.Sequential(_norm(cout), nn.SiLU(), Conv(cout, cout, 3, backend=backend))
         self.shortcut = Conv(cin, cout, 1, backend=backend) if cin != cout else nn.Identity()
 
     def forward(self, x, emb):
+        if self.norm_backend == "hip":              # the time embedding is conv2's norm's shift: the sum is never formed
+            shift = self.time_emb(emb).expand(x.shape[0], -1)          # (one timestep for the whole batch: a [1, C] row)
+            return _norm_act_conv(self.conv2, _norm_act_conv(self.conv1, x), shift=shift) + self.shortcut(x)
         h = self.conv1(x) + self.time_emb(emb)[:, :, None, None]
         return self.conv2(h) + self.shortcut(x)
 
@@ -160,17 +238,22 @@ class ResBlock(nn.Module):
 class AttnBlock(nn.Module):
     """AttentionBlock, Model/model.py:135-155: qkv is chunked per head as (head, {q, k, v}, d)."""
 
-    def __init__(self, channels, heads, backend):
+    def __init__(self, channels, heads, backend, norm_backend="torch"):
         super().__init__()
         assert channels % heads == 0
-        self.heads = heads
+        self.heads, self.norm_backend = heads, norm_backend
         self.norm = _norm(channels)
         self.qkv = Conv(channels, 3 * channels, 1, bias=False, backend=backend)
         self.proj = Conv(channels, channels, 1, backend=backend)
 
     def forward(self, x):
         B, C, H, W = x.shape
-        q, k, v = self.qkv(self.norm(x)).reshape(B * self.heads, -1, H * W).chunk(3, dim=1)
+        if self.norm_backend == "hip":
+            n = self.norm
+            h = group_norm_act(x, n.weight, n.bias, n.num_groups, act=False, eps=n.eps)
+        else:
+            h = self.norm(x)
+        q, k, v = self.qkv(h).reshape(B * self.heads, -1, H * W).chunk(3, dim=1)
         scale = 1.0 / math.sqrt(math.sqrt(C // self.heads))
         p = torch.einsum("bct,bcs->bts", q * scale, k * scale).softmax(dim=-1)
         h = torch.einsum("bts,bcs->bct", p, v).reshape(B, -1, H, W)
@@ -212,11 +295,12 @@ class _Stage(nn.ModuleList):
 class TrainUNet(nn.Module):
     """UNetModel (Model/model.py:190-310) for training: the reference's constructor arguments, parameters with exactly the keys
     and shapes of unet.param_shapes(cfg) (the reference's state_dict() layout), forward(x, t) with t an int or a [B] tensor of
-    per-sample timesteps."""
+    per-sample timesteps.  norm_backend="hip" runs every GroupNorm (+SiLU) through group_norm_act; the nn.GroupNorm modules stay
+    where they are as the parameter holders, so the keys do not depend on it."""
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(8, 16),
                  dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True, num_heads=4, pre_downsample_times=1,
-                 conv_backend="hip"):
+                 conv_backend="hip", norm_backend="torch"):
         super().__init__()
         if dropout:
             raise NotImplementedError("dropout is never instantiated by the reference harness (Model/model.py:198)")
@@ -224,10 +308,13 @@ class TrainUNet(nn.Module):
             raise NotImplementedError("conv_resample=False (AvgPool down-sampling) is not on the reference's path")
         if conv_backend not in CONV_BACKENDS:
             raise ValueError("conv_backend must be one of %s, not %r" % (CONV_BACKENDS, conv_backend))
+        if norm_backend not in NORM_BACKENDS:
+            raise ValueError("norm_backend must be one of %s, not %r" % (NORM_BACKENDS, norm_backend))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks, self.num_heads = num_res_blocks, num_heads
         self.attention_resolutions, self.channel_mult = tuple(attention_resolutions), tuple(channel_mult)
         self.conv_backend = be = conv_backend
+        self.norm_backend = nb = norm_backend
         mc, ted = model_channels, model_channels * 4
         self.time_embed = nn.Sequential(nn.Linear(mc, ted), nn.SiLU(), nn.Linear(ted, ted))
         ch = int(self.channel_mult[0] * mc)
@@ -235,24 +322,24 @@ class TrainUNet(nn.Module):
         chans, ds, mults = [ch], 1, self.channel_mult[1:]
         for level, mult in enumerate(mults):
             for _ in range(num_res_blocks):
-                layers = [ResBlock(ch, int(mult * mc), ted, be)]
+                layers = [ResBlock(ch, int(mult * mc), ted, be, nb)]
                 ch = int(mult * mc)
                 if ds in self.attention_resolutions:
-                    layers.append(AttnBlock(ch, num_heads, be))
+                    layers.append(AttnBlock(ch, num_heads, be, nb))
                 self.down_blocks.append(_Stage(layers))
                 chans.append(ch)
             if level != len(mults) - 1:
                 self.down_blocks.append(_Stage([Down(ch, be)]))
                 chans.append(ch)
                 ds *= 2
-        self.middle_block = _Stage([ResBlock(ch, ch, ted, be), AttnBlock(ch, num_heads, be), ResBlock(ch, ch, ted, be)])
+        self.middle_block = _Stage([ResBlock(ch, ch, ted, be, nb), AttnBlock(ch, num_heads, be, nb), ResBlock(ch, ch, ted, be, nb)])
         self.up_blocks = nn.ModuleList()
         for level, mult in list(enumerate(mults))[::-1]:
             for i in range(num_res_blocks + 1):
-                layers = [ResBlock(ch + chans.pop(), int(mc * mult), ted, be)]
+                layers = [ResBlock(ch + chans.pop(), int(mc * mult), ted, be, nb)]
                 ch = int(mc * mult)
                 if ds in self.attention_resolutions:
-                    layers.append(AttnBlock(ch, num_heads, be))
+                    layers.append(AttnBlock(ch, num_heads, be, nb))
                 if level and i == num_res_blocks:
                     layers.append(Up(ch, be))
                     ds //= 2
@@ -287,7 +374,7 @@ class TrainUNet(nn.Module):
             if hs:
                 h_ = hs.pop()                       # Model/model.py:304-309: the size comes from the NEXT skip
             h = stage(cat_in, emb, (h_.shape[-2], h_.shape[-1]))
-        return self.out(h)
+        return _norm_act_conv(self.out, h) if self.norm_backend == "hip" else self.out(h)
 
 
 # ------------------------------------------------------------------------------------------------ the training step
@@ -296,7 +383,7 @@ class Trainer:
     network of opt's *_img / *_proj fields (num_res_blocks_<domain> / num_heads_<domain>, when opt has them, override the
     reference's constructor defaults 2 and 4), that domain's GaussianDiffusion, and Adam as the reference builds it."""
 
-    def __init__(self, opt, domain, seed=0, conv_backend="hip"):
+    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch"):
         from .diffusion import GaussianDiffusion, NoiseSource
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
@@ -308,7 +395,7 @@ class Trainer:
         self.device = torch.device(opt.device)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
-            self.model = TrainUNet(conv_backend=conv_backend, **kw).to(self.device)
+            self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
         self.optimizer = torch.optim.Adam(self.model.parameters(), lr=getattr(opt, "init_lr", 2e-4), weight_decay=1e-5,
