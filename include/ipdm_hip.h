@@ -430,6 +430,45 @@ int ipdm_gn_act_bgrad(const float *d_x, const float *d_shift, const float *d_gam
                       const float *d_dy, float *d_dx, float *d_dgamma, float *d_dbeta, float *d_dshift, int32_t B, int32_t C,
                       int32_t groups, int32_t HW, double eps, int32_t act, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ training attention ---- */
+/* The attention core of AttentionBlock (Model/model.py:148-153: einsum -> softmax -> einsum) under autograd, one fused
+ * operation with its backward (csrc/attn_grad.hip); the backward is what loss.backward() runs through it.  The layout of
+ * ipdm_op_attention: d_qkv [B, heads*3*d, T] float32, per head the rows (q: d, k: d, v: d), T contiguous; d_out
+ * [B, heads*d, T]; d_lse [B, heads, T].  Per (sample, head), with s = d^(-1/4):
+ *
+ *   S_ts = sum_c (s q_ct)(s k_cs)    P = softmax_s(S)    O_ct = sum_s P_ts v_cs    L_t = log sum_s exp(S_ts)
+ *   dV_cs = sum_t P_ts dO_ct         dP_ts = sum_c dO_ct v_cs    D_t = sum_c dO_ct O_ct
+ *   dS_ts = P_ts (dP_ts - D_t)       dq_ct = s^2 sum_s dS_ts k_cs    dk_cs = s^2 sum_t dS_ts q_ct
+ *
+ * Every contraction is exact f32 on the f32 MFMA with f32 accumulation (not the bf16 split of the inference kernels, which
+ * these entries leave untouched).  ipdm_attn_fprop is a flash-style loop over key tiles with a running maximum and sum; it
+ * leaves L in d_lse, and a caller keeps qkv, out and L for the backward -- nothing else.  A NULL d_lse means "no backward will
+ * follow": the statistics are not written and out has the same bits.  ipdm_attn_bgrad recomputes P = exp(S - L) tile by tile:
+ * no tensor with a T x T extent exists anywhere, the workspace (D_t: B*heads*T floats) included.  It writes every element of
+ * d_dqkv (the layout of d_qkv).
+ *
+ * No atomics and a fixed summation order: D_t is a float64 sum over c ascending; one launch gives each workgroup a key tile and
+ * walks the query tiles in ascending order (dK, dV), one gives each workgroup a query tile and walks the key tiles in ascending
+ * order (dQ).  Two calls give the same bits; row b of out, lse and dqkv depends on row b of the inputs alone and has the same
+ * bits for every B.
+ *
+ * Any 1 <= d <= 64 (zero-padded in LDS and registers to the width ipdm_attn_train_plan reports, never read from the
+ * neighbouring rows of qkv) and any T >= 1 (ragged tiles are masked and never stored; rows need no alignment).  Bad arguments
+ * -- a NULL pointer (d_lse of ipdm_attn_fprop excepted), a size < 1 -- return IPDM_ERR_INVALID, d > 64 IPDM_ERR_UNSUPPORTED, a
+ * short workspace (ipdm_attn_bgrad; the forward uses none) IPDM_ERR_WORKSPACE, all before any launch, with the text in
+ * ipdm_last_error.  IPDM_ABI_VERSION stays 5: additive entries, detected by symbol. */
+/* bytes of d_ws for the two calls of one layer; 0 for arguments a call refuses */
+size_t ipdm_attn_train_workspace_bytes(int32_t B, int32_t heads, int32_t d, int32_t T);
+/* host-only plan query: out = {padded head width, queries (keys) a workgroup owns, keys (queries) per streamed tile, streamed
+ * tiles per sequence}; the status of a call with the same d and T */
+int32_t ipdm_attn_train_plan(int32_t d, int32_t T, int32_t out[4]);
+/* d_qkv [B, heads*3*d, T] -> d_out [B, heads*d, T], d_lse [B, heads, T] or NULL */
+int ipdm_attn_fprop(const float *d_qkv, float *d_out, float *d_lse, int32_t B, int32_t heads, int32_t d, int32_t T, void *d_ws,
+                    size_t ws_bytes, void *stream);
+/* the forward's d_qkv, d_out and d_lse, d_dout [B, heads*d, T] -> d_dqkv [B, heads*3*d, T] */
+int ipdm_attn_bgrad(const float *d_qkv, const float *d_out, const float *d_lse, const float *d_dout, float *d_dqkv, int32_t B,
+                    int32_t heads, int32_t d, int32_t T, void *d_ws, size_t ws_bytes, void *stream);
+
 /* op-level entry points (parity tests of the individual kernels against torch-CPU ops) */
 /* F.conv2d(cat(x1,x2) [upsampled to H,W by nearest], w, b, stride, padding=k/2) with optional fused
  * GroupNorm(+SiLU) prologue over the concatenated input and optional residual add.

@@ -129,6 +129,10 @@ PROTOTYPES = {
     "ipdm_gn_act_plan": (_i32, [_i32, _i32, _i32, C.POINTER(_i32)]),
     "ipdm_gn_act_fprop": (C.c_int, [_vp] * 6 + [_i32] * 4 + [_f64, _i32, _vp, _sz, _vp]),
     "ipdm_gn_act_bgrad": (C.c_int, [_vp] * 10 + [_i32] * 4 + [_f64, _i32, _vp, _sz, _vp]),
+    "ipdm_attn_train_workspace_bytes": (_sz, [_i32] * 4),
+    "ipdm_attn_train_plan": (_i32, [_i32, _i32, C.POINTER(_i32 * 4)]),
+    "ipdm_attn_fprop": (C.c_int, [_vp] * 3 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "ipdm_attn_bgrad": (C.c_int, [_vp] * 5 + [_i32] * 4 + [_vp, _sz, _vp]),
     "ipdm_op_conv2d": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
                                  _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ipdm_op_conv_gn_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp,

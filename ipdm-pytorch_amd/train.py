@@ -5,15 +5,20 @@
   group_norm_act   GroupNorm (+ the time-embedding add in front) (+ SiLU) as one operation under torch.autograd on the kernels
               of csrc/gn_grad.hip (ipdm_gn_act_fprop / ipdm_gn_act_bgrad): it keeps x and two float64 numbers per (sample,
               group) for the backward, where the torch ops keep three tensors of the activation's size.
+  attention   the attention core (einsum -> softmax -> einsum of AttentionBlock) as one operation under torch.autograd on the
+              kernels of csrc/attn_grad.hip (ipdm_attn_fprop / ipdm_attn_bgrad): it keeps qkv, its output and one float per
+              (sample, head, query) for the backward, where the torch ops keep the [B heads, T, T] probability matrix.
   TrainUNet   the reference's UNetModel as a torch.nn.Module with the reference's state_dict() layout.  Every convolution goes
               through conv2d (conv_backend="hip"); with norm_backend="hip" every GroupNorm (+SiLU) goes through group_norm_act
-              and the time embedding enters conv2's norm as its shift.  The time-embedding Linears, the attention core, the
-              nearest resize, the concatenations and, with norm_backend="torch" (the default), GroupNorm and SiLU are torch
+              and the time embedding enters conv2's norm as its shift; with attn_backend="hip" every attention core goes
+              through attention.  The time-embedding Linears, the nearest resize, the concatenations and, with
+              norm_backend="torch" / attn_backend="torch" (the defaults), GroupNorm, SiLU and the attention core are torch
               ops.  conv_backend="torch" sends the convolutions through F.conv2d as well: the A/B arm, and with
-              norm_backend="torch" the only arm that runs on the CPU.
+              norm_backend="torch" and attn_backend="torch" the only arm that runs on the CPU.
   Trainer     train() of the reference harness: q_sample at per-row timesteps, the epsilon loss, backward, Adam.
 
-A missing kernel is an error: conv_backend="hip" never falls back to F.conv2d, norm_backend="hip" never to F.group_norm.  The dataloader, fit(), tensorboard and EMA are not
+A missing kernel is an error: conv_backend="hip" never falls back to F.conv2d, norm_backend="hip" never to F.group_norm,
+attn_backend="hip" never to the einsums.  The dataloader, fit(), tensorboard and EMA are not
 here."""
 import collections
 import math
@@ -30,6 +35,7 @@ from .unet import UNetModel, make_cfg, param_shapes
 
 CONV_BACKENDS = ("hip", "torch")
 NORM_BACKENDS = ("torch", "hip")
+ATTN_BACKENDS = ("torch", "hip")
 
 
 # ------------------------------------------------------------------------------------------------ convolution under autograd
@@ -157,6 +163,54 @@ def group_norm_act(x, gamma, beta, groups, shift=None, act=True, eps=1e-5):
     return _GroupNormAct.apply(x, gamma, beta, shift, int(groups), bool(act), float(eps))
 
 
+# ------------------------------------------------------------------------------------------------ the attention core under autograd
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads, grad_mode):
+        if not (qkv.is_cuda and qkv.dtype == torch.float32):
+            raise IpdmError("attention runs on float32 GPU tensors only (no CPU fallback); got %s %s" % (qkv.device, qkv.dtype))
+        if qkv.dim() not in (3, 4) or heads < 1 or qkv.shape[1] % (3 * heads):
+            raise ValueError("attention: qkv %s does not go with %d heads ([B, 3C, T] or [B, 3C, H, W], C a multiple of heads)"
+                             % (tuple(qkv.shape), heads))
+        qkv = qkv.contiguous()
+        B, d = int(qkv.shape[0]), int(qkv.shape[1]) // (3 * heads)
+        geo = (B, int(heads), d, qkv.numel() // max(1, B * 3 * heads * d))
+        out = torch.empty((B, heads * d) + tuple(qkv.shape[2:]), dtype=torch.float32, device=qkv.device)
+        keep = grad_mode and ctx.needs_input_grad[0]           # else no backward will follow: the statistics are not written
+        lse = torch.empty((B, heads, geo[3]), dtype=torch.float32, device=qkv.device) if keep else None
+        with torch.cuda.device(qkv.device):
+            call("ipdm_attn_fprop", ptr(qkv), ptr(out), ptr(lse), *geo, None, 0, _lib.current_stream())
+        if keep:
+            ctx.save_for_backward(qkv, out, lse)
+        ctx.geo = geo
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        qkv, out, lse = ctx.saved_tensors
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        with torch.cuda.device(qkv.device):
+            need = lib().ipdm_attn_train_workspace_bytes(*ctx.geo)
+            if need == 0:
+                raise IpdmError("attention: %s" % lib().ipdm_last_error().decode())
+            ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)       # torch's caching allocator
+            call("ipdm_attn_bgrad", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), *ctx.geo, ptr(ws), ws.numel(),
+                 _lib.current_stream())
+        return dqkv, None, None
+
+
+def attention(qkv, heads):
+    """The attention core of AttentionBlock: qkv [B, 3C, T] or [B, 3C, H, W], per head the rows (q: d, k: d, v: d), ->
+    softmax_s((s q)^T (s k)) v with s = d^(-1/4), [B, C, T] or [B, C, H, W]; differentiable once: one fused forward and a
+    three-launch backward on torch's current stream (csrc/attn_grad.hip).  Saved for the backward: qkv, the output (the tensor
+    the proj convolution keeps as well) and log-sum-exp per (sample, head, query) -- no [T, T] tensor exists."""
+    return _Attention.apply(qkv, int(heads), torch.is_grad_enabled())          # (inside forward() the grad mode is always off)
+
+
 # ------------------------------------------------------------------------------------------------ the network
 def gn_groups(channels):
     """norm_layer's group count, Model/model.py:69-90: 32 when it divides, one group per channel below 32, else the divisor
@@ -238,10 +292,10 @@ class ResBlock(nn.Module):
 class AttnBlock(nn.Module):
     """AttentionBlock, Model/model.py:135-155: qkv is chunked per head as (head, {q, k, v}, d)."""
 
-    def __init__(self, channels, heads, backend, norm_backend="torch"):
+    def __init__(self, channels, heads, backend, norm_backend="torch", attn_backend="torch"):
         super().__init__()
         assert channels % heads == 0
-        self.heads, self.norm_backend = heads, norm_backend
+        self.heads, self.norm_backend, self.attn_backend = heads, norm_backend, attn_backend
         self.norm = _norm(channels)
         self.qkv = Conv(channels, 3 * channels, 1, bias=False, backend=backend)
         self.proj = Conv(channels, channels, 1, backend=backend)
@@ -253,6 +307,8 @@ class AttnBlock(nn.Module):
             h = group_norm_act(x, n.weight, n.bias, n.num_groups, act=False, eps=n.eps)
         else:
             h = self.norm(x)
+        if self.attn_backend == "hip":              # the qkv convolution's output as it is: no chunk, no scaled copies, no [T, T]
+            return self.proj(attention(self.qkv(h), self.heads)) + x
         q, k, v = self.qkv(h).reshape(B * self.heads, -1, H * W).chunk(3, dim=1)
         scale = 1.0 / math.sqrt(math.sqrt(C // self.heads))
         p = torch.einsum("bct,bcs->bts", q * scale, k * scale).softmax(dim=-1)
@@ -296,11 +352,12 @@ class TrainUNet(nn.Module):
     """UNetModel (Model/model.py:190-310) for training: the reference's constructor arguments, parameters with exactly the keys
     and shapes of unet.param_shapes(cfg) (the reference's state_dict() layout), forward(x, t) with t an int or a [B] tensor of
     per-sample timesteps.  norm_backend="hip" runs every GroupNorm (+SiLU) through group_norm_act; the nn.GroupNorm modules stay
-    where they are as the parameter holders, so the keys do not depend on it."""
+    where they are as the parameter holders, so the keys do not depend on it.  attn_backend="hip" runs every attention core
+    through attention; it has no parameters of its own."""
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(8, 16),
                  dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True, num_heads=4, pre_downsample_times=1,
-                 conv_backend="hip", norm_backend="torch"):
+                 conv_backend="hip", norm_backend="torch", attn_backend="torch"):
         super().__init__()
         if dropout:
             raise NotImplementedError("dropout is never instantiated by the reference harness (Model/model.py:198)")
@@ -310,11 +367,14 @@ class TrainUNet(nn.Module):
             raise ValueError("conv_backend must be one of %s, not %r" % (CONV_BACKENDS, conv_backend))
         if norm_backend not in NORM_BACKENDS:
             raise ValueError("norm_backend must be one of %s, not %r" % (NORM_BACKENDS, norm_backend))
+        if attn_backend not in ATTN_BACKENDS:
+            raise ValueError("attn_backend must be one of %s, not %r" % (ATTN_BACKENDS, attn_backend))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks, self.num_heads = num_res_blocks, num_heads
         self.attention_resolutions, self.channel_mult = tuple(attention_resolutions), tuple(channel_mult)
         self.conv_backend = be = conv_backend
         self.norm_backend = nb = norm_backend
+        self.attn_backend = ab = attn_backend
         mc, ted = model_channels, model_channels * 4
         self.time_embed = nn.Sequential(nn.Linear(mc, ted), nn.SiLU(), nn.Linear(ted, ted))
         ch = int(self.channel_mult[0] * mc)
@@ -325,21 +385,21 @@ class TrainUNet(nn.Module):
                 layers = [ResBlock(ch, int(mult * mc), ted, be, nb)]
                 ch = int(mult * mc)
                 if ds in self.attention_resolutions:
-                    layers.append(AttnBlock(ch, num_heads, be, nb))
+                    layers.append(AttnBlock(ch, num_heads, be, nb, ab))
                 self.down_blocks.append(_Stage(layers))
                 chans.append(ch)
             if level != len(mults) - 1:
                 self.down_blocks.append(_Stage([Down(ch, be)]))
                 chans.append(ch)
                 ds *= 2
-        self.middle_block = _Stage([ResBlock(ch, ch, ted, be, nb), AttnBlock(ch, num_heads, be, nb), ResBlock(ch, ch, ted, be, nb)])
+        self.middle_block = _Stage([ResBlock(ch, ch, ted, be, nb), AttnBlock(ch, num_heads, be, nb, ab), ResBlock(ch, ch, ted, be, nb)])
         self.up_blocks = nn.ModuleList()
         for level, mult in list(enumerate(mults))[::-1]:
             for i in range(num_res_blocks + 1):
                 layers = [ResBlock(ch + chans.pop(), int(mc * mult), ted, be, nb)]
                 ch = int(mc * mult)
                 if ds in self.attention_resolutions:
-                    layers.append(AttnBlock(ch, num_heads, be, nb))
+                    layers.append(AttnBlock(ch, num_heads, be, nb, ab))
                 if level and i == num_res_blocks:
                     layers.append(Up(ch, be))
                     ds //= 2
@@ -383,7 +443,7 @@ class Trainer:
     network of opt's *_img / *_proj fields (num_res_blocks_<domain> / num_heads_<domain>, when opt has them, override the
     reference's constructor defaults 2 and 4), that domain's GaussianDiffusion, and Adam as the reference builds it."""
 
-    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch"):
+    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch"):
         from .diffusion import GaussianDiffusion, NoiseSource
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
@@ -395,7 +455,7 @@ class Trainer:
         self.device = torch.device(opt.device)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
-            self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, **kw).to(self.device)
+            self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
         self.optimizer = torch.optim.Adam(self.model.parameters(), lr=getattr(opt, "init_lr", 2e-4), weight_decay=1e-5,
