@@ -29,10 +29,6 @@
 using namespace ipdm;
 using namespace ipdm::attn;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int KV = 64;         // keys per LDS tile

@@ -3,14 +3,12 @@
 // itself (zseq) must apply the same float operations in the same order, whichever kernel produced the slices.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kernel_util.h"      // crow: the row of an accumulator register of the 32x32 MFMAs
 
 namespace ipdm {
 namespace attn {
 
 constexpr float LOG2E = 1.4426950408889634f;
-
-// row of accumulator register r (lane half h) in the output layout of the 32x32 MFMAs
-__device__ inline int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // Maximum / sum over the two halves of the wave (lanes l and l ^ 32) by v_permlane32_swap (gfx950): one VALU instruction
 // turns two copies of x into {lo, lo} and {hi, hi}.  As __shfl_xor(x, 32) the exchange is a ds_bpermute, an LDS round trip

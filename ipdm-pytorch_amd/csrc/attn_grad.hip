@@ -29,11 +29,10 @@
 // alignment of the rows (T = 1827).  A workgroup belongs to one (sample, head) and its order depends on T alone: a sample
 // launched alone has the bits of its row of a batch, and two calls give the same bits.
 #include "common.h"
+#include "kernel_util.h"      // f32x16, crow
 
 namespace ipdm {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int AG_WAVES = 2;
 constexpr int AG_THREADS = 64 * AG_WAVES;
@@ -42,9 +41,6 @@ constexpr int AG_STAGE = 64;              // streamed columns per LDS stage (two
 constexpr int AG_LD = AG_STAGE + 1;
 constexpr int AG_DMAX = 64;
 constexpr int AG_TPB = 256;               // the D pre-pass
-
-// row of accumulator register r in the 32x32 result (the column is lane & 31)
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // A stage on its way from global memory to LDS: rows wave, wave + AG_WAVES, ... of column x0 + (lane) in registers.  The loads
 // are unconditional (row and column clamped into the chunk) so that all of them are in flight at once, and they are issued a
@@ -121,7 +117,7 @@ __device__ __forceinline__ void store_owned(float *__restrict__ rows, const f32x
     for (int m = 0; m < DP / 32; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int c = m * 32 + mfma_row(r, hi);
+            const int c = m * 32 + crow(r, hi);
             if (c < d) rows[(size_t)c * T + x] = acc[m][r] * mul;
         }
 }
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(AG_THREADS) void attn_train_fwd_kernel(AttnArgs a)
             float bm = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (kb + mfma_row(r, hi) >= T) S[r] = -INFINITY;
+                if (kb + crow(r, hi) >= T) S[r] = -INFINITY;
                 bm = fmaxf(bm, S[r]);
             }
             bm = fmaxf(bm, other_half(bm));
@@ -201,7 +197,7 @@ __global__ __launch_bounds__(AG_THREADS) void attn_train_fwd_kernel(AttnArgs a)
     for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int c = m * 32 + mfma_row(r, hi);
+            const int c = m * 32 + crow(r, hi);
             if (c < d) a.o[(bh * d + c) * T + t] = O[m][r] / sum;
         }
     if (a.l && hi == 0) a.l[bh * T + t] = mx + logf(sum);
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(AG_THREADS) void attn_train_dq_kernel(AttnArgs a)
             const f32x16 dP = score<DP>(Vs, sub, greg, l31, hi);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float p = (kb + mfma_row(r, hi) < T && t < T) ? expf(S[r] - L) : 0.0f;
+                const float p = (kb + crow(r, hi) < T && t < T) ? expf(S[r] - L) : 0.0f;
                 S[r] = p * (dP[r] - Dt);
             }
             accumulate<DP>(dQ, Ks, sub, S, l31, hi);
@@ -314,7 +310,7 @@ __global__ __launch_bounds__(AG_THREADS) void attn_train_dkv_kernel(AttnArgs a)
             f32x16 dP = score<DP>(Gs, sub, vreg, l31, hi);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = sub * 32 + mfma_row(r, hi);
+                const int i = sub * 32 + crow(r, hi);
                 const float p = (t0 + i < T && s < T) ? expf(S[r] - Ls[i]) : 0.0f;
                 S[r] = p;
                 dP[r] = p * (dP[r] - Ds[i]);

@@ -21,11 +21,9 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "kernel_util.h"      // f32x*, OOB (idle staging slots read 0), bload
 
 using namespace ipdm;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -85,13 +83,6 @@ __device__ inline float sum_lanes_row(float x)           // over the 16 lanes of
     return x;
 }
 #undef IPDM_DPP_F
-
-// out-of-range per-lane offsets of a raw buffer read 0 (idle staging slots)
-constexpr int DOOB = 0x7fffffff;
-__device__ inline float dload(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
 
 // ---- epilogue shared by the kernels of this file: + bias (+ residual); 4 consecutive pixels per cout; fused GroupNorm
 // statistics of the output.  ty: the thread's row inside the 64x16 tile; in_lds: the (dead) staging area, >= 2*CO*256 floats
@@ -212,9 +203,9 @@ __global__ void __launch_bounds__(256, (STRIDE == 2 ? (CO <= 8 ? 4 : 3) : (CO <=
             sx = min((int)floorf((float)sx * a.scale_x), a.Ws - 1);
         }
         // byte offsets inside a channel plane (buffer loads: no 64-bit address arithmetic on the VALU, which bounds this kernel)
-        sp_src[j] = e < DIN_H * DIN_W ? (sy * a.Ws + sx) * 4 : DOOB;
+        sp_src[j] = e < DIN_H * DIN_W ? (sy * a.Ws + sx) * 4 : OOB;
         sp_srcp[j] = !(PLANAR || SKIP == 2) ? sp_src[j]
-                   : (e < DIN_H * DIN_W ? ((((sy & 1) * 2 + (sx & 1)) * (a.Hs >> 1) + (sy >> 1)) * (a.Ws >> 1) + (sx >> 1)) * 4 : DOOB);
+                   : (e < DIN_H * DIN_W ? ((((sy & 1) * 2 + (sx & 1)) * (a.Hs >> 1) + (sy >> 1)) * (a.Ws >> 1) + (sx >> 1)) * 4 : OOB);
         sp_dst[j] = e < DIN_H * DIN_W ? r * DIN_P + c : -1;
     }
     const int plane_bytes = src_plane * 4;
@@ -247,7 +238,7 @@ __global__ void __launch_bounds__(256, (STRIDE == 2 ? (CO <= 8 ? 4 : 3) : (CO <=
             const __amdgpu_buffer_rsrc_t r = from1 ? rsA : rsB;
             const int so = (from1 ? cg : cg - C1v) * plane_bytes;
 #pragma unroll
-            for (int j = 0; j < NSP; ++j) raw[c][j] = dload(r, PL && from1 ? sp_srcp[j] : sp_src[j], so);
+            for (int j = 0; j < NSP; ++j) raw[c][j] = bload(r, PL && from1 ? sp_srcp[j] : sp_src[j], so);
         }
 #pragma unroll
         for (int c = 0; c < DKC; ++c) {
@@ -349,7 +340,7 @@ __global__ void __launch_bounds__(256, (CO <= 8 ? 5 : 3)) conv_direct_up2_kernel
         const int r = e / SW, c = e % SW;
         const int sy = sy0 + r, sx = sx0 + c;
         const bool ok = e < SH * SW && sy >= 0 && sy < a.Hs && sx >= 0 && sx < a.Ws;      // outside the source: the conv's zero padding
-        sp_src[j] = ok ? (sy * a.Ws + sx) * 4 : DOOB;
+        sp_src[j] = ok ? (sy * a.Ws + sx) * 4 : OOB;
         sp_dst[j] = e < SH * SW ? r * SP + c : -1;
     }
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(a.x1 + (size_t)n * Cin * src_plane), 0, Cin * plane_bytes, 0x00020000);
@@ -362,7 +353,7 @@ __global__ void __launch_bounds__(256, (CO <= 8 ? 5 : 3)) conv_direct_up2_kernel
         for (int c = 0; c < DKC; ++c) {
             const int so = min(c0 + c, Cin - 1) * plane_bytes;
 #pragma unroll
-            for (int j = 0; j < NSP; ++j) raw[c][j] = dload(rsrc, sp_src[j], so);
+            for (int j = 0; j < NSP; ++j) raw[c][j] = bload(rsrc, sp_src[j], so);
         }
 #pragma unroll
         for (int c = 0; c < DKC; ++c)

@@ -35,27 +35,21 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "kernel_util.h"      // f32x*, OOB, bload
 
 using namespace ipdm;
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int NT_W = 64, NT_H = 16;                     // a wave's strip
-constexpr int NOOB = 0x7fffffff;
 
 inline double nm_bytes(const ConvArgs &a)
 {
     return 4.0 * a.B * ((double)(a.C1 + a.C2) * a.Hs * a.Ws + (double)a.Cout * a.Ho * a.Wo * (a.res ? 2 : 1));
 }
 
-__device__ inline float nload(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
 __device__ inline f32x4 nload4(__amdgpu_buffer_rsrc_t r, int voff, int soff)
 {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -92,7 +86,7 @@ __global__ void __launch_bounds__(256, (G <= 3 ? 3 : 2)) conv_nm_kernel(ConvArgs
     // end lanes (left of pixel 0 / right of pixel 63; everything else out of range = no memory traffic)
     const bool has_left = x0 > 0, has_right = x0 + NT_W < a.W;                 // (uniform) the strip's halo columns exist
     const int voff = k * plane_bytes + n * 16;
-    int voff_e = NOOB;
+    int voff_e = OOB;
     if (KS == 3) {
         if (n == 0 && has_left) voff_e = k * plane_bytes;                      // byte (x0 - 1) through the scalar offset - 4
         if (n == 15 && has_right) voff_e = k * plane_bytes + (has_left ? 65 : 64) * 4;
@@ -121,8 +115,8 @@ __global__ void __launch_bounds__(256, (G <= 3 ? 3 : 2)) conv_nm_kernel(ConvArgs
         const __amdgpu_buffer_rsrc_t rs = from1 ? rs1 : rs2;
         const int cb = (from1 ? 4 * g : 4 * g - a.C1) * plane_bytes;
         const int so = cb + (min(max(y, 0), a.H - 1) * a.Ws + x0) * 4;
-        xr[g] = nload4(rs, rowok ? voff : NOOB, so);
-        if (KS == 3) xe[g] = nload(rs, rowok ? voff_e : NOOB, has_left ? so - 4 : so);
+        xr[g] = nload4(rs, rowok ? voff : OOB, so);
+        if (KS == 3) xe[g] = bload(rs, rowok ? voff_e : OOB, has_left ? so - 4 : so);
     };
 #pragma unroll
     for (int g = 0; g < G; ++g) issue_row(g, 0);
@@ -135,8 +129,8 @@ __global__ void __launch_bounds__(256, (G <= 3 ? 3 : 2)) conv_nm_kernel(ConvArgs
     const bool couts_ok = 4 * k < a.Cout;                                        // (Cout % 4 == 0) the lane's four couts exist
     const bool vec = (a.Wo & 3) == 0;                                            // (uniform) runs are whole and 16-byte aligned
     const bool run_ok = x0 + 4 * n + 3 < a.Wo;
-    const int voff_o = (couts_ok && run_ok && vec) ? (4 * k * out_plane + 4 * n) * 4 : NOOB;
-    const int voff_o1 = couts_ok ? (4 * k * out_plane + 4 * n) * 4 : NOOB;       // element-wise path (widths that are not multiples of 4)
+    const int voff_o = (couts_ok && run_ok && vec) ? (4 * k * out_plane + 4 * n) * 4 : OOB;
+    const int voff_o1 = couts_ok ? (4 * k * out_plane + 4 * n) * 4 : OOB;       // element-wise path (widths that are not multiples of 4)
     float bias[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) bias[r] = (a.bias && couts_ok) ? a.bias[4 * k + r] : 0.0f;
@@ -161,18 +155,18 @@ __global__ void __launch_bounds__(256, (G <= 3 ? 3 : 2)) conv_nm_kernel(ConvArgs
                     v += rv[r];
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, voff_o, so + r * plane4, 0);
                     if (a.stats) {
-                        if (edge_strip && voff_o == NOOB) v = f32x4{0, 0, 0, 0};
+                        if (edge_strip && voff_o == OOB) v = f32x4{0, 0, 0, 0};
                         st1[r] += (v[0] + v[1]) + (v[2] + v[3]);
                         st2[r] += fmaf(v[3], v[3], fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0])));
                     }
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const int vo = (x0 + 4 * n + j < a.Wo) ? voff_o1 + 4 * j : NOOB;
+                        const int vo = (x0 + 4 * n + j < a.Wo) ? voff_o1 + 4 * j : OOB;
                         float e = v[j];
-                        if (a.res) e += nload(r_rsrc, vo, so + r * plane4);
+                        if (a.res) e += bload(r_rsrc, vo, so + r * plane4);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, e), o_rsrc, vo, so + r * plane4, 0);
-                        v[j] = vo != NOOB ? e : 0.0f;
+                        v[j] = vo != OOB ? e : 0.0f;
                     }
                     if (a.stats) {
                         st1[r] += (v[0] + v[1]) + (v[2] + v[3]);

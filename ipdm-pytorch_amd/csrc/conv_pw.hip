@@ -32,12 +32,9 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "kernel_util.h"      // f32x*, i32x4, OOB, bload
 
 using namespace ipdm;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef IPDM_PW_SAFE_WAIT
 #define IPDM_PW_SAFE_WAIT 0         // 1: every wait for a ring slot drains the whole queue (s_waitcnt vmcnt(0)) instead of the hand-counted
@@ -51,13 +48,8 @@ namespace {
 
 constexpr int BN = 128;                                // couts per item
 constexpr int NW = 8;                                  // waves per workgroup
-constexpr int OOB = 0x7fffffff;
 constexpr int KC_MIN = 32;                             // channel granularity the launcher asks for (both ring shapes divide it)
 
-__device__ inline float bload(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
 __device__ inline f32x4 bload4(__amdgpu_buffer_rsrc_t r, int voff, int soff)
 {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -70,7 +62,6 @@ __device__ inline f32x4 bload4(__amdgpu_buffer_rsrc_t r, int voff, int soff)
 // else the wave has in flight by then (bias / residual loads, stores) is younger and only makes the wait stricter.  The
 // compiler's own waits (for ITS loads) do not know about the ring either and are likewise stricter than necessary, never
 // weaker.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ inline i32x4 make_rsrc(const void *p, int bytes)
 {
     const unsigned long long u = (unsigned long long)p;

@@ -42,14 +42,11 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "kernel_util.h"      // f32x*, OOB, bload, row_slot
 
 using namespace ipdm;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef IPDM_CONV_STAMPS
 #define IPDM_CONV_STAMPS 0          // `make stamps`: in-kernel s_memtime stamps of the phases (a stamped build changes what it measures)
@@ -76,11 +73,6 @@ constexpr int U_CHUNK_FLOATS = U_FLOATS;               // packed weights of one 
 
 struct TileId { int n, oy0, ox0, co0; };
 
-// The stage images keep the rows i of the 4x4 transform domain in the order 0, 1, 3, 2: consumer wave ih then holds rows
-// (0, 1) or (3, 2) in its accumulators 0-3 / 4-7, and in the output transform BOTH waves keep first + second and send the
-// second (T1 resp. T2) -- no wave-dependent selects.
-__host__ __device__ constexpr int row_slot(int i) { return i ^ (i >> 1); }
-
 __device__ inline TileId decode_tile(const ConvArgs &a, int tile)
 {
     TileId t;
@@ -94,14 +86,6 @@ __device__ inline TileId decode_tile(const ConvArgs &a, int tile)
     t.ox0 = tx * TW;
     t.co0 = co_t * BN;
     return t;
-}
-
-// per-lane buffer offset that is out of range: loads return 0, stores are dropped (the scalar offset stays in range)
-constexpr int OOB = 0x7fffffff;
-
-__device__ inline float bload(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 
 #define IPDM_DPP_F(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (ctrl), 0xf, 0xf, false))

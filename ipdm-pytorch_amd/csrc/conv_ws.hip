@@ -36,12 +36,9 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "kernel_util.h"      // f32x*, OOB, bload
 
 using namespace ipdm;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -101,16 +98,6 @@ __device__ inline TileId decode_tile(const ConvArgs &a, int tile)
     t.ox0 = tx * TW;
     t.co0 = co_t * BN;
     return t;
-}
-
-// Per-lane (VGPR) buffer offset that is out of range: loads return 0 and stores are dropped, no branch.  The hardware
-// compares the VGPR offset with (num_records - scalar offset), so the SCALAR offset must always stay inside the buffer:
-// invalid elements are always killed through the per-lane offset, never through the scalar one.
-constexpr int OOB = 0x7fffffff;
-
-__device__ inline float bload(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 
 // SiLU(x*sc+sh) on a pair: 3 packed VALU + 2 exp + 2 rcp (the producers get ~1 VALU issue per partner MFMA)

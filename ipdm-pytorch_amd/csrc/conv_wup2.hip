@@ -29,12 +29,9 @@
 #include <type_traits>
 #include "common.h"
 #include "unet_kernels.h"
+#include "kernel_util.h"      // f32x*, OOB, bload
 
 using namespace ipdm;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef IPDM_WUP2_KO
 #define IPDM_WUP2_KO 0              // compile-time timing knock-outs (results are WRONG): 2 no input transform, 4 no output transform / stores,
@@ -73,13 +70,6 @@ __device__ inline ItemId decode_item(const ConvArgs &a, int item)
     t.ox0 = tx * TW;
     t.co0 = co_t * BN;
     return t;
-}
-
-constexpr int OOB = 0x7fffffff;                        // per-lane buffer offset out of range: loads return 0, stores are dropped
-
-__device__ inline float bload(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 
 // a.H x a.W: the SOURCE grid (= the size of one parity plane of the output); a.w: the image of conv_pack_weights_wup2

@@ -80,3 +80,27 @@ def test_no_early_write_of_an_mfma_source_operand_in_the_built_libraries(tmp_pat
     assert all("v_mfma_f32_32x32x16_bf16" in ln and "v_cndmask_b32" in ln for ln in flagged), r.stdout[-2000:]
     assert len({ln.split("conv_wino3_kernelIL")[1][:6] for ln in flagged}) == 4, flagged      # every instantiation
 
+
+ISA_EQUAL = os.path.join(ROOT, "tools", "isa_equal.py")
+
+
+def test_isa_equal_pairs_kernels_and_tells_same_code_from_other_code(tmp_path):
+    """tools/isa_equal.py, the instrument of a refactor that must not move a fenced kernel's code: the built conv_wino2.o against a fresh
+    compile of conv_wino2.hip (other addresses, the same instructions) is identical in every kernel, exit 0; against a compile with a
+    timing knock-out (-DIPDM_WINO2_KO=1: no activation) all four instantiations are reported as different, exit 1."""
+    built = os.path.join(CSRC, "conv_wino2.o")
+    assert os.path.exists(built), "csrc/conv_wino2.o missing: run __graft_entry__.build()"
+    base = ["hipcc", "-O3", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-Wno-unused-function", "-c", os.path.join(CSRC, "conv_wino2.hip"), "-o"]
+    same, other = str(tmp_path / "wino2_again.o"), str(tmp_path / "wino2_ko1.o")
+    jobs = [subprocess.Popen(base + [same], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL),
+            subprocess.Popen(base + [other, "-DIPDM_WINO2_KO=1"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)]
+    assert [j.wait(timeout=900) for j in jobs] == [0, 0]
+    r = subprocess.run([sys.executable, ISA_EQUAL, built, same], capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if "conv_wino2_kernelIL" in ln]
+    assert r.returncode == 0 and len(lines) == 4 and all(": identical" in ln for ln in lines), r.stdout[-2000:]
+    r = subprocess.run([sys.executable, ISA_EQUAL, built, other, "--kernel", "conv_wino2_kernel"], capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if "conv_wino2_kernelIL" in ln]
+    assert r.returncode == 1 and len(lines) == 4 and all("lines differ" in ln for ln in lines), r.stdout[-2000:]
+    r = subprocess.run([sys.executable, ISA_EQUAL, built, other, "--kernel", "no_such_kernel"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 1, r.stdout[-2000:]                                                 # nothing compared is not "identical"
+
