@@ -643,6 +643,55 @@ int ipdm_yj_invert(const float *d_y, float *d_out, int32_t B, int64_t n_per_slic
  * array: callable without a GPU, like ipdm_fbp_table.  The oracle of the device fit. */
 int ipdm_yj_fit_host(const float *x_host, int32_t B, int64_t n_per_slice, double *params_host, int32_t *evals_host);
 
+/* ------------------------------------------------------------------ training: optimiser, patches */
+/* The optimiser update of train() (Utils/train_test_utils.py:268) as one launch per parameter set (csrc/adam.hip) and the
+ * training loader's random patches cut on the device (csrc/crop.hip).  IPDM_ABI_VERSION stays 5: the entries were added
+ * without touching an existing signature; a binder detects them by symbol (dlsym of ipdm_adam_step).
+ *
+ * One tensor of a parameter set: parameter, gradient and the two moment estimates, n floats each, contiguous; a view may start
+ * at any float offset.  g == NULL: the tensor has no gradient this step and is left untouched (torch skips it the same way). */
+typedef struct ipdm_adam_tensor {
+    float *p;
+    const float *g;
+    float *m, *v;
+    int64_t n;
+} ipdm_adam_tensor;
+/* `len` floats of tensor `tensor` from float `offset` on; offsets are multiples of IPDM_ADAM_CHUNK */
+typedef struct ipdm_adam_chunk {
+    int32_t tensor, len;
+    int64_t offset;
+} ipdm_adam_chunk;
+#define IPDM_ADAM_CHUNK 4096
+/* The chunk table of a parameter set, built ONCE on the host from the tensors' sizes (any size >= 0; an empty tensor has no
+ * chunk): fills out[0 .. min(count, cap)) when out is not NULL and returns the count -- call with out == NULL for the size --
+ * or IPDM_ERR_INVALID for a negative size or count.  Host code, callable without a GPU. */
+int64_t ipdm_adam_chunks(const int64_t *sizes, int32_t n_tensors, ipdm_adam_chunk *out, int64_t cap);
+/* replaces optimizer.step() of torch.optim.Adam(params, lr, betas, eps, weight_decay) as the reference builds it (weight decay
+ * as L2 folded into the gradient, no amsgrad, no maximize), for update number `step` (1 = the first) of every tensor of the
+ * set, in ONE launch however many tensors there are.  Per element, in float32:
+ *   gt = g + wd p;  m' = m + (1 - beta1)(gt - m);  v' = beta2 v + (1 - beta2) gt^2;
+ *   p' = p - (lr / (1 - beta1^step)) m' / (sqrt(v') / sqrt(1 - beta2^step) + eps)
+ * with the bias corrections and lr / bc1 formed in double on the host and used as float32 scalars, as torch does.  p, m, v are
+ * written in place; g is only read.  d_tensors [n_tensors] and d_chunks [n_chunks] (ipdm_adam_chunks' table for these sizes) are
+ * DEVICE arrays: the caller uploads the per-step pointer table stream-ordered on `stream` (it is far too large for kernel
+ * arguments) from host memory that is not rewritten before the copy has happened.  No float outside [0, n) of a tensor is read or
+ * written, whatever the alignment of its four addresses (16-byte accesses only where all four allow them).  No atomics: the
+ * same inputs give the same bits.  A NULL table, a negative count, step < 1, a negative or non-finite lr / eps / weight decay or
+ * a beta outside [0, 1): IPDM_ERR_INVALID before any launch.  Asynchronous on `stream`, allocates nothing, does not synchronise. */
+int ipdm_adam_step(const ipdm_adam_tensor *d_tensors, int32_t n_tensors, const ipdm_adam_chunk *d_chunks, int64_t n_chunks,
+                   double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void *stream);
+/* replaces Siemens_dataset_npz.get_patch (Dataset/npz_data_loader.py:170-177) for a batch, with the `/ 10` of the projections
+ * under clip_proj (:97-98) and the .clamp(min=0) of train() (Utils/train_test_utils.py:262) fused:
+ *   d_out[i, j, y, x] = max(d_slices[i, r + y, c + x] (/ 10 when div10), 0),   (r, c) = offsets_host[i * m + j]
+ * d_slices [n, H, W], d_out [n, m, ph, pw]; offsets_host is a HOST array [n * m][2] of (row, column), read before the call
+ * returns (the offsets travel in the kernel arguments, IPDM_CROP_MAX patches per launch).  The division is a true float32
+ * division; a NaN stays a NaN.  ph == H and pw == W (the identity crop) and offsets on the last row or column are valid; an
+ * offset that lets a patch leave its slice, a patch larger than the slice or a NULL pointer: IPDM_ERR_INVALID before any launch.
+ * Asynchronous on `stream`, allocates nothing, does not synchronise. */
+#define IPDM_CROP_MAX 256
+int ipdm_crop_patches(const float *d_slices, float *d_out, int32_t n, int32_t m, int32_t H, int32_t W, int32_t ph, int32_t pw,
+                      const int32_t *offsets_host, int32_t div10, void *stream);
+
 /* ------------------------------------------------------------------ measurement ------------- */
 /* Per-launch HIP-event timing of the hot kernels on their launch stream (bench.py roofline leg; no
  * reference counterpart -- the reference has no profiling).  Classes: 0 = conv 3x3

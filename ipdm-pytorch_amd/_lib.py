@@ -52,6 +52,7 @@ _vp, _i32, _i64, _u64, _f32, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_u
 ABI_VERSION = 5          # ipdm_abi_version() of the header these prototypes were written against
 PROF_CLASSES = 8         # kernel classes of ipdm_profile_end (include/ipdm_hip.h)
 SLICE_IDS_MAX = 64       # IPDM_SLICE_IDS_MAX: entries of the id table of the _ids entry points
+ADAM_CHUNK = 4096        # IPDM_ADAM_CHUNK: floats per chunk of ipdm_adam_chunks' table
 
 PROTOTYPES = {
     "ipdm_last_error": (C.c_char_p, []),
@@ -169,6 +170,9 @@ PROTOTYPES = {
     "ipdm_yj_apply": (C.c_int, [_vp, _vp, _i32, _i64, C.POINTER(_f64), _vp]),
     "ipdm_yj_invert": (C.c_int, [_vp, _vp, _i32, _i64, C.POINTER(_f64), _vp]),
     "ipdm_yj_fit_host": (C.c_int, [_vp, _i32, _i64, C.POINTER(_f64), C.POINTER(_i32)]),
+    "ipdm_adam_chunks": (_i64, [_vp, _i32, _vp, _i64]),
+    "ipdm_adam_step": (C.c_int, [_vp, _i32, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "ipdm_crop_patches": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp, _i32, _vp]),
 }
 
 _lib = None

@@ -47,9 +47,21 @@ _FLAGS = [
     # where opt.normal's power transform is fitted, applied and inverted (no reference counterpart): "sklearn" = the host path of
     # the reference (normalize.py copies every slice to the host), "hip" = the float64 kernels of csrc/yj.hip on the device.
     ("normal_backend", str, "sklearn", None),
+    # the training run (fit() in a train_* mode: train.progressive_domain_trainer; Config/default_config.py:10-18,142-155)
+    ("save_freq", int, 10000, None), ("batch_size", int, 4, None), ("max_epochs", int, 300, None), ("init_lr", float, 2e-4, None),
+    ("train_dataset_path_FD_img", str, None, None), ("train_dataset_path_LD_img", str, None, None),
+    ("train_dataset_path_FD_proj", str, None, None), ("train_dataset_path_LD_proj", str, None, None),
+    ("num_workers", int, 4, None), ("patch", int, [512, 512], "+"), ("patch_per_image", int, 4, None),
+    # where the training step's pieces run (no reference counterpart; the Trainer's defaults): the convolutions ("hip" | "torch"),
+    # GroupNorm+SiLU and the attention core ("torch" | "hip"), the optimiser update ("torch" = torch.optim.Adam, "hip" = HipAdam, one
+    # launch per step); train_seed seeds the initial weights, the patch offsets, the timesteps and the noise of a run.
+    ("conv_backend", str, "hip", None), ("norm_backend", str, "torch", None), ("attn_backend", str, "torch", None),
+    ("optim_backend", str, "torch", None), ("train_seed", int, 0, None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 NORMAL_BACKENDS = ("sklearn", "hip")
+TRAIN_BACKENDS = dict(conv_backend=("hip", "torch"), norm_backend=("torch", "hip"), attn_backend=("torch", "hip"),
+                      optim_backend=("torch", "hip"))
 
 
 def check_metrics_backend(value):
@@ -66,6 +78,18 @@ def check_normal_backend(value):
     return value
 
 
+def check_train_backends(opt):
+    """The four *_backend keys of a training run as Trainer keywords (a key the options lack takes the Trainer's default, the
+    first entry); an unknown value is refused, like normal_backend."""
+    out = {}
+    for name, allowed in TRAIN_BACKENDS.items():
+        value = getattr(opt, name, allowed[0])
+        if value not in allowed:
+            raise ValueError("%s must be one of %s, not %r" % (name, allowed, value))
+        out[name] = value
+    return out
+
+
 def default_cfg(argv=None):
     """Config/default_config.py:7-172: argparse defaults, then --load_option_path JSON overlays every
     key that was not given on the command line."""
@@ -78,6 +102,8 @@ def default_cfg(argv=None):
             kw["choices"] = METRICS_BACKENDS
         if name == "normal_backend":
             kw["choices"] = NORMAL_BACKENDS
+        if name in TRAIN_BACKENDS:
+            kw["choices"] = TRAIN_BACKENDS[name]
         parser.add_argument("--" + name, **kw)
     argv = sys.argv[1:] if argv is None else argv
     opt = parser.parse_args(argv)

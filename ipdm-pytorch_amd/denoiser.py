@@ -104,7 +104,7 @@ class progressive_domain_denoiser(EvaluationMixin):
         o = self.opt
         self.img_model = UNetModel(in_channels=o.in_channels_img, model_channels=o.model_channels_img,
                                    out_channels=o.out_channels_img, attention_resolutions=o.attention_resolutions_img,
-                                   channel_mult=o.channel_mult_img).to(o.device)
+                                   channel_mult=o.channel_mult_img, **self._net_extras("img")).to(o.device)
         self.img_device = torch.device(o.device)
         self.img_dtype = torch.float32
         self.img_gaussian_diffusion = GaussianDiffusion(timesteps=o.timesteps_img, beta_schedule="cosine",
@@ -115,11 +115,17 @@ class progressive_domain_denoiser(EvaluationMixin):
         self.proj_model = UNetModel(in_channels=o.in_channels_proj, model_channels=o.model_channels_proj,
                                     out_channels=o.out_channels_proj,
                                     attention_resolutions=o.attention_resolutions_proj,
-                                    channel_mult=o.channel_mult_proj).to(o.device)
+                                    channel_mult=o.channel_mult_proj, **self._net_extras("proj")).to(o.device)
         self.proj_device = o.device
         self.proj_dtype = torch.float32
         self.proj_gaussian_diffusion = GaussianDiffusion(timesteps=o.timesteps_proj, beta_schedule="cosine",
                                                          schedule_power=o.schedule_power_proj)
+
+    def _net_extras(self, domain):
+        """num_res_blocks_<domain> / num_heads_<domain>, when opt has them (the reference has no such keys and always builds its
+        constructor defaults, 2 and 4): the keys train.Trainer reads, so that a network trained with them loads here."""
+        return {k: getattr(self.opt, "%s_%s" % (k, domain)) for k in ("num_res_blocks", "num_heads")
+                if getattr(self.opt, "%s_%s" % (k, domain), None) is not None}
 
     def init_convertor(self, convertor):
         """Utils/train_test_utils.py:225-233.  The reference reads Recon/Simens_alut.txt / Simens_theta.txt from its

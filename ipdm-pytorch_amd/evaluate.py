@@ -372,15 +372,39 @@ def _split_path(p):
     return parts[-2], parts[-1]
 
 
+def run_seed(seed, position):
+    """The generator seed of item / iteration `position` of a run seeded with `seed`: 32 bits (torch's CPU generator takes no
+    more from a seed), distinct for the positions of one run and for neighbouring seeds at one position."""
+    return (int(seed) * 2654435761 + int(position)) % (1 << 32)
+
+
 class Siemens_dataset_npz(torch.utils.data.Dataset):
-    """Dataset/npz_data_loader.py:55-201 for evaluation: four parallel trees `<root>/<patient>/<slice>.npz|npy`
-    (low-dose image, full-dose projection, full-dose image, low-dose projection); item = [ld_img, fd_proj, fd_img,
-    ld_proj] as [1, H, W] tensors (None for trees not given); projections divided by 10 when proj_clip."""
+    """Dataset/npz_data_loader.py:55-201: four parallel trees `<root>/<patient>/<slice>.npz|npy` (low-dose image, full-dose
+    projection, full-dose image, low-dose projection); item = [ld_img, fd_proj, fd_img, ld_proj] as [1, H, W] tensors (None for
+    trees not given); projections divided by 10 when proj_clip.
+
+    patch=(ph, pw), patch_per_image=m (the training loader, get_patch, :170-177): an item is [m, ph, pw] per present kind, m
+    random crops of the slice; collate stacks items to [bs, m, ph, pw].  The reference reseeds torch's GLOBAL generator from
+    entropy for every crop; here the offsets of an item come from a torch.Generator of its own, seeded from `seed`
+    (opt.train_seed) and the item's position in the run (`position`: the number of items handed out so far, which a resumed run
+    sets to where it stopped), so a run is reproducible and resumable and the global generator is left alone.  The offsets of
+    the last item are kept in `last_offsets` ({kind: int32 [m, 2] of (row, column)}).
+
+    device_crop=True (what progressive_domain_trainer asks for): the same offsets are drawn, but the item carries WHOLE
+    slices, float32 and not yet divided, and a fifth entry, the offsets as int32 [4, m, 2] in the item's kind order (zeros for an
+    absent kind); the trainer moves the slices to the device once and cuts there (crop_patches: ipdm_crop_patches fuses the
+    `/ 10` and the clamp).  Both paths cut the same bits from the same offsets for float32 files."""
+
+    KINDS = ("ldimg", "fdproj", "fdimg", "ldproj")           # the order of an item
 
     def __init__(self, ldproj_path=None, ldimg_path=None, fdproj_path=None, fdimg_path=None, proj_clip=False,
-                 img_clip=True, data_type="siemens", patch=None, patch_per_image=None, assign=None):
+                 img_clip=True, data_type="siemens", patch=None, patch_per_image=None, assign=None, seed=0, device_crop=False):
         if patch is not None:
-            raise NotImplementedError("random training patches belong to the training loop (out of scope)")
+            patch = tuple(int(v) for v in patch)
+            if len(patch) != 2 or min(patch) < 1 or patch_per_image is None or int(patch_per_image) < 1:
+                raise ValueError("patch=(ph, pw) needs two positive sizes and patch_per_image >= 1, not %r / %r" % (patch, patch_per_image))
+        self.patch, self.patch_per_image = patch, None if patch_per_image is None else int(patch_per_image)
+        self.seed, self.position, self.device_crop, self.last_offsets = int(seed), 0, bool(device_crop) and patch is not None, {}
         self.data_type, self.proj_clip, self.img_clip = data_type, proj_clip, img_clip
         self.patient_name = self.slice_name = None
         self.paths = dict(ldimg=ldimg_path, fdproj=fdproj_path, fdimg=fdimg_path, ldproj=ldproj_path)
@@ -415,8 +439,47 @@ class Siemens_dataset_npz(torch.utils.data.Dataset):
                 return len(self.files[kind])
         return 0
 
+    def patch_offsets(self, position, shapes):
+        """(row, column) of the m patches of every slice shape in `shapes` ({kind: (H, W)}, walked in item order) for the item at
+        `position` of the run: int32 [m, 2] per kind, rows uniform in [0, H - ph], columns in [0, W - pw] (RandomCrop's ranges),
+        from a generator seeded with (seed, position) alone."""
+        g = torch.Generator().manual_seed(run_seed(self.seed, position))
+        ph, pw = self.patch
+        out = {}
+        for kind in self.KINDS:
+            if kind not in shapes:
+                continue
+            H, W = shapes[kind]
+            if ph > H or pw > W:
+                raise ValueError("a %d x %d patch does not fit the %d x %d %s slices" % (ph, pw, H, W, kind))
+            r = torch.randint(0, H - ph + 1, (self.patch_per_image,), generator=g)
+            c = torch.randint(0, W - pw + 1, (self.patch_per_image,), generator=g)
+            out[kind] = torch.stack([r, c], 1).to(torch.int32)
+        return out
+
+    def get_patch(self, data, offsets):
+        """get_patch (:170-177) at given offsets: data [1, H, W] -> float32 [m, ph, pw]."""
+        ph, pw = self.patch
+        patch = torch.zeros((self.patch_per_image, ph, pw))
+        for i, (r, c) in enumerate(offsets.tolist()):
+            patch[i] = data[0, r:r + ph, c:c + pw]
+        return patch
+
     def __getitem__(self, idx):
-        return [self._item(k, self.files[k][idx]) if k in self.files else None for k in ("ldimg", "fdproj", "fdimg", "ldproj")]
+        if self.patch is None:
+            return [self._item(k, self.files[k][idx]) if k in self.files else None for k in self.KINDS]
+        if self.device_crop:          # whole float32 slices, undivided: the device cut divides (same bits as a / 10 in float32)
+            data = {k: torch.from_numpy(np.ascontiguousarray(self.get_data(self.files[k][idx]), dtype=np.float32))[None]
+                    for k in self.KINDS if k in self.files}
+        else:
+            data = {k: self._item(k, self.files[k][idx]) for k in self.KINDS if k in self.files}
+        offs = self.patch_offsets(self.position, {k: tuple(v.shape[-2:]) for k, v in data.items()})
+        self.position += 1
+        self.last_offsets = offs
+        if not self.device_crop:
+            return [self.get_patch(data[k], offs[k]) if k in data else None for k in self.KINDS]
+        table = torch.stack([offs[k] if k in offs else torch.zeros((self.patch_per_image, 2), dtype=torch.int32) for k in self.KINDS])
+        return [data.get(k) for k in self.KINDS] + [table]
 
     def get_data_from_name(self, patient_name, slice_name):
         out = []
@@ -430,7 +493,29 @@ class Siemens_dataset_npz(torch.utils.data.Dataset):
 
     @staticmethod
     def collate(batch):
-        return tuple(torch.stack([b[i] for b in batch], 0) if batch[0][i] is not None else None for i in range(4))
+        return tuple(torch.stack([b[i] for b in batch], 0) if batch[0][i] is not None else None for i in range(len(batch[0])))
+
+
+def crop_patches(slices, offsets, patch, div10=False):
+    """The device cut of the training loader (ipdm_crop_patches, csrc/crop.hip): slices [n, 1, H, W] or [n, H, W] float32 on the
+    GPU, offsets int [n, m, 2] of (row, column) on the host -> clamp(slices[i, r:r+ph, c:c+pw] (/ 10), min=0) as [n, m, ph, pw],
+    one launch on torch's current stream.  No host fall-back: a failing call raises."""
+    from . import _lib
+    if not (slices.is_cuda and slices.dtype == torch.float32):
+        raise _lib.IpdmError("crop_patches runs on float32 GPU tensors only (no CPU fallback); got %s %s" % (slices.device, slices.dtype))
+    if slices.dim() == 4 and slices.shape[1] == 1:
+        slices = slices[:, 0]
+    offsets = torch.as_tensor(offsets).to("cpu", torch.int32).contiguous()
+    if slices.dim() != 3 or offsets.dim() != 3 or offsets.shape[0] != slices.shape[0] or offsets.shape[2] != 2:
+        raise ValueError("crop_patches: slices %s do not go with offsets %s ([n, H, W] and [n, m, 2])" % (tuple(slices.shape), tuple(offsets.shape)))
+    slices = slices.contiguous()
+    n, H, W = (int(v) for v in slices.shape)
+    m, (ph, pw) = int(offsets.shape[1]), (int(v) for v in patch)
+    out = torch.empty((n, m, ph, pw), dtype=torch.float32, device=slices.device)
+    with torch.cuda.device(slices.device):
+        _lib.call("ipdm_crop_patches", _lib.ptr(slices), _lib.ptr(out), n, m, H, W, ph, pw, _lib.ptr(offsets), int(bool(div10)),
+                  _lib.current_stream())
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- drivers

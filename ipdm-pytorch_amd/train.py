@@ -15,14 +15,27 @@
               norm_backend="torch" / attn_backend="torch" (the defaults), GroupNorm, SiLU and the attention core are torch
               ops.  conv_backend="torch" sends the convolutions through F.conv2d as well: the A/B arm, and with
               norm_backend="torch" and attn_backend="torch" the only arm that runs on the CPU.
-  Trainer     train() of the reference harness: q_sample at per-row timesteps, the epsilon loss, backward, Adam.
+  HipAdam     torch.optim.Adam as the reference builds it, with the update of a whole param group as one launch
+              (ipdm_adam_step, csrc/adam.hip); state and state_dict() have torch.optim.Adam's layout, so checkpoints move
+              between the two in both directions.
+  Trainer     train() of the reference harness: q_sample at per-row timesteps, the epsilon loss, backward, Adam
+              (optim_backend="torch": torch.optim.Adam, the default; "hip": HipAdam).
+  RandomSampler   Utils/sampler.py: the index order of a training run (single process).
+  progressive_domain_trainer   the reference's progressive_domain_denoiser(opt) in a train_* mode: the training loader with its
+              random patches (cut on the device, evaluate.crop_patches), fit() with the loss log, the scalars, the model /
+              optimizer checkpoints, the periodic test() and resume.
 
 A missing kernel is an error: conv_backend="hip" never falls back to F.conv2d, norm_backend="hip" never to F.group_norm,
-attn_backend="hip" never to the einsums.  The dataloader, fit(), tensorboard and EMA are not
-here."""
+attn_backend="hip" never to the einsums, optim_backend="hip" never to torch.optim.Adam.  The reference has no EMA and no
+gradient all-reduce in train(); neither is here."""
 import collections
+import copy
+import ctypes
+import json
 import math
 import os
+import time
+import warnings
 
 import torch
 import torch.nn as nn
@@ -36,6 +49,7 @@ from .unet import UNetModel, make_cfg, param_shapes
 CONV_BACKENDS = ("hip", "torch")
 NORM_BACKENDS = ("torch", "hip")
 ATTN_BACKENDS = ("torch", "hip")
+OPTIM_BACKENDS = ("torch", "hip")
 
 
 # ------------------------------------------------------------------------------------------------ convolution under autograd
@@ -437,17 +451,200 @@ class TrainUNet(nn.Module):
         return _norm_act_conv(self.out, h) if self.norm_backend == "hip" else self.out(h)
 
 
+# ------------------------------------------------------------------------------------------------ the optimiser
+class HipAdam(torch.optim.Optimizer):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay) as the reference builds it (Utils/train_test_utils.py:150-151:
+    weight decay as L2 folded into the gradient, no amsgrad, no maximize) with step() as ONE ipdm_adam_step launch per param
+    group, where torch runs a string of foreach launches over the group's tensors.
+
+    `state` and state_dict() have torch.optim.Adam's layout -- per parameter `step` (a float32 scalar on the host), `exp_avg`,
+    `exp_avg_sq`, and this torch's own param_groups keys -- so a checkpoint written under one optimiser loads under the other.
+    step() costs the host little more than reading four addresses per tensor once a run is in its steady state (every parameter
+    has a gradient, one common step count); the state tensors it remembers for that are dropped by load_state_dict and
+    add_param_group -- code that swaps entries of `state` by hand calls _forget().
+    A parameter whose .grad is None is skipped, as torch skips it: its record goes into the table with a NULL gradient and its
+    `step` does not advance.  (Parameters of one group whose `step` counts differ -- only after such skips -- have different
+    bias corrections: the group is then updated with one launch per distinct count.)  Parameters are float32 GPU tensors,
+    contiguous; a view that starts at any float offset is fine.  There is no fall-back to torch's update."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        if not (lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError("HipAdam: lr %r, betas %r, eps %r, weight_decay %r" % (lr, betas, eps, weight_decay))
+        self._plans, self._tables, self._steady = {}, {}, {}
+        # the keys (and the other defaults) of THIS torch's Adam: param_groups then round-trip through either class
+        probe = torch.optim.Adam([torch.zeros(1, requires_grad=True)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(params, dict(probe.defaults))
+
+    # whatever replaces parameters or state drops what step() remembers of them
+    def _forget(self):
+        for d in (self._plans, self._tables, self._steady):
+            d.clear()
+
+    def load_state_dict(self, state_dict):
+        self._forget()
+        return super().load_state_dict(state_dict)
+
+    def add_param_group(self, param_group):
+        self._forget()
+        return super().add_param_group(param_group)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._plans, self._tables, self._steady = {}, {}, {}
+
+    def _plan(self, gi, sizes, device):
+        """The chunk table of param group gi on the device, built once per (sizes, device) by ipdm_adam_chunks."""
+        plan = self._plans.get(gi)
+        if plan is None or plan[0] != sizes or plan[1] != device:
+            arr = (ctypes.c_int64 * max(1, len(sizes)))(*sizes)
+            count = lib().ipdm_adam_chunks(arr, len(sizes), None, 0)
+            if count < 0:
+                raise IpdmError("ipdm_adam_chunks failed (%d): %s" % (count, lib().ipdm_last_error().decode()))
+            host = torch.zeros((max(1, count), 2), dtype=torch.int64)          # 16-byte records: (tensor, len), offset
+            lib().ipdm_adam_chunks(arr, len(sizes), ptr(host), count)
+            plan = (sizes, device, host.to(device), int(count))
+            self._plans[gi] = plan
+            self._tables.pop(gi, None)
+        return plan
+
+    def _table(self, gi, columns, device):
+        """The per-step table of ipdm_adam_tensor records on the device, from its five columns (p, g, m, v addresses and n).  It
+        is far too large for kernel arguments (some 400 records of 40 bytes), so it is uploaded stream-ordered: the records are
+        written into a FRESH pinned host tensor and copied with non_blocking=True on the current stream.  What keeps the next
+        step's table from overwriting this one before the copy has happened is torch's caching host allocator: a non-blocking
+        copy records an event on the stream behind it, and the allocator does not hand the pinned block out again -- to the
+        next step's pin_memory() -- before that event has completed.  The device tensor comes from the caching device
+        allocator, whose blocks are reused in stream order.  The host never writes either buffer after this function.  A table
+        equal to the last one (same addresses: the caching allocator usually puts the gradients back where they were) is not
+        uploaded again."""
+        last = self._tables.get(gi)
+        if last is not None and last[0] == columns:
+            return last[1]
+        dev = torch.tensor(columns, dtype=torch.int64).t().contiguous().pin_memory().to(device, non_blocking=True)
+        self._tables[gi] = (columns, dev)
+        return dev
+
+    def _check(self, t, what, device, shape=None):
+        if not (t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous() and (shape is None or t.shape == shape)):
+            raise IpdmError("HipAdam updates contiguous float32 tensors of one GPU only (no CPU fallback); %s is %s %s %s"
+                            % (what, t.device, t.dtype, tuple(t.shape)))
+
+    def _launch(self, gi, group, columns, device, t):
+        _, _, chunks, n_chunks = self._plan(gi, tuple(columns[4]), device)
+        beta1, beta2 = group["betas"]
+        with torch.cuda.device(device):
+            table = self._table(gi, columns, device)
+            call("ipdm_adam_step", ptr(table), len(columns[4]), ptr(chunks), n_chunks, float(group["lr"]), float(beta1), float(beta2),
+                 float(group["eps"]), float(group["weight_decay"]), int(t), _lib.current_stream())
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, group in enumerate(self.param_groups):
+            if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
+                raise NotImplementedError("HipAdam: amsgrad / maximize / decoupled_weight_decay are not what the reference builds")
+            params = group["params"]
+            if not params:
+                continue
+            grads = [p.grad for p in params]
+            steady = self._steady.get(gi)
+            if steady is not None and len(steady["params"]) == len(params) and all(map(_same, steady["params"], params)) \
+                    and not any(g is None or not g.is_contiguous() for g in grads):
+                # the steady state of a training run: every parameter has a gradient and they all share one step count.  What
+                # is left per step is reading 4 addresses per tensor; the step counts are one vector, advanced by one add.
+                # (assigning .grad already holds a gradient to its parameter's dtype, device and shape)
+                steady["steps"].add_(1)
+                steady["t"] += 1
+                columns = [[t.data_ptr() for t in params], [g.data_ptr() for g in grads], [t.data_ptr() for t in steady["m"]],
+                           [t.data_ptr() for t in steady["v"]], steady["n"]]
+                self._launch(gi, group, columns, steady["device"], steady["t"])
+                continue
+            self._step_checked(gi, group, params, grads)
+        return loss
+
+    def _step_checked(self, gi, group, params, grads):
+        """A step with everything looked at: state made where it is missing, tensors checked, parameters without a gradient
+        skipped, one launch per distinct step count.  When it ends with every parameter updated at one common count, the next
+        steps take the short way (step())."""
+        self._steady.pop(gi, None)
+        device = params[0].device
+        cols, steps, keep = ([], [], [], [], []), [], []
+        for p, g in zip(params, grads):
+            self._check(p, "a parameter", device)
+            st = self.state[p]
+            if g is None:
+                m, v = st.get("exp_avg"), st.get("exp_avg_sq")
+                row, count = (p.data_ptr(), 0, 0 if m is None else m.data_ptr(), 0 if v is None else v.data_ptr(), p.numel()), None
+            else:
+                if g.layout != torch.strided:
+                    raise IpdmError("HipAdam: sparse gradients are not supported")
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                    keep.append(g)                    # (alive until the launch is on the stream)
+                self._check(g, "a gradient", device, p.shape)
+                if len(st) == 0:                      # torch.optim.Adam's lazy state, same dtypes and devices
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                self._check(m, "exp_avg", device, p.shape)
+                self._check(v, "exp_avg_sq", device, p.shape)
+                st["step"] += 1
+                row, count = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()), int(st["step"])
+            for c, x in zip(cols, row):
+                c.append(x)
+            steps.append(count)
+        counts = sorted({t for t in steps if t is not None})
+        for t in counts:                              # (one launch unless skipped gradients have left the counts apart)
+            gcol = cols[1] if len(counts) == 1 else [g if s == t else 0 for g, s in zip(cols[1], steps)]
+            self._launch(gi, group, [cols[0], gcol, cols[2], cols[3], cols[4]], device, t)
+        del keep
+        if len(counts) == 1 and None not in steps:
+            # from here on the step counts of the group are views of ONE host vector (still a float32 scalar each, as torch lays
+            # them out), so that the short way advances them with a single add
+            vec = torch.full((len(params),), float(counts[0]), dtype=torch.float32)
+            for i, p in enumerate(params):
+                self.state[p]["step"] = vec[i]
+            self._steady[gi] = dict(params=list(params), m=[self.state[p]["exp_avg"] for p in params],
+                                    v=[self.state[p]["exp_avg_sq"] for p in params], n=list(cols[4]), steps=vec, t=counts[0], device=device)
+
+
+def _same(a, b):
+    return a is b
+
+
+def clean_keys(sd):
+    """load_network's key clean-up (Utils/loggerx.py:131-140): `module.` removed from every key of a loaded state_dict."""
+    return collections.OrderedDict((k.replace("module.", "") if isinstance(k, str) else k, v) for k, v in sd.items())
+
+
+def checkpoint_file(directory, name, epoch):
+    """<directory>/<name>-<epoch>, or the same under <directory>/save_models when a run directory was given; None when neither
+    exists (progressive_domain_denoiser.load_model's rule)."""
+    for d in (directory, os.path.join(directory, "save_models")):
+        f = os.path.join(d, "%s-%d" % (name, int(epoch)))
+        if os.path.exists(f):
+            return f
+    return None
+
+
 # ------------------------------------------------------------------------------------------------ the training step
 class Trainer:
     """train() of the reference harness (Utils/train_test_utils.py:146-168,253-272) for one domain ("img" or "proj"): the
     network of opt's *_img / *_proj fields (num_res_blocks_<domain> / num_heads_<domain>, when opt has them, override the
-    reference's constructor defaults 2 and 4), that domain's GaussianDiffusion, and Adam as the reference builds it."""
+    reference's constructor defaults 2 and 4), that domain's GaussianDiffusion, and Adam as the reference builds it:
+    torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip")."""
 
-    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch"):
+    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch"):
         from .diffusion import GaussianDiffusion, NoiseSource
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
-        self.opt, self.domain, self.seed = opt, domain, int(seed)
+        if optim_backend not in OPTIM_BACKENDS:
+            raise ValueError("optim_backend must be one of %s, not %r" % (OPTIM_BACKENDS, optim_backend))
+        self.opt, self.domain, self.seed, self.optim_backend = opt, domain, int(seed), optim_backend
         o = lambda name: getattr(opt, "%s_%s" % (name, domain))          # noqa: E731
         kw = dict(in_channels=o("in_channels"), model_channels=o("model_channels"), out_channels=o("out_channels"),
                   attention_resolutions=tuple(o("attention_resolutions")), channel_mult=tuple(o("channel_mult")),
@@ -458,8 +655,8 @@ class Trainer:
             self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
-        self.optimizer = torch.optim.Adam(self.model.parameters(), lr=getattr(opt, "init_lr", 2e-4), weight_decay=1e-5,
-                                          betas=(0.9, 0.999))
+        adam = HipAdam if optim_backend == "hip" else torch.optim.Adam
+        self.optimizer = adam(self.model.parameters(), lr=getattr(opt, "init_lr", 2e-4), weight_decay=1e-5, betas=(0.9, 0.999))
         self.noise = NoiseSource(self.seed)
         self._gen = torch.Generator().manual_seed(self.seed)
 
@@ -495,12 +692,26 @@ class Trainer:
 
     def save_checkpoint(self, directory, epoch):
         """LoggerX.checkpoints (Utils/loggerx.py:62-67): <directory>/save_models/{img_model,proj_model}-<epoch>, a state_dict;
-        progressive_domain_denoiser.load_model reads it (load_*_model_path = directory, resume_epochs_* = epoch)."""
+        progressive_domain_denoiser.load_model reads it (load_*_model_path = directory, resume_epochs_* = epoch).  Beside it
+        <directory>/save_models/optimizer-<epoch>, the optimiser's state_dict (torch.optim.Adam's layout under either
+        optim_backend).  Returns the model file."""
         d = os.path.join(directory, "save_models")
         os.makedirs(d, exist_ok=True)
         f = os.path.join(d, "%s_model-%d" % (self.domain, int(epoch)))
         torch.save(collections.OrderedDict((k, v.detach().cpu()) for k, v in self.model.state_dict().items()), f)
+        torch.save(self.optimizer.state_dict(), os.path.join(d, "optimizer-%d" % int(epoch)))
         return f
+
+    def load_checkpoint(self, directory, epoch):
+        """LoggerX.load_checkpoints (Utils/loggerx.py:71-80) for this trainer: <directory>[/save_models]/<domain>_model-<epoch>
+        into the network and optimizer-<epoch> into the optimiser (written under either optim_backend), both through
+        load_network's key clean-up.  A file that does not exist is skipped with a warning, as load_model does."""
+        for name, module in (("%s_model" % self.domain, self.model), ("optimizer", self.optimizer)):
+            f = checkpoint_file(directory, name, epoch)
+            if f is None:
+                warnings.warn("checkpoint %s-%d not found under %s: %s keeps its state" % (name, int(epoch), directory, name), UserWarning)
+                continue
+            module.load_state_dict(clean_keys(torch.load(f, map_location="cpu")))
 
     def sampling_model(self):
         """A UNetModel (the inference network of this library) loaded with the current weights, on the trainer's device."""
@@ -514,3 +725,201 @@ def expected_param_shapes(model):
     k = model.unet_kwargs()
     return param_shapes(make_cfg(k["in_channels"], k["model_channels"], k["out_channels"], k["num_res_blocks"],
                                  k["attention_resolutions"], k["channel_mult"], k["num_heads"]))
+
+
+# ------------------------------------------------------------------------------------------------ the training run
+class RandomSampler(torch.utils.data.Sampler):
+    """Utils/sampler.py: the index order of a training run.  Epoch e is torch.randperm(n) under a generator seeded with
+    seed + e, n = len(dataset) rounded down to a multiple of batch_size (the last short batch is dropped); epochs are laid end
+    to end, cut to num_iter * batch_size indices, and the first restore_iter * batch_size of them are skipped (a resumed run
+    continues where it stopped).  Same sequence as the reference for the same (len, batch_size, num_iter, restore_iter, seed).
+    Single process only: the reference's striding of the sequence over the ranks of a process group (and its weighted-sampling
+    branch, which its harness never asks for) is not built."""
+
+    def __init__(self, dataset, batch_size=0, num_iter=None, restore_iter=0, seed=0):
+        super().__init__()
+        self.dataset, self.batch_size, self.seed = dataset, int(batch_size), int(seed)
+        self.num_samples, self.restore = int(num_iter) * self.batch_size, int(restore_iter) * self.batch_size
+
+    def __iter__(self):
+        n = len(self.dataset)
+        n -= n % self.batch_size
+        if n <= 0:
+            raise ValueError("RandomSampler: %d items do not fill one batch of %d" % (len(self.dataset), self.batch_size))
+        order = []
+        for epoch in range(self.num_samples // n + 1):
+            order.extend(torch.randperm(n, generator=torch.Generator().manual_seed(self.seed + epoch)).tolist())
+        return iter(order[self.restore:self.num_samples])
+
+    def __len__(self):
+        return self.num_samples - self.restore
+
+
+class progressive_domain_trainer:
+    """The reference's progressive_domain_denoiser(opt) in a train_* mode (Utils/train_test_utils.py:121-200, 253-272, 326-376):
+    where the reference writes progressive_domain_denoiser(opt).fit() with opt.mode "train_img" / "train_proj", write
+    progressive_domain_trainer(opt).fit() (progressive_domain_denoiser keeps refusing those modes).
+
+    It builds a Trainer for the domain (option keys conv_backend / norm_backend / attn_backend / optim_backend / train_seed, the
+    Trainer's defaults when absent), the training dataset and loader with the reference's iteration arithmetic, and the save
+    tree <root>/<model_name>_<run_name>/save_models with option.json (root: result_save_path, or ./ModelTrainLog/.../<time>).
+    fit() runs the reference's loop: a loss / lr line per step in LoggerX.msg's format, the ten-step loss mean as train/loss,
+    <domain>_model-<it> and optimizer-<it> every save_freq iterations and, with test_numbers > 0, test(it) behind each
+    checkpoint.  Scalars are always appended to <root>/trainSummary/scalars.jsonl (one JSON object per line; the per-step loss
+    as train/loss_step) and go to torch.utils.tensorboard.SummaryWriter as well when that imports.
+
+    What a step draws is a function of (train_seed, n_iter) alone -- the patch offsets through the dataset's position, the
+    timesteps, the noise (draw n_iter of the trainer's NoiseSource) -- so a resumed run repeats the run it resumes.  resume:
+    resume_epochs_<domain> > 0 with load_<domain>_model_path loads <domain>_model-<epochs> and optimizer-<epochs> and skips the
+    sampler to the reference's resume_iter = resume_epochs * save_freq // batch_size (which is the iteration the checkpoint was
+    written at when batch_size == 1, as in the reference's shipped options; init_data_loader(resume_iter=...) names another).
+    Single process: the reference's train() has no gradient all-reduce either.  The reference has no EMA."""
+
+    def __init__(self, opt, result_save_path=None):
+        from .config import check_train_backends
+        if opt.mode not in ("train_img", "train_proj"):
+            raise ValueError("progressive_domain_trainer runs mode 'train_img' or 'train_proj', not %r (progressive_domain_denoiser "
+                             "runs the test_* modes)" % (opt.mode,))
+        self.opt, self.opt_temp = opt, copy.deepcopy(opt)
+        self.domain = "img" if opt.mode == "train_img" else "proj"
+        self.rank = 0
+        backends = check_train_backends(opt)
+        self.train_seed = int(getattr(opt, "train_seed", 0))
+        self.result_save_path = result_save_path
+        run = "%s_%s" % (opt.model_name, opt.run_name)
+        self.save_root = (os.path.join(result_save_path, run) if result_save_path is not None else
+                          os.path.join(os.getcwd(), "ModelTrainLog", run, time.strftime("%Y-%m-%dT%H-%M-%S")))
+        self.models_save_dir = os.path.join(self.save_root, "save_models")
+        os.makedirs(self.models_save_dir, exist_ok=True)
+        self.save_option(opt)
+        self.scalars_path = os.path.join(self.save_root, "trainSummary", "scalars.jsonl")
+        os.makedirs(os.path.dirname(self.scalars_path), exist_ok=True)
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            self.summer = SummaryWriter(log_dir=os.path.dirname(self.scalars_path))
+        except Exception:                                          # noqa: BLE001 - tensorboard is optional: the jsonl file is the record
+            self.summer = None
+        self.trainer = Trainer(opt, self.domain, seed=self.train_seed, **backends)
+        self.train_model, self.optimizer = self.trainer.model, self.trainer.optimizer
+        self.partial_timesteps = self.trainer.partial_timesteps
+        self.train_resume_epochs = int(getattr(opt, "resume_epochs_" + self.domain))
+        self.load_model()
+        self.train_dataset = self.train_loader = self._tester = None
+        self.losses = []                                           # (n_iter, loss) of every step of this object
+        self.init_data_loader()
+
+    # ---- LoggerX (Utils/loggerx.py)
+    def save_option(self, opt):
+        with open(os.path.join(self.models_save_dir, "option.json"), "w") as f:
+            f.write(json.dumps(opt.__dict__, sort_keys=False, indent=4, separators=(",", ": "), default=str))
+
+    def msg(self, loss, lr, step):
+        print("[%s] %05d, loss %2.5f, lr %2.5f, " % (time.strftime("%Y-%m-%d %H:%M:%S", time.localtime()), step, loss, lr))
+
+    def checkpoints(self, epoch):
+        return self.trainer.save_checkpoint(self.save_root, epoch)
+
+    def load_model(self):
+        path = getattr(self.opt, "load_%s_model_path" % self.domain)
+        if self.train_resume_epochs > 0 and path is not None:
+            self.trainer.load_checkpoint(path, self.train_resume_epochs)
+
+    # ---- scalars
+    def _scalar_line(self, record):
+        with open(self.scalars_path, "a") as f:
+            f.write(json.dumps(record) + "\n")
+
+    def add_scalar(self, tag, value, global_step, **extra):
+        self._scalar_line(dict(tag=tag, value=float(value), step=int(global_step), **extra))
+        if self.summer is not None:
+            self.summer.add_scalar(tag, value, global_step=global_step)
+
+    def add_scalars(self, tag, values, global_step):
+        self._scalar_line(dict(tag=tag, values={k: float(v) for k, v in values.items()}, step=int(global_step)))
+        if self.summer is not None:
+            self.summer.add_scalars(tag, values, global_step=global_step)
+
+    # ---- the loader (:350-376)
+    def init_data_loader(self, resume_iter=None):
+        from .evaluate import Siemens_dataset_npz
+        o = self.opt
+        patch = getattr(o, "patch", None)
+        ds = Siemens_dataset_npz(ldimg_path=o.train_dataset_path_LD_img, fdimg_path=o.train_dataset_path_FD_img,
+                                 ldproj_path=o.train_dataset_path_LD_proj, fdproj_path=o.train_dataset_path_FD_proj,
+                                 proj_clip=o.clip_proj, img_clip=o.clip_img, data_type=o.data_type, patch=patch,
+                                 patch_per_image=getattr(o, "patch_per_image", None), seed=self.train_seed,
+                                 device_crop=torch.device(o.device).type == "cuda")
+        o.max_iter = len(ds) * o.max_epochs // o.batch_size
+        o.resume_iter = self.train_resume_epochs * o.save_freq // o.batch_size if resume_iter is None else int(resume_iter)
+        ds.position = o.resume_iter * o.batch_size                 # the patches of a resumed run continue where they stopped
+        sampler = RandomSampler(ds, batch_size=o.batch_size, num_iter=o.max_iter, restore_iter=o.resume_iter)
+        self.train_len = len(ds)
+        self.train_dataset = ds
+        self.train_loader = torch.utils.data.DataLoader(dataset=ds, batch_size=o.batch_size, sampler=sampler, shuffle=False,
+                                                        drop_last=False, collate_fn=ds.collate)
+
+    # ---- train() (:253-272)
+    def train(self, images, n_iter, loss_temp):
+        o, ds = self.opt, self.train_dataset
+        col = 1 if self.domain == "proj" else 2
+        x = images[col]
+        if x is None:
+            raise ValueError("mode %r trains on the full-dose %s tree: train_dataset_path_FD_%s is not set" % (o.mode, self.domain, self.domain))
+        if ds is not None and ds.device_crop:                      # whole slices came: one copy to the device, one launch cuts
+            from .evaluate import crop_patches
+            x = crop_patches(x.float().to(o.device), images[4][:, col], ds.patch, div10=self.domain == "proj" and bool(o.clip_proj))
+        bs = x.shape[0] * x.shape[1]
+        from .evaluate import run_seed
+        t = torch.randint(0, self.partial_timesteps, (bs,), generator=torch.Generator().manual_seed(run_seed(self.train_seed, n_iter)))
+        self.trainer.noise.draw = int(n_iter)
+        loss = self.trainer.step(x, t=t)
+        lr = self.optimizer.param_groups[0]["lr"]
+        loss_temp[0] += loss
+        self.losses.append((int(n_iter), loss))
+        self.add_scalar("train/loss_step", loss, n_iter, lr=float(lr))
+        self.msg(loss, lr, n_iter)
+
+    # ---- test() (:274-324) through an inner denoiser of the matching test_* mode
+    def _make_tester(self):
+        from .denoiser import progressive_domain_denoiser
+        topt = copy.deepcopy(self.opt)
+        topt.mode = "test_" + self.domain
+        topt.resume_epochs_img = topt.resume_epochs_proj = 0       # its network comes from sampling_model(), not from a file
+        den = progressive_domain_denoiser(topt, result_save_path=None, seed=self.train_seed)
+        den._init_evaluation(self.save_root)
+        return den
+
+    def test(self, epoch):
+        """test(it) of the reference in a train_* mode: the test dataset scored with the current weights (the inference network
+        of sampling_model()), metric files under <root>/save_test_results/Save_Iter_<it>, and the psnr / ssim groups of the
+        totals as scalars.  As in the reference the per-sample list is never cleared: the totals of test(it) are over every
+        sample scored so far."""
+        if self._tester is None:
+            self._tester = self._make_tester()
+        den = self._tester
+        setattr(den, self.domain + "_model", self.trainer.sampling_model())
+        den.test(epoch)
+        for key in den.metric_total.keys():
+            group = den.metric_total[key]
+            if group:
+                self.add_scalars(key + "/psnr", {k: v for k, v in group.items() if "psnr" in k}, epoch)
+                self.add_scalars(key + "/ssim", {k: v for k, v in group.items() if "ssim" in k}, epoch)
+
+    # ---- fit() (:326-345)
+    def fit(self):
+        o = self.opt
+        loader = iter(self.train_loader)
+        loss_temp = [0]
+        for n_iter in range(o.resume_iter + 1, o.max_iter + 1):
+            inputs = next(loader)
+            self.train(inputs, n_iter, loss_temp)
+            if n_iter % 10 == 0:
+                self.add_scalar("train/loss", loss_temp[0] / 10, n_iter // 10)
+                loss_temp = [0]
+            if n_iter % o.save_freq == 0:
+                it = n_iter // o.save_freq
+                self.checkpoints(it)
+                if o.test_numbers > 0:
+                    self.test(it)
+        if self.summer is not None:
+            self.summer.flush()

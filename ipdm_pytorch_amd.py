@@ -1,5 +1,5 @@
 """Import alias: the package directory is `ipdm-pytorch_amd/` (not a valid Python identifier), so
-`import ipdm_pytorch_amd` loads it from there."""
+`import ipdm_pytorch_amd` loads it from there.  Run as a script it is the reference's main.py: options, then fit()."""
 import importlib.util
 import os
 import sys
@@ -10,3 +10,6 @@ _spec = importlib.util.spec_from_file_location("ipdm_pytorch_amd", os.path.join(
 _mod = importlib.util.module_from_spec(_spec)
 sys.modules["ipdm_pytorch_amd"] = _mod
 _spec.loader.exec_module(_mod)
+
+if __name__ == "__main__":
+    sys.exit(_mod.main())
