@@ -1,6 +1,7 @@
 """Reference values of the optimiser tests (tests/test_gpu_adam.py, tests/test_adam_host.py): the parameter set, the float64
 value of one Adam update with its conditioning, the float32 arbiter (torch.optim.Adam on the CPU) and a plain float32 numpy
-restatement of the kernel's expression.
+restatement of the kernel's expression.  The layout helpers take the parameter set as an argument: LAYOUT (the default, 58
+chunks) or LONG_LAYOUT (a chunk table of more than twice the kernel's grid).
 
 The function (include/ipdm_hip.h: ipdm_adam_step), per element:
     gt = g + wd p;   m' = m + w1 (gt - m);   v' = b2 v + w2 gt^2;   p' = p - ss m' / (sqrt(v') / bc2s + eps)
@@ -23,12 +24,24 @@ LR, BETAS, EPS = 2e-4, (0.9, 0.999), 1e-8
 # kernel may not look at p alone)
 LAYOUT = ([(n, 0, 0) for n in (0, 1, 3, 4, 5, 63, 64, 65, 1023, 3 * CHUNK + 1)] + [(7, 0, 0)] * 40 + [(CHUNK + 37, 1, 1), (261, 3, 0)])
 ARMS = [(1, 0.0), (1, 1e-5), (1000, 0.0), (1000, 1e-5)]          # (t, weight decay); t = 1 starts from m = v = 0
+# A chunk table longer than twice the kernel's grid (min(n_chunks, GRID_CAP) workgroups that stride over the table), so that some
+# workgroups make three trips, in under 0.2 M floats: small tensors whose sizes cycle through 1, 3, 4, 5, 7, 63, 64, 65 (one
+# chunk each) and three tensors of several chunks -- one of 5 * CHUNK + 1 floats behind 2045 small ones (chunks 2045 .. 2050:
+# they straddle table index 2047 | 2048), the one whose p alone is misaligned behind 2043 more (chunks 4094 .. 4096, across
+# 4095 | 4096) and one all of whose arrays start one float into a 16-byte group.  4399 chunks: the last entry, 4398, is 302 past
+# a multiple of the grid, so workgroups 0 .. 302 make three trips and the others two.
+GRID_CAP = 2048
+_SMALL = (1, 3, 4, 5, 7, 63, 64, 65)
+LONG_LAYOUT = ([(_SMALL[i % 8], 0, 0) for i in range(2045)] + [(5 * CHUNK + 1, 0, 0)] + [(_SMALL[(i + 3) % 8], 0, 0) for i in range(2043)]
+               + [(2 * CHUNK + 261, 3, 0), (CHUNK + 37, 1, 1)] + [(_SMALL[(i + 5) % 8], 0, 0) for i in range(300)])
+LONG_CHUNKS = 2045 + 6 + 2043 + 3 + 2 + 300
+LONG_ARMS = [(1000, 1e-5), (1, 0.0)]
 
 
-def offsets(which):
+def offsets(which, layout=LAYOUT):
     """Start of every tensor in the flat array `which` ("p" or one of "g", "m", "v") and the array's length."""
     out, pos = [], 0
-    for n, mod_p, mod_o in LAYOUT:
+    for n, mod_p, mod_o in layout:
         pos += PAD
         pos += (-pos) % 4 + (mod_p if which == "p" else mod_o)
         out.append(pos)
@@ -36,34 +49,34 @@ def offsets(which):
     return out, pos + PAD
 
 
-def scatter(which, values):
+def scatter(which, values, layout=LAYOUT):
     """The flat array `which`: the tensors' values at their places, sentinels everywhere else."""
-    offs, total = offsets(which)
+    offs, total = offsets(which, layout)
     flat = np.full(total, SENTINEL, np.float32)
     lo = 0
-    for (n, _, _), o in zip(LAYOUT, offs):
+    for (n, _, _), o in zip(layout, offs):
         flat[o:o + n] = values[lo:lo + n]
         lo += n
     return flat
 
 
-def gather(which, flat):
-    offs, _ = offsets(which)
-    return np.concatenate([flat[o:o + n] for (n, _, _), o in zip(LAYOUT, offs)])
+def gather(which, flat, layout=LAYOUT):
+    offs, _ = offsets(which, layout)
+    return np.concatenate([flat[o:o + n] for (n, _, _), o in zip(layout, offs)])
 
 
-def sentinels_intact(which, flat):
-    offs, total = offsets(which)
+def sentinels_intact(which, flat, layout=LAYOUT):
+    offs, total = offsets(which, layout)
     keep = np.ones(total, bool)
-    for (n, _, _), o in zip(LAYOUT, offs):
+    for (n, _, _), o in zip(layout, offs):
         keep[o:o + n] = False
-    return bool((flat[keep] == np.float32(SENTINEL)).all()) and int(keep.sum()) >= PAD * (len(LAYOUT) + 1)
+    return bool((flat[keep] == np.float32(SENTINEL)).all()) and int(keep.sum()) >= PAD * (len(layout) + 1)
 
 
-def inputs(t):
+def inputs(t, layout=LAYOUT):
     """(p, g, m, v), float32, all tensors concatenated.  A tenth of the gradients is exactly zero; at t > 1 half of those
     elements have v = 0 as well (the denominator is eps alone) while m is not zero there."""
-    N = sum(n for n, _, _ in LAYOUT)
+    N = sum(n for n, _, _ in layout)
     p = (synth.hash_normal((N,), 8101) * 0.1).astype(np.float32)
     g = (synth.hash_normal((N,), 8102) * 0.01).astype(np.float32)
     u = synth.hash_uniform((N,), 8103)
@@ -95,9 +108,9 @@ def value64(p, g, m, v, t, wd):
     return (m1, v1, p1), (a_m, v1.clone(), p.abs() + (p1 - p).abs())
 
 
-def arbiter32(p, g, m, v, t, wd):
+def arbiter32(p, g, m, v, t, wd, layout=LAYOUT):
     """torch.optim.Adam on the CPU in float32, one step from the same state: (m', v', p') as float32 tensors."""
-    splits = [n for n, _, _ in LAYOUT]
+    splits = [n for n, _, _ in layout]
     params = [torch.nn.Parameter(x.clone()) for x in torch.from_numpy(p).split(splits)]
     opt = torch.optim.Adam(params, lr=LR, betas=BETAS, eps=EPS, weight_decay=wd)
     for q, gq, mq, vq in zip(params, torch.from_numpy(g).split(splits), torch.from_numpy(m).split(splits), torch.from_numpy(v).split(splits)):

@@ -121,7 +121,8 @@ def test_new_entries_refuse_bad_arguments_on_the_host():
 def test_float32_restatement_passes_the_gate_the_kernel_is_held_to():
     """The gate of tests/test_gpu_adam.py on the CPU: a plain float32 numpy evaluation of the update passes it on the same
     inputs, so the conditioning fits a float32 evaluation (a miss on the device is then the kernel's).  Measured: rms <= 1.03,
-    elementwise <= 1.76.  The layout helpers put every tensor back where it came from and see a touched sentinel."""
+    elementwise <= 1.76; on the long table's set (ar.LONG_LAYOUT, two arms) rms <= 1.02, elementwise <= 1.31.  The layout
+    helpers put every tensor back where it came from and see a touched sentinel, for both layouts."""
     from tests import _adam_ref as ar
     from tests._accuracy import check
     for t, wd in ar.ARMS:
@@ -130,6 +131,13 @@ def test_float32_restatement_passes_the_gate_the_kernel_is_held_to():
         y32 = ar.arbiter32(*vals, t, wd)
         for name, y, y3, rr, aa in zip("mvp", ar.numpy32(*vals, t, wd), y32, r, a):
             check(y, y3.double(), rr, aa, "adam-numpy", ctx=(name, t, wd))
+    for t, wd in ar.LONG_ARMS:                                     # the long table's inputs: fair in the same sense
+        vals = ar.inputs(t, ar.LONG_LAYOUT)
+        r, a = ar.value64(*vals, t, wd)
+        y32 = ar.arbiter32(*vals, t, wd, ar.LONG_LAYOUT)
+        for name, y, y3, rr, aa in zip("mvp", ar.numpy32(*vals, t, wd), y32, r, a):
+            ratios = check(y, y3.double(), rr, aa, "adam-numpy", ctx=(name, t, wd, "long"))
+            print("adam-numpy long table t=%d wd=%g %s: rms ratio %.3f, elementwise ratio %.3f" % (t, wd, name, ratios[0], ratios[1]))
     p = ar.inputs(1)[0]
     for which in "pg":
         flat = ar.scatter(which, p)
@@ -138,3 +146,28 @@ def test_float32_restatement_passes_the_gate_the_kernel_is_held_to():
         assert offs[-2] % 4 == 1 and offs[-1] % 4 == (3 if which == "p" else 0) and all(o % 4 == 0 for o in offs[:-2])
         flat[offs[5] - 1] = 0.0
         assert not ar.sentinels_intact(which, flat)
+    lay = ar.LONG_LAYOUT
+    p = ar.inputs(1, lay)[0]
+    assert len(p) == sum(n for n, _, _ in lay) and ar.offsets("p", lay)[1] < 2_000_000
+    for which in "pg":
+        flat = ar.scatter(which, p, lay)
+        assert np.array_equal(ar.gather(which, flat, lay), p) and ar.sentinels_intact(which, flat, lay)
+        flat[ar.offsets(which, lay)[0][2045] + 5 * ar.CHUNK + 1] = 0.0           # the float behind the tensor of six chunks
+        assert not ar.sentinels_intact(which, flat, lay)
+
+
+def test_long_layout_has_a_table_of_more_than_twice_the_grid():
+    """ar.LONG_LAYOUT through ipdm_adam_chunks: more than 2 * GRID_CAP entries, the last one not on a multiple of the grid, and
+    the two tensors placed across table indices 2047 | 2048 and 4095 | 4096 lie there."""
+    from ipdm_pytorch_amd import _lib
+    from tests import _adam_ref as ar
+    sizes = [n for n, _, _ in ar.LONG_LAYOUT]
+    arr = (C.c_int64 * len(sizes))(*sizes)
+    count = _lib.lib().ipdm_adam_chunks(arr, len(sizes), None, 0)
+    assert count == ar.LONG_CHUNKS == 4399 and count > 2 * ar.GRID_CAP and (count - 1) % ar.GRID_CAP == 302
+    out = np.zeros((count, 2), np.int64)
+    assert _lib.lib().ipdm_adam_chunks(arr, len(sizes), _lib.ptr(out), count) == count
+    tensor = out.view(np.int32).reshape(count, 4)[:, 0]
+    assert list(np.nonzero(tensor == 2045)[0]) == [2045, 2046, 2047, 2048, 2049, 2050]
+    assert list(np.nonzero(tensor == 4089)[0]) == [4094, 4095, 4096] and ar.LONG_LAYOUT[4089] == (2 * ar.CHUNK + 261, 3, 0)
+    assert sorted({n for n, _, _ in ar.LONG_LAYOUT if n < ar.CHUNK}) == [1, 3, 4, 5, 7, 63, 64, 65]

@@ -4,8 +4,13 @@ float64 value in units of the float32 torch-CPU evaluation's own distance).
 
 For each shape and each output (y, dX, dW, db): r is the float64 torch-CPU value on the same float32 inputs, y32 the float32
 torch-CPU value, a the same op on absolute values (dW: sum |dY| |X|; dX: the transposed convolution of |dY| with |W|).  Outputs
-and workspace are NaN before every call (an unwritten slab or border pixel stays NaN and fails the gate)."""
+and workspace are NaN before every call (an unwritten slab or border pixel stays NaN and fails the gate).
+
+Two shapes of their own (tests/_conv_grad_ref.SLAB_SHAPES, not in SHAPES: the parametrised tests do not multiply them) have
+K = B Ho Wo past the slab cap, where the weight gradient's slabs double to 1024 pixels; tests/test_conv_grad_host.py shows on the
+CPU that the gate's arbiter is a fair yardstick for that summation order."""
 import functools
+import math
 
 import pytest
 import torch
@@ -13,6 +18,7 @@ import torch.nn.functional as F
 
 from ipdm_pytorch_amd import synth
 
+from tests import _conv_grad_ref as cr
 from tests._accuracy import M_ELEM, R_RMS, U, measure
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +154,39 @@ def test_entries_against_float64(geo):
     assert torch.equal(run_dgrad(geo, dyd, wd), dx)
     dw2, db2 = run_wgrad(geo, xd, dyd)
     assert torch.equal(dw2, dw) and torch.equal(db2, db)
+
+
+@pytest.mark.parametrize("geo", cr.SLAB_SHAPES, ids=cr.SLAB_IDS)
+def test_weight_gradient_past_the_slab_cap(geo):
+    """K = 16 814 100 > WG_SLAB * WG_MAX_SLABS: slab_len_of doubles the slab to 1024 pixels (float32 chains of 1024 terms instead
+    of 512, a 32-bit slab index beside a 64-bit pixel index), 16 421 slabs, the last of 20 pixels -- a ragged last 16-pixel stage.
+    dW and db over the whole shape on the gate; fprop and dgrad, which take no other branch here, once on three bands of rows
+    (first, middle, last; cr.BANDS) with every other element required to be written and finite."""
+    lib = _lib().lib()
+    B, Cin, Cout, H, W, k, s = geo
+    K = B * H * W
+    slabs = lib.ipdm_conv2d_wgrad_slabs(B, *out_hw(geo))
+    assert out_hw(geo) == (H, W) and K > cr.WG_SLAB * cr.WG_MAX_SLABS and lib.ipdm_conv2d_wgrad_slabs(1, 4096, 4096) == cr.WG_MAX_SLABS
+    assert slabs == math.ceil(K / 1024) == cr.SLABS and K - (slabs - 1) * 1024 == cr.LAST_SLAB
+    print("conv_grad %s: K = %d, %d slabs of %d pixels, the last of %d" % ("x".join(map(str, geo)), K, slabs, cr.SLAB_LEN, cr.LAST_SLAB))
+    x, w, b, dy = cr.inputs(geo)
+    xd, wd, bd, dyd = (t.to(DEV) for t in (x, w, b, dy))
+    dw, db = run_wgrad(geo, xd, dyd)
+    y = run_fprop(geo, xd, wd, bd).cpu()
+    dx = run_dgrad(geo, dyd, wd).cpu()
+    dw, db = dw.cpu(), db.cpu()
+    del xd, dyd
+    ref = cr.wgrad_reference(geo, x, dy)
+    gate(dw, ref["dw"], "dw", geo)
+    gate(db, ref["db"], "db", geo)
+    r, a, _ = ref["dw"]
+    print("conv_grad dw %s: max |dW - r| / (u a) = %.3f" % ("x".join(map(str, geo)), float(((dw.double() - r).abs() / (U * a)).max())))
+    assert y.shape == (B, Cout, H, W) and dx.shape == x.shape and bool(torch.isfinite(y).all()) and bool(torch.isfinite(dx).all())
+    for rows in cr.BANDS:
+        band = cr.band_reference(geo, x, w, b, dy, rows)
+        gate(y[:, :, rows[0]:rows[1]], band["y"], "y", geo + rows)
+        gate(dx[:, :, rows[0]:rows[1]], band["dx"], "dx", geo + rows)
+    assert cr.BANDS[0][0] == 0 and cr.BANDS[-1][1] == H
 
 
 @pytest.mark.parametrize("geo", SHAPES, ids=IDS)

@@ -2,7 +2,8 @@
 and a select in front, so every result is compared bit for bit with torch on the CPU:
     clamp(slice[r:r+ph, c:c+pw] / 10, min=0)    and the form without the division,
 negative inputs included, for patches in the first and the last corner, the identity crop (ph = H, pw = W), odd W and pw, and
-more patches than one launch carries.  Sentinels around the result come back unchanged."""
+more patches than one launch carries, and patches of more elements than the grid has lanes (at most GRID_CAP workgroups of 256
+per patch, `e += gridDim.x * 256` for the rest).  Sentinels around the result come back unchanged."""
 import numpy as np
 import pytest
 import torch
@@ -35,7 +36,11 @@ CASES = [  # (n, m, H, W, ph, pw, offsets or None = hashed)
     (2, 2, 40, 24, 40, 24, [[(0, 0), (0, 0)], [(0, 0), (0, 0)]]),                               # the identity crop
     (2, 1, 40, 24, 40, 8, [[(0, 16)], [(0, 3)]]),                                               # full height, last column
     (3, 100, 40, 24, 5, 3, None),                                                               # 300 patches: two launches
+    (1, 2, 300, 270, 260, 253, [[(0, 0), (40, 17)]]),       # 65 780 elements: one workgroup's worth past the grid's 65 536, pw odd
+    (1, 1, 520, 515, 512, 512, [[(8, 3)]]),                 # the default patch: four whole trips
 ]
+GRID_CAP = 256                                              # workgroups per patch (csrc/crop.hip)
+PAST_THE_GRID = CASES[-2:]
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d-%dx%d-of-%dx%d" % c[:6])
@@ -43,6 +48,12 @@ CASES = [  # (n, m, H, W, ph, pw, offsets or None = hashed)
 def test_crop_equals_torch_bit_for_bit(case, div10):
     from ipdm_pytorch_amd import _lib
     n, m, H, W, ph, pw, offs = case
+    if case in PAST_THE_GRID:
+        assert ph * pw > GRID_CAP * 256 == 65536
+        print("crop %dx%d: %d elements, a grid of %d workgroups of 256: %d trips (the last one of %d elements)"
+              % (ph, pw, ph * pw, GRID_CAP, -(-ph * pw // 65536), (ph * pw - 1) % 65536 + 1))
+    else:
+        assert ph * pw <= GRID_CAP * 256
     if offs is None:
         u = synth.hash_uniform((n, m, 2), 77)
         offs = np.stack([np.floor(u[..., 0] * (H - ph + 1)), np.floor(u[..., 1] * (W - pw + 1))], -1)

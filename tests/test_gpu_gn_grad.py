@@ -18,7 +18,13 @@ plan gives, so that ragged last slices occur).  Outputs, stats and workspace are
 fails.  Two conditions of the function, not tolerances: dshift with one channel per group is zero in exact arithmetic (its
 float64 value is cancellation residue), so it is held to the elementwise gate everywhere and to the rms gate only where
 cpg > 1; and in a constant group rstd = 1 / sqrt(eps) multiplies the arbiter's residue, so the rms gate of dx runs over the
-other groups while the elementwise gate runs over everything."""
+other groups while the elementwise gate runs over everything.
+
+Beside the small shapes (cpg 1 .. 5, at most 3 slices) three lists hold the extents at which the kernels take other branches:
+the production widths (cpg 8 .. 32), cpg at and past RED_ROWS = 32 (a full LDS block of row partials, and a second pass of the
+`c0 += RED_ROWS` loops in the one-pass and the split backward), and slice counts 33 and 64 (lanes of the upper half of the
+folding wave carry data; 64 is the clamp, with slices longer than GN_SLICE_MIN).  Every case first asserts, from
+ipdm_gn_act_plan, the form and slice count it runs with, and prints them."""
 import ctypes as C
 import functools
 
@@ -44,8 +50,33 @@ SHAPES = [
     (1, 8, 8, 96, 80),          # long rows, N = 7680
     (2, 64, 32, 64, 72),        # N = 9216: the split form under the default plan
 ]
-IDS = ["x".join(str(v) for v in s) for s in SHAPES]
+# production widths (the networks' 256 / 512 / 768 / 1024-channel levels); groups follow train.gn_groups: cpg 8, 16, 24, 32
+WIDE_SHAPES = [
+    (2, 256, 32, 6, 5),         # cpg 8
+    (1, 512, 32, 4, 3),         # cpg 16
+    (1, 768, 32, 3, 3),         # cpg 24, HW odd
+    (2, 1024, 32, 4, 4),        # cpg 32: one full RED_ROWS block
+]
+# cpg around and past RED_ROWS; these groups are NOT train.gn_groups' choice (only the entries are run on them)
+RED_SHAPES = [
+    (2, 64, 2, 9, 7),           # cpg 32, HW = 63: channel rows not 16-byte aligned
+    (1, 66, 2, 6, 5),           # cpg 33: a second RED_ROWS pass of one row
+    (1, 40, 1, 6, 5),           # cpg 40
+    (1, 64, 2, 17, 16),         # cpg 32, N = 8704: the split form under the default plan
+]
+# shape -> the slice count the plan must give: lanes 32 .. 63 of the folding wave carry data
+SLICE_SHAPES = {
+    (1, 33, 1, 80, 50): 33,     # N = 132 000, cpg 33 (two RED_ROWS passes); L = HW = 4000: every slice is one whole channel row
+    (1, 33, 1, 81, 50): 33,     # N = 133 650, L = 4052 > HW = 4050: slices cross channel rows, the last one ragged
+    (1, 4, 1, 260, 253): 64,    # N = 263 120: 64 by the clamp, slices of 4112 > GN_SLICE_MIN floats, the last one ragged (4064)
+    (1, 4, 1, 261, 253): 64,    # N = 264 132, HW odd: no 16-byte aligned channel row after the first
+}
+NEW_SHAPES = WIDE_SHAPES + RED_SHAPES + list(SLICE_SHAPES)
+ALL_SHAPES = SHAPES + NEW_SHAPES
+SPLIT_BY_PLAN = [SHAPES[-1], RED_SHAPES[-1]] + list(SLICE_SHAPES)          # N above the one-pass form's default limit
+IDS = ["x".join(str(v) for v in s) for s in ALL_SHAPES]
 EDGE_SHAPES = [SHAPES[3], SHAPES[0]]
+RED_ROWS, GN_SLICE_MIN, GN_SPLIT_MAX = 32, 4096, 64                        # csrc/gn_grad.hip's (test_the_new_shapes_... reads them there)
 DEV = "cuda:0"
 NAN = float("nan")
 EPS = 1e-5
@@ -62,7 +93,7 @@ def _lib():
 
 def make_inputs(shape, shift, seed=0):
     B, Cn, groups, H, W = shape
-    base = 9000 + 10 * SHAPES.index(shape) + 1000 * seed
+    base = 9000 + 10 * ALL_SHAPES.index(shape) + 1000 * seed
     n = lambda s, k: torch.from_numpy(synth.hash_normal(s, base + k))            # noqa: E731
     return dict(x=n((B, Cn, H, W), 0), gamma=1 + 0.3 * n((Cn,), 1), beta=0.3 * n((Cn,), 2),
                 shift=0.5 * n((B, Cn), 3) if shift else None, dy=n((B, Cn, H, W), 4))
@@ -209,8 +240,23 @@ def agree(got, other, ref, what, tag):
     assert d <= 2 * M_ELEM * max(1.0, q32), ("the two forms differ", what, tag, d)
 
 
-CASES = [(s, act, shift) for s in SHAPES for act in (0, 1) for shift in (False, True)]
-CASE_IDS = ["%s-act%d-%s" % (IDS[SHAPES.index(s)], act, "shift" if shift else "noshift") for s, act, shift in CASES]
+CASES = [(s, act, shift) for s in ALL_SHAPES for act in (0, 1) for shift in (False, True)]
+CASE_IDS = ["%s-act%d-%s" % (IDS[ALL_SHAPES.index(s)], act, "shift" if shift else "noshift") for s, act, shift in CASES]
+
+
+def slice_len(shape, split):
+    """Floats per slice as the plan cuts a group: whole float4 runs, ceil(ceil(N / 4) / split) of them."""
+    N = shape[1] // shape[2] * shape[3] * shape[4]
+    nv = (N + 3) // 4
+    return (nv + split - 1) // split * 4
+
+
+def branch(shape):
+    """What the library's plan query says the run of `shape` is, under the option in force, as text for the test's output."""
+    form, split = plan_of(shape)
+    cpg = shape[1] // shape[2]
+    text = "cpg %d (%d RED_ROWS pass%s) %s" % (cpg, -(-cpg // RED_ROWS), "" if cpg <= RED_ROWS else "es", "split" if form else "one pass")
+    return text + (", %d slices of %d floats" % (split, slice_len(shape, split)) if form else "")
 
 
 def test_the_split_runs_have_ragged_slices_and_the_last_shape_is_split_by_the_plan():
@@ -223,6 +269,44 @@ def test_the_split_runs_have_ragged_slices_and_the_last_shape_is_split_by_the_pl
     assert ragged, plans
 
 
+def test_the_new_shapes_take_the_branches_they_are_there_for():
+    """The widths, RED_ROWS passes and slice counts the shapes added for them really have, from the library's plan query and
+    the constants in the source: a later change of a constant must not turn one of them into a duplicate of an old shape."""
+    import os
+    import re
+    from ipdm_pytorch_amd.train import gn_groups
+    L = _lib()
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ipdm-pytorch_amd", "csrc", "gn_grad.hip")) as f:
+        src = f.read()
+    const = lambda name: int(re.search(r"constexpr \w+ %s = (\d+);" % name, src).group(1))            # noqa: E731
+    assert (const("RED_ROWS"), const("GN_SLICE_MIN"), const("GN_SPLIT_MAX")) == (RED_ROWS, GN_SLICE_MIN, GN_SPLIT_MAX)
+    cpg = lambda s: s[1] // s[2]                                                                     # noqa: E731
+    assert [cpg(s) for s in SHAPES] == [1, 1, 1, 2, 3, 4, 5, 1, 2]                                   # what was covered before
+    assert all(gn_groups(s[1]) == s[2] for s in SHAPES + WIDE_SHAPES) and [cpg(s) for s in WIDE_SHAPES] == [8, 16, 24, RED_ROWS]
+    assert [cpg(s) for s in RED_SHAPES] == [RED_ROWS, RED_ROWS + 1, 40, RED_ROWS]
+    assert [plan_of(s)[0] for s in WIDE_SHAPES + RED_SHAPES] == [0] * 7 + [1]
+    assert any(cpg(s) > RED_ROWS and plan_of(s)[0] == 0 for s in RED_SHAPES)                         # a second pass in the one-pass kernel
+    for shape, want in SLICE_SHAPES.items():
+        form, split = plan_of(shape)
+        N, Ls = cpg(shape) * shape[3] * shape[4], slice_len(shape, want)
+        assert (form, split) == (1, want) and GN_SPLIT_MAX // 2 < split <= GN_SPLIT_MAX, (shape, form, split)
+        assert (split - 1) * Ls < N <= split * Ls                                                    # no empty slice
+        print("gn_grad %s: %s, last slice %d floats" % (IDS[ALL_SHAPES.index(shape)], branch(shape), N - (split - 1) * Ls))
+    a, b, c, d = SLICE_SHAPES
+    assert cpg(a) > RED_ROWS and cpg(b) > RED_ROWS                                                   # two RED_ROWS passes in the split kernel
+    assert slice_len(b, 33) % (b[3] * b[4]) != 0 and 133650 - 32 * slice_len(b, 33) < slice_len(b, 33)   # slices cross rows; ragged
+    for s in (c, d):                                                                                 # 64 by the clamp, not by N / GN_SLICE_MIN
+        N = cpg(s) * s[3] * s[4]
+        assert -(-N // GN_SLICE_MIN) > GN_SPLIT_MAX and slice_len(s, 64) > GN_SLICE_MIN and N % slice_len(s, 64) != 0
+    assert (d[3] * d[4]) % 4 == 1
+    with L.option(OPTION, 1):                                                                        # the split form of the rest
+        for s in WIDE_SHAPES + RED_SHAPES:
+            form, split = plan_of(s)
+            assert form == 1 and split >= 2
+            print("gn_grad %s (split form): %s" % (IDS[ALL_SHAPES.index(s)], branch(s)))
+        assert any(cpg(s) > RED_ROWS and slice_len(s, plan_of(s)[1]) % (s[3] * s[4]) != 0 for s in RED_SHAPES)
+
+
 @pytest.mark.parametrize("shape,act,shift", CASES, ids=CASE_IDS)
 def test_entries_against_float64(shape, act, shift):
     L = _lib()
@@ -233,7 +317,10 @@ def test_entries_against_float64(shape, act, shift):
     for form, value in FORMS.items():
         tag = "%s %s" % (CASE_IDS[CASES.index((shape, act, shift))], form)
         with L.option(OPTION, value):
-            assert plan_of(shape)[0] == (1 if value or shape == SHAPES[-1] else 0)            # the run really took the form
+            assert plan_of(shape)[0] == (1 if value or shape in SPLIT_BY_PLAN else 0)        # the run really took the form
+            assert shape not in SLICE_SHAPES or plan_of(shape) == (1, SLICE_SHAPES[shape])
+            if shape in NEW_SHAPES:
+                print("gn_grad %s %s: %s" % (IDS[ALL_SHAPES.index(shape)], form, branch(shape)))
             out = outs[form] = run_all(d, groups, act)
             gate_outputs(out, ref, shape, tag)
             # two identical calls are bit-equal, for all five outputs (and the statistics)
@@ -253,7 +340,7 @@ def test_entries_against_float64(shape, act, shift):
             agree(outs["plan"][k], outs["split"][k], ref[k], k, CASE_IDS[CASES.index((shape, act, shift))])
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+@pytest.mark.parametrize("shape", ALL_SHAPES, ids=IDS)
 def test_rows_of_a_batch_have_the_bits_of_single_row_calls(shape):
     L = _lib()
     groups = shape[2]
