@@ -531,6 +531,13 @@ int ipdm_art_plan_create(const ipdm_art_geom *geom, const float *lut_area_host, 
                          ipdm_art_plan **out);
 int ipdm_art_plan_destroy(ipdm_art_plan *plan);
 size_t ipdm_art_workspace_bytes(const ipdm_art_plan *plan, int32_t B);
+/* host-only plan query (no launch, nothing written to the plan): out = {1 when a sweep of ipdm_art_reconstruct is ONE launch
+ * now (0: one launch per view -- the option art_per_view, a grid that does not fit the device, or a grid barrier that expired
+ * in an earlier call of this plan), 16x16-pixel tiles of the grid, groups of the one-launch sweep's grid barrier, tiles in
+ * its last group, bins of a tile's LDS window, slices one launch carries}.  A test reads from it which code a geometry
+ * reaches, and that a reconstruction stayed in the one-launch form.  IPDM_ABI_VERSION stays 5: an additive entry, detected by
+ * symbol. */
+int32_t ipdm_art_plan_info(const ipdm_art_plan *plan, int32_t out[6]);
 /* recons_torch(h_proj, lut_area, betas, nstart, ntv, sample_rate, permute): d_proj [B, na, nr] -> d_volume [B, ny, nx]
  * (NOT permuted: the caller applies permute(0,2,1) as a view, PyAPI.cpp:55-57).  sample_rate > 1 uses the first
  * na / sample_rate views and rows, as the reference does (PyAPI.cpp:37).  Every launch is on `stream` and all scalars

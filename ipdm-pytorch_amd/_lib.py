@@ -155,6 +155,7 @@ PROTOTYPES = {
     "ipdm_art_plan_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "ipdm_art_plan_destroy": (C.c_int, [_vp]),
     "ipdm_art_workspace_bytes": (C.c_size_t, [_vp, _i32]),
+    "ipdm_art_plan_info": (_i32, [_vp, C.POINTER(_i32 * 6)]),
     "ipdm_art_reconstruct": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),
     "ipdm_art_project": (C.c_int, [_vp, _vp, _vp, _i32, _vp, C.c_size_t, _vp]),
     "ipdm_metrics_plan_create": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),

@@ -84,6 +84,13 @@ class ArtPlan:
         except Exception:
             pass
 
+    def info(self):
+        """ipdm_art_plan_info (host only): the sweep form the plan runs now and the static shape of its grid.
+        one_launch turns 0 for good when a grid barrier of this plan expired (the reconstruction was redone per view)."""
+        out = (_i32 * 6)()
+        call("ipdm_art_plan_info", self._plan, C.byref(out))
+        return dict(zip(("one_launch", "tiles", "groups", "last_group", "win", "bmax"), (int(v) for v in out)))
+
     def _workspace(self, B):
         need = lib().ipdm_art_workspace_bytes(self._plan, B)
         if self._ws is None or self._ws.numel() < need:

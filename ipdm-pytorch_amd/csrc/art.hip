@@ -713,6 +713,21 @@ extern "C" int ipdm_art_plan_destroy(ipdm_art_plan *p)
     return IPDM_OK;
 }
 
+// host-only plan query: which sweep form the plan runs now, and the static shape of its grid, barrier and windows
+extern "C" int32_t ipdm_art_plan_info(const ipdm_art_plan *p, int32_t out[6])
+{
+    IPDM_REQUIRE(p && out, "ipdm_art_plan_info: NULL pointer (plan, out)");
+    const int tiles = cdiv(p->c.nx, 16) * cdiv(p->c.ny, 16);
+    const int groups = cdiv(tiles, SYNC_GROUP);
+    out[0] = p->persistent_ok ? 1 : 0;
+    out[1] = tiles;
+    out[2] = groups;
+    out[3] = tiles - (groups - 1) * SYNC_GROUP;
+    out[4] = WIN;
+    out[5] = BMAX;
+    return IPDM_OK;
+}
+
 namespace {
 constexpr int SQ_BLOCKS = 64;
 struct ArtWs {

@@ -1,7 +1,8 @@
 """GPU parity of the "ART" convertor: HIP SART / forward projector through the C ABI against the
 CPU oracle's sequential restatement of Recon/TASART2DNSL0-Cpp/TASART2DNSL0.cu on small geometries, and -- at the
 reference's full 512x512 / 2000x912 geometry -- through properties: projection -> FBP (the pinned convertor)
-reproduces the phantom, projection -> SART round trip, bit-reproducibility, batch == per-slice.
+reproduces the phantom, projection -> SART round trip, bit-reproducibility, batch == per-slice.  The second half of the
+file runs the geometries of tests/_art_cases.py, each chosen for code the small square ones cannot reach.
 
 The ART oracle is "parity unpinned" (the CUDA reference cannot run here, oracle/art_oracle.c); its two data tables
 are pinned on the reference's files."""
@@ -225,3 +226,217 @@ def test_drop_in_art_convertor():
     out, ns = den.proj_denoiser(den.ldproj, save_state=False)           # only_convertor: ART of the input
     assert tuple(out.shape) == (1, 1, 512, 512) and ns is None
     assert np.sqrt(((out[0, 0].numpy() - mu) ** 2).mean()) <= 0.02 * mu.max()
+
+
+# ------------------------------------------------------------------------------- geometries chosen for the code they reach
+# tests/_art_cases.py: W (a tile spans more bins than its LDS window: the three direct-to-global scatter arms and both
+# out-of-window correction fallbacks), R (non-square, ragged tiles, image offsets, angle_start), G (35 tiles: two groups of
+# the grid barrier, 32 + 3), S (the old geometry, as control).  Every case proves on the host that its geometry reaches that
+# code (window span, plan.info()) and, in the default form, that the plan was in the one-launch form before AND after: an
+# expired grid barrier redoes the reconstruction with one launch per view and hands back correct numbers, so only the plan
+# can tell.  The parity bound of a geometry is 5e-5 max(1, D(g) / D(S)), D the oracle's own deviation under a one-ulp move of
+# every view angle (tests/_art_cases.sensitivity).
+from tests import _art_cases as ac  # noqa: E402
+
+NEW = ("W", "R", "G")
+_CASE_PLANS = {}
+
+
+def _case_plan(tag, per_view=False):
+    """One plan per geometry and sweep form for the whole module (the form is read at plan creation)."""
+    from ipdm_pytorch_amd import _lib
+    if (tag, per_view) not in _CASE_PLANS:
+        g, _, lut, betas = ac.case(tag)
+        with _lib.option("art_per_view", 1 if per_view else 0):
+            _CASE_PLANS[tag, per_view] = art.ArtPlan(lut, betas, device=DEV, geom=g)
+    return _CASE_PLANS[tag, per_view]
+
+
+def _prove(tag, plan, per_view=False):
+    """The code this geometry was chosen for is the code the plan runs."""
+    g, span, info = ac.case(tag)[0], ac.span(tag), plan.info()
+    print("\n[%s] %dx%d nr %d na %d: span %d, info %s" % (tag, g.nx, g.ny, g.nr, g.na, span, info))
+    assert info["win"] == ac.WIN and info["bmax"] == ac.BMAX and info["tiles"] == ac.tiles(g)
+    assert info["groups"] == -(-info["tiles"] // ac.SYNC_GROUP)
+    assert info["last_group"] == info["tiles"] - (info["groups"] - 1) * ac.SYNC_GROUP
+    assert info["one_launch"] == (0 if per_view else 1), "the plan left the one-launch form: a grid barrier expired"
+    if tag == "W":
+        assert info["win"] == 64 < span
+    else:
+        assert span <= 60 < info["win"]
+    if tag == "G":
+        assert (info["tiles"], info["groups"], info["last_group"]) == (35, 2, 3)
+    if tag == "R":
+        assert info["tiles"] == 15 and g.nx != g.ny
+    return info
+
+
+def _t(a):
+    return torch.tensor(np.asarray(a))
+
+
+def _rel(got, want):
+    return float(np.abs(got - want).max() / np.abs(want).max())
+
+
+@pytest.mark.parametrize("tag", NEW)
+def test_project_geometries_vs_oracle(tag):
+    plan = _case_plan(tag)
+    _prove(tag, plan)
+    want = ac.oracle_project(tag)
+    got = plan.project_device(_t(ac.project_inputs(tag))).cpu().numpy()
+    bound, err = ac.bounds(tag)[0], _rel(got, want)
+    print("[%s] project: D %.2e (S %.2e) bound %.2e achieved %.2e" % (tag, ac.sensitivity(tag)[0], ac.sensitivity("S")[0], bound, err))
+    assert got.shape == want.shape and (want[1] < 0).any()
+    assert err <= bound, (err, bound)
+
+
+@pytest.mark.parametrize("per_view", [False, True])
+@pytest.mark.parametrize("nsart", [1, 3])
+@pytest.mark.parametrize("tag", NEW)
+def test_reconstruct_geometries_vs_oracle(tag, nsart, per_view):
+    plan = _case_plan(tag, per_view)
+    _prove(tag, plan, per_view)
+    want = ac.oracle_reconstruct(tag, nsart, 0)
+    got = plan.reconstruct_device(_t(ac.recon_inputs(tag)[1]), nsart, 0).cpu().numpy()
+    _prove(tag, plan, per_view)                      # ... and it still is: no barrier expired on the way
+    bound, err = ac.bounds(tag)[1], _rel(got, want)
+    print("[%s] reconstruct(%d, 0) %s: D %.2e (S %.2e) bound %.2e achieved %.2e"
+          % (tag, nsart, "per view" if per_view else "one launch", ac.sensitivity(tag)[1], ac.sensitivity("S")[1], bound, err))
+    assert err <= bound, (err, bound)
+
+
+@pytest.mark.parametrize("per_view", [False, True])
+def test_reconstruct_tv_on_the_non_square_grid(per_view):
+    """The TV criterion of test_reconstruct_small_vs_oracle carries over to R: under equal sinogram noise (5e-6 of the maximum)
+    the oracle's own TV response there is max 1.5e-3, mean 5.9e-6 of scale, below S (1.9e-3, 6.6e-6).  (Not to G: 5.7e-3 by the
+    same probe, above the criterion with no device involved.)"""
+    plan = _case_plan("R", per_view)
+    _prove("R", plan, per_view)
+    want = ac.oracle_reconstruct("R", 3, 2)
+    got = plan.reconstruct_device(_t(ac.recon_inputs("R")[1]), 3, 2).cpu().numpy()
+    _prove("R", plan, per_view)
+    err, scale = np.abs(got - want), np.abs(want).max()
+    print("[R] reconstruct(3, 2): mean %.2e max %.2e of scale" % (err.mean() / scale, err.max() / scale))
+    assert err.mean() <= 1e-5 * scale and err.max() <= 5e-3 * scale, (err.mean(), err.max(), scale)
+
+
+@pytest.mark.parametrize("tag", NEW)
+def test_geometries_bits(tag):
+    """Two calls, the two sweep forms, and a batch against its slices run alone: the same bits."""
+    plan, plan_pv = _case_plan(tag), _case_plan(tag, True)
+    _prove(tag, plan)
+    proj = _t(ac.recon_inputs(tag)[1]).to(DEV)
+    a = plan.reconstruct_device(proj, 2, 1)
+    assert torch.equal(plan.reconstruct_device(proj, 2, 1), a)
+    assert torch.equal(plan_pv.reconstruct_device(proj, 2, 1), a)
+    for i in (0, proj.shape[0] - 1):
+        assert torch.equal(plan.reconstruct_device(proj[i:i + 1], 2, 1), a[i:i + 1]), i
+        assert torch.equal(plan_pv.reconstruct_device(proj[i:i + 1], 2, 1), a[i:i + 1]), i
+    _prove(tag, plan)
+    _prove(tag, plan_pv, True)
+    assert bool(torch.isfinite(a).all()) and float(a.max()) > 0.1
+
+
+def test_full_one_launch_equals_per_view_bits(full_plan):
+    """At the reference's 512x512 / 2000x912 geometry (1024 tiles, 32 full barrier groups) the one-launch sweep computes the bits of
+    one launch per view, and stayed one launch."""
+    from ipdm_pytorch_amd import _lib
+    info = full_plan.info()
+    assert (info["one_launch"], info["tiles"], info["groups"], info["last_group"]) == (1, 1024, 32, 32), info
+    mu = np.stack([synth.rasterize(synth.ellipse_phantom(s)).astype(np.float32) for s in (6, 8)])
+    sino = full_plan.project_device(torch.from_numpy(mu))
+    a = full_plan.reconstruct_device(sino, 1, 0)
+    assert full_plan.info()["one_launch"] == 1, "a grid barrier expired: the reconstruction was redone per view"
+    with _lib.option("art_per_view", 1):
+        plan_pv = art.ArtPlan(art.area_lut(), art.view_angles(), device=DEV)
+    assert plan_pv.info()["one_launch"] == 0
+    assert torch.equal(plan_pv.reconstruct_device(sino, 1, 0), a)
+    assert bool(torch.isfinite(a).all()) and float(a.max()) > 0.1 * float(mu.max())
+
+
+@pytest.mark.parametrize("tag", ["S", "W"])
+def test_project_across_the_slice_chunk(tag):
+    """B = 9 is projected as 8 + 1 slices: every slice has the bits of its single-slice call, and the first slice, the last of the
+    first chunk and the one behind it pass the oracle gate."""
+    g, go, lut, betas = ac.case(tag)
+    plan = _case_plan(tag)
+    _prove(tag, plan)
+    vol = ac.phantoms(9, g.nx, g.ny, negative=8)
+    got = plan.project_device(torch.from_numpy(vol))
+    for i in range(9):
+        assert torch.equal(plan.project_device(torch.from_numpy(vol[i:i + 1])), got[i:i + 1]), i
+    want = oa.project(go, lut, betas, vol[[0, 7, 8]])
+    bound, err = ac.bounds(tag)[0], _rel(got[[0, 7, 8]].cpu().numpy(), want)
+    print("[%s] project B = 9, slices 0, 7, 8: bound %.2e achieved %.2e" % (tag, bound, err))
+    assert err <= bound, (err, bound)
+    assert all(np.abs(want[i]).max() > 1.0 for i in range(3))           # (three real projections, each gated by the maximum of all)
+
+
+@pytest.mark.parametrize("per_view", [False, True])
+def test_zero_sweeps_return_zeros(per_view):
+    """nsart = 0: the start volume, zero, into an output prefilled with NaN."""
+    from ipdm_pytorch_amd import _lib
+    g = ac.case("R")[0]
+    plan = _case_plan("R", per_view)
+    proj = _t(ac.recon_inputs("R")[1]).to(DEV)
+    out = torch.full((3, g.ny, g.nx), float("nan"), device=DEV)
+    ws = plan._workspace(3)
+    _lib.call("ipdm_art_reconstruct", plan._plan, _lib.ptr(proj), _lib.ptr(out), 3, 0, 4, 1, _lib.ptr(ws), ws.numel(),
+              _lib.current_stream())
+    torch.cuda.synchronize()
+    assert torch.equal(out, torch.zeros_like(out))
+    _prove("R", plan, per_view)
+
+
+def test_tv_steps_after_the_last_sweep_do_not_reach_the_output():
+    """The volume handed back is the one BEFORE the TV steps of the last sweep (x_res, .cu DoReconstruction; oracle/art_oracle.c does
+    the same): reconstruct(1, 4) has the bits of reconstruct(1, 0), while the TV steps of sweep 1 do reach sweep 2 -- the oracle's
+    reconstruct(2, 4) and reconstruct(2, 0) differ by 6e-2 of the maximum."""
+    plan = _case_plan("R")
+    proj = _t(ac.recon_inputs("R")[1]).to(DEV)
+    assert torch.equal(plan.reconstruct_device(proj, 1, 4), plan.reconstruct_device(proj, 1, 0))
+    a, b = plan.reconstruct_device(proj, 2, 4), plan.reconstruct_device(proj, 2, 0)
+    d_dev = float((a - b).abs().max() / b.abs().max())
+    oa_, ob_ = ac.oracle_reconstruct("R", 2, 4), ac.oracle_reconstruct("R", 2, 0)
+    d_cpu = _rel(oa_, ob_)
+    print("[R] reconstruct(2, 4) vs (2, 0): device %.2e oracle %.2e of the maximum" % (d_dev, d_cpu))
+    assert not torch.equal(a, b) and d_cpu >= 5e-2 and d_dev >= 0.5 * d_cpu, (d_dev, d_cpu)
+    _prove("R", plan)
+
+
+def test_sample_rate_in_both_forms():
+    """sample_rate = 2 (the first na / 2 views, rows of the full sinogram): the per-view form has the bits of the one-launch form,
+    and both are the oracle's reconstruction from those views."""
+    g, go, lut, betas = ac.case("R")
+    plan, plan_pv = _case_plan("R"), _case_plan("R", True)
+    proj = ac.recon_inputs("R")[1]
+    a = plan.reconstruct_device(_t(proj), 3, 0, sample_rate=2)
+    assert torch.equal(plan_pv.reconstruct_device(_t(proj), 3, 0, sample_rate=2), a)
+    half = g.na // 2
+    want = oa.reconstruct(ac.copy_geom(go, na=half), lut, betas[:half], np.ascontiguousarray(proj[:, :half]), 3, 0, permute=False)
+    bound, err = ac.bounds("R")[1], _rel(a.cpu().numpy(), want)
+    print("[R] reconstruct(3, 0, sample_rate 2): bound %.2e achieved %.2e" % (bound, err))
+    assert err <= bound, (err, bound)
+    _prove("R", plan)
+    # (and half the views are not all of them)
+    assert _rel(a.cpu().numpy(), ac.oracle_reconstruct("R", 3, 0)) > 10 * bound
+
+
+def test_image_offset_is_a_pixel_shift_and_angle_start_a_view_roll():
+    """The two properties tests/test_art_geometry_host.py holds the oracle to, through ipdm_art_project: offsets of (3, -2) pixels
+    project like the volume moved by (+3, -2) pixels on the zero-offset grid (different float32 pixel centres: the project bound);
+    angle_start of 7 view steps gives view v the bits of view v - 7."""
+    g, go, lut, betas, vol, moved = ac.shift_case()
+    zero = art.ArtPlan(lut, betas, device=DEV, geom=g)
+    off = art.ArtPlan(lut, betas, device=DEV, geom=ac.copy_geom(g, offset_x=3 * g.dx, offset_y=-2 * g.dy))
+    roll = art.ArtPlan(lut, betas, device=DEV, geom=ac.copy_geom(g, angle_start=35.0))
+    p_zero, p_moved = zero.project_device(torch.from_numpy(vol)), zero.project_device(torch.from_numpy(moved))
+    p_off, p_roll = off.project_device(torch.from_numpy(vol)), roll.project_device(torch.from_numpy(vol))
+    bound, err = ac.bounds("R")[0], _rel(p_off.cpu().numpy(), p_moved.cpu().numpy())
+    print("[R grid] offset vs shift: bound %.2e achieved %.2e" % (bound, err))
+    assert err <= bound, (err, bound)
+    assert _rel(p_off.cpu().numpy(), p_zero.cpu().numpy()) >= 0.05                     # the offset is not ignored
+    assert torch.equal(p_roll[:, 7:], p_zero[:, :-7]) and not torch.equal(p_roll, p_zero)
+    want = oa.project(go, lut, betas, vol)
+    assert _rel(p_zero.cpu().numpy(), want) <= bound
