@@ -389,6 +389,45 @@ int ipdm_conv2d_dgrad(const float *d_dy, const float *d_w, float *d_dx, int32_t 
 int ipdm_conv2d_wgrad(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
                       int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- the same forward and input gradient on the tuned inference kernels (csrc/conv_tuned.hip), opt-in ----
+ * The wide layers' forward and input gradient through the inference dispatcher (the kernels of ipdm_conv_kernel_code's numbering),
+ * with the packed weight images written on the DEVICE from the live [Cout,Cin,k,k] parameters in front of every launch.  A layer has
+ * two roles: role 0 (fprop) is the layer itself; role 1 (dgrad) is the stride-1 layer w'[ci][co][a][b] = w[co][ci][k-1-a][k-1-b]
+ * (Cin and Cout exchanged, taps mirrored), whose forward on dY is the input gradient.  Arguments are those of ipdm_conv2d_fprop /
+ * ipdm_conv2d_dgrad: Cin, Cout, H, W, ksize, stride describe the LAYER in both roles.  IPDM_ABI_VERSION stays 5: additive entries,
+ * detected by symbol.
+ *
+ * Which layers are taken is a rule of the layer alone, never of the batch: role 0 where ipdm_conv_layout_code(Cout, ksize, stride)
+ * is non-zero (wide 3x3 of either stride, wide 1x1); role 1 for stride-1 layers where ipdm_conv_layout_code(Cin, ksize, 1) is
+ * non-zero.  Everything else stays on ipdm_conv2d_fprop / ipdm_conv2d_dgrad.  The entries reuse the dispatcher, so row b of a batch
+ * has the bits of a call on row b alone, two calls give the same bits, the result of role 0 has the bits of ipdm_op_conv2d on the
+ * same weights, and the options conv_no_wino, wino_v1, wino2_min_tiles, pw_force, conv_no_splitk and conv_bf16x3 act as in inference.
+ * No allocation, no synchronisation: asynchronous on `stream`. */
+/* role 0 = fprop, 1 = dgrad.  Kernel code in ipdm_conv_kernel_code's numbering that the call will run, or 0: the layer is not taken
+ * (narrow in that role; role 1 with stride 2; a size past the kernels' 2 GiB addressing limits), -1 bad argument.  Host only, answers
+ * without a device, honours the option table. */
+int32_t ipdm_conv2d_tuned_code(int32_t role, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride);
+/* d_ws of the two calls below: the image the planned kernel reads + the plan's K-split buffer; 0 where the code is <= 0 */
+size_t ipdm_conv2d_tuned_workspace_bytes(int32_t role, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
+                                         int32_t stride);
+/* Bad arguments (a NULL pointer other than d_b, ksize not in {1,3}, stride not in {1,2}, stride 2 with ksize 1, a size < 1) return
+ * IPDM_ERR_INVALID, a layer whose code is 0 IPDM_ERR_UNSUPPORTED, a short workspace IPDM_ERR_WORKSPACE, all before any launch. */
+int ipdm_conv2d_fprop_tuned(const float *d_x, const float *d_w, const float *d_b, float *d_y, int32_t B, int32_t Cin, int32_t Cout,
+                            int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+int ipdm_conv2d_dgrad_tuned(const float *d_dy, const float *d_w, float *d_dx, int32_t B, int32_t Cin, int32_t Cout, int32_t H,
+                            int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+/* The packers alone (tests, other binders).  image 0 = plain ([cin_pad][k k][cout_pad], cout-interleaved), 1 = wino (U = G g G^T of
+ * the F(2x2,3x3) domain, with the three bf16 terms behind it on the layers conv_bf16x3 takes).  The device packer writes every byte
+ * of the image, padding included, and gives the host packer's image byte for byte. */
+/* bytes of the image of the role's layer; 0: the layer carries no such image (or a bad argument) */
+size_t ipdm_conv_image_bytes(int32_t image, int32_t role, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride);
+/* d_w [Cout,Cin,k,k] (device) -> d_image (device, 16-byte aligned); IPDM_ERR_UNSUPPORTED where ipdm_conv_image_bytes is 0 */
+int ipdm_conv_pack_device(int32_t image, int32_t role, const float *d_w, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride,
+                          void *d_image, void *stream);
+/* the executor's host packer on the role's weights: w_host [Cout,Cin,k,k] -> image_host.  Host only. */
+int ipdm_conv_pack_host(int32_t image, int32_t role, const float *w_host, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride,
+                        void *image_host);
+
 /* ------------------------------------------------------------------ training normalisations ---- */
 /* GroupNorm (+ a per-(sample, channel) shift in front) (+ SiLU) under autograd, one fused operation with its backward
  * (csrc/gn_grad.hip).  Replaces norm_layer (Model/model.py:69-90: nn.GroupNorm, eps 1e-5, affine) where the training step uses

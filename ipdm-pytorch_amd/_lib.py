@@ -126,6 +126,13 @@ PROTOTYPES = {
     "ipdm_conv2d_fprop": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
     "ipdm_conv2d_dgrad": (C.c_int, [_vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
     "ipdm_conv2d_wgrad": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "ipdm_conv2d_tuned_code": (_i32, [_i32] * 8),
+    "ipdm_conv2d_tuned_workspace_bytes": (_sz, [_i32] * 8),
+    "ipdm_conv2d_fprop_tuned": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "ipdm_conv2d_dgrad_tuned": (C.c_int, [_vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "ipdm_conv_image_bytes": (_sz, [_i32] * 6),
+    "ipdm_conv_pack_device": (C.c_int, [_i32, _i32, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "ipdm_conv_pack_host": (C.c_int, [_i32, _i32, _vp] + [_i32] * 4 + [_vp]),
     "ipdm_gn_act_workspace_bytes": (_sz, [_i32] * 4),
     "ipdm_gn_act_plan": (_i32, [_i32, _i32, _i32, C.POINTER(_i32)]),
     "ipdm_gn_act_fprop": (C.c_int, [_vp] * 6 + [_i32] * 4 + [_f64, _i32, _vp, _sz, _vp]),

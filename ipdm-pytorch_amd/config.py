@@ -52,7 +52,7 @@ _FLAGS = [
     ("train_dataset_path_FD_img", str, None, None), ("train_dataset_path_LD_img", str, None, None),
     ("train_dataset_path_FD_proj", str, None, None), ("train_dataset_path_LD_proj", str, None, None),
     ("num_workers", int, 4, None), ("patch", int, [512, 512], "+"), ("patch_per_image", int, 4, None),
-    # where the training step's pieces run (no reference counterpart; the Trainer's defaults): the convolutions ("hip" | "torch"),
+    # where the training step's pieces run (no reference counterpart; the Trainer's defaults): the convolutions ("hip" | "hip_tuned" | "torch"),
     # GroupNorm+SiLU and the attention core ("torch" | "hip"), the optimiser update ("torch" = torch.optim.Adam, "hip" = HipAdam, one
     # launch per step); train_seed seeds the initial weights, the patch offsets, the timesteps and the noise of a run.
     ("conv_backend", str, "hip", None), ("norm_backend", str, "torch", None), ("attn_backend", str, "torch", None),
@@ -60,7 +60,7 @@ _FLAGS = [
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 NORMAL_BACKENDS = ("sklearn", "hip")
-TRAIN_BACKENDS = dict(conv_backend=("hip", "torch"), norm_backend=("torch", "hip"), attn_backend=("torch", "hip"),
+TRAIN_BACKENDS = dict(conv_backend=("hip", "hip_tuned", "torch"), norm_backend=("torch", "hip"), attn_backend=("torch", "hip"),
                       optim_backend=("torch", "hip"))
 
 

@@ -14,7 +14,10 @@
               through attention.  The time-embedding Linears, the nearest resize, the concatenations and, with
               norm_backend="torch" / attn_backend="torch" (the defaults), GroupNorm, SiLU and the attention core are torch
               ops.  conv_backend="torch" sends the convolutions through F.conv2d as well: the A/B arm, and with
-              norm_backend="torch" and attn_backend="torch" the only arm that runs on the CPU.
+              norm_backend="torch" and attn_backend="torch" the only arm that runs on the CPU.  conv_backend="hip_tuned"
+              (opt-in) is "hip" with the forward and the input gradient of the wide layers on the inference dispatcher's
+              tuned kernels, their weight images packed on the device (csrc/conv_tuned.hip; conv2d(..., tuned=True));
+              conv_routes(shape) reports which kernel each convolution takes.
   HipAdam     torch.optim.Adam as the reference builds it, with the update of a whole param group as one launch
               (ipdm_adam_step, csrc/adam.hip); state and state_dict() have torch.optim.Adam's layout, so checkpoints move
               between the two in both directions.
@@ -46,7 +49,7 @@ from . import _lib
 from ._lib import IpdmError, call, lib, ptr
 from .unet import UNetModel, make_cfg, param_shapes
 
-CONV_BACKENDS = ("hip", "torch")
+CONV_BACKENDS = ("hip", "hip_tuned", "torch")
 NORM_BACKENDS = ("torch", "hip")
 ATTN_BACKENDS = ("torch", "hip")
 OPTIM_BACKENDS = ("torch", "hip")
@@ -70,9 +73,25 @@ def _workspace(geo, device):
     return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
 
 
+def _tuned_code(role, geo):
+    """ipdm_conv2d_tuned_code: the kernel the tuned entry of `role` (0 fprop, 1 dgrad) will run on this layer, 0 where the layer
+    stays on conv_grad.hip's entry.  A negative answer is an error, never a reason to fall back."""
+    code = lib().ipdm_conv2d_tuned_code(role, *geo)
+    if code < 0:
+        raise IpdmError("ipdm_conv2d_tuned_code failed (%d): %s" % (code, lib().ipdm_last_error().decode()))
+    return code
+
+
+def _tuned_workspace(role, geo, device):
+    need = lib().ipdm_conv2d_tuned_workspace_bytes(role, *geo)
+    if need == 0:
+        raise IpdmError("conv2d: no tuned workspace for a layer whose tuned code is non-zero (role %d, %r)" % (role, geo))
+    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
+
+
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride):
+    def forward(ctx, x, w, b, stride, tuned):
         x, w = x.contiguous(), w.contiguous()
         b = None if b is None else b.contiguous()
         geo = _geometry(x, w, stride)
@@ -80,11 +99,16 @@ class _Conv2d(torch.autograd.Function):
         pad = k // 2
         y = torch.empty((B, Cout, (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            ws = _workspace(geo, x.device)
-            call("ipdm_conv2d_fprop", ptr(x), ptr(w), ptr(b), ptr(y), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                 _lib.current_stream())
+            if tuned and _tuned_code(0, geo):
+                ws = _tuned_workspace(0, geo, x.device)
+                call("ipdm_conv2d_fprop_tuned", ptr(x), ptr(w), ptr(b), ptr(y), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
+                     _lib.current_stream())
+            else:
+                ws = _workspace(geo, x.device)
+                call("ipdm_conv2d_fprop", ptr(x), ptr(w), ptr(b), ptr(y), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
+                     _lib.current_stream())
         ctx.save_for_backward(x, w)
-        ctx.geo, ctx.has_bias = geo, b is not None
+        ctx.geo, ctx.has_bias, ctx.tuned = geo, b is not None, tuned
         return y
 
     @staticmethod
@@ -99,21 +123,31 @@ class _Conv2d(torch.autograd.Function):
             ws = _workspace(ctx.geo, x.device)
             if need_x:
                 dx = torch.empty_like(x)
-                call("ipdm_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                     _lib.current_stream())
+                if ctx.tuned and _tuned_code(1, ctx.geo):
+                    tws = _tuned_workspace(1, ctx.geo, x.device)
+                    call("ipdm_conv2d_dgrad_tuned", ptr(dy), ptr(w), ptr(dx), B, Cin, Cout, H, W, k, s, ptr(tws), tws.numel(),
+                         _lib.current_stream())
+                else:
+                    call("ipdm_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
+                         _lib.current_stream())
             if need_w or need_b:
                 dw = torch.empty_like(w)
                 db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if need_b else None
                 call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
                      _lib.current_stream())
-        return dx, (dw if need_w else None), db, None
+        return dx, (dw if need_w else None), db, None, None
 
 
-def conv2d(x, w, b=None, stride=1):
+def conv2d(x, w, b=None, stride=1, tuned=False):
     """F.conv2d(x, w, b, stride, padding=k // 2) for the reference's layers (k 1 or 3; stride 2 with k 3 only), differentiable
     once: forward, input gradient and weight / bias gradient are HIP kernels on torch's current stream.  Only the gradients
-    autograd asks for are computed (the stem's input gradient, the largest one, never is)."""
-    return _Conv2d.apply(x, w, b, int(stride))
+    autograd asks for are computed (the stem's input gradient, the largest one, never is).
+
+    tuned=True sends the forward and the input gradient of the layers ipdm_conv2d_tuned_code takes (the wide ones) through
+    the inference dispatcher's kernels, their weight images packed on the device in front of each launch
+    (ipdm_conv2d_fprop_tuned / ipdm_conv2d_dgrad_tuned); the layers it answers 0 for, and every weight / bias gradient, stay
+    on the entries above.  A failing query or call raises: there is no fall-back after a failure."""
+    return _Conv2d.apply(x, w, b, int(stride), bool(tuned))
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm (+SiLU) under autograd
@@ -268,8 +302,8 @@ class Conv(nn.Module):
             self.register_parameter("bias", None)
 
     def forward(self, x):
-        if self.backend == "hip":
-            return conv2d(x, self.weight, self.bias, self.stride)
+        if self.backend in ("hip", "hip_tuned"):
+            return conv2d(x, self.weight, self.bias, self.stride, tuned=self.backend == "hip_tuned")
         return F.conv2d(x, self.weight, self.bias, stride=self.stride, padding=self.weight.shape[-1] // 2)
 
 
@@ -430,6 +464,57 @@ class TrainUNet(nn.Module):
         """Reference checkpoints (`module.` removed from the keys, Utils/loggerx.py:131-140) and UNetModel.state_dict()."""
         return super().load_state_dict(collections.OrderedDict((k.replace("module.", ""), torch.as_tensor(v)) for k, v in sd.items()),
                                        strict=strict)
+
+    def conv_routes(self, shape):
+        """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name ->
+        (fprop code, dgrad code), the kernels of ipdm_conv_kernel_code's numbering its forward and input gradient take under
+        conv_backend="hip_tuned"; 0: that pass stays on conv_grad.hip's entry (every pass does under the other backends).
+        Host only: the walk follows forward() on shapes, and the codes come from ipdm_conv2d_tuned_code (option table
+        included)."""
+        B, _, H, W = (int(v) for v in shape)
+        names = {id(m): n for n, m in self.named_modules()}
+        routes = collections.OrderedDict()
+
+        def conv(m, h, w):
+            if self.conv_backend != "hip_tuned":
+                routes[names[id(m)]] = (0, 0)
+                return
+            cout, cin, k = int(m.weight.shape[0]), int(m.weight.shape[1]), int(m.weight.shape[2])
+            geo = (B, cin, cout, h, w, k, int(m.stride))
+            routes[names[id(m)]] = (_tuned_code(0, geo), _tuned_code(1, geo))
+
+        def stage(st, h, w, size):
+            for layer in st:
+                if isinstance(layer, ResBlock):
+                    conv(layer.conv1[2], h, w)
+                    conv(layer.conv2[2], h, w)
+                    if isinstance(layer.shortcut, Conv):
+                        conv(layer.shortcut, h, w)
+                elif isinstance(layer, AttnBlock):
+                    conv(layer.qkv, h, w)
+                    conv(layer.proj, h, w)
+                elif isinstance(layer, Down):
+                    conv(layer.op, h, w)
+                    h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                elif isinstance(layer, Up):
+                    h, w = size
+                    conv(layer.conv, h, w)
+                else:
+                    conv(layer, h, w)
+            return h, w
+
+        hs, h, w = [], H, W
+        for st in self.down_blocks:
+            h, w = stage(st, h, w, None)
+            hs.append((h, w))
+        h, w = stage(self.middle_block, h, w, None)
+        size = hs.pop()
+        for st in self.up_blocks:
+            if hs:
+                size = hs.pop()
+            h, w = stage(st, h, w, size)
+        conv(self.out[2], h, w)
+        return routes
 
     def forward(self, x, t):
         p = self.time_embed[0].weight

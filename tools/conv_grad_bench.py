@@ -5,12 +5,16 @@ TrainUNet by forward hooks on a meta-device forward (no memory, no arithmetic). 
 in one process, device time between two events around `--reps` back-to-back calls, medians over the rounds:
 
   hip    ipdm_conv2d_fprop / ipdm_conv2d_dgrad / ipdm_conv2d_wgrad (with the bias gradient)
+  tuned  ipdm_conv2d_fprop_tuned / ipdm_conv2d_dgrad_tuned (csrc/conv_tuned.hip: the device packer + the inference dispatcher's
+         kernel) on the layers ipdm_conv2d_tuned_code takes -- conv_backend="hip_tuned"; elsewhere that backend runs the hip
+         arm's entry, and the per-step sums say so -- and, as arms of their own, the packer launches alone (pack_fprop, pack_dgrad)
   torch  torch's own convolution on the same device: F.conv2d, and aten.convolution_backward asked for the input gradient
          alone / for the weight and bias gradients alone
 
-and one whole Trainer.step per network under both conv_backend arms (same images, timesteps and draws).
+and one whole Trainer.step per network under the three conv_backend arms (same images, timesteps and draws), with
+norm_backend "torch" and "hip".
 
-    python tools/conv_grad_bench.py --out profiles/r20_conv_grad_bench.json
+    python tools/conv_grad_bench.py --out profiles/r28_conv_grad_bench.json
 """
 import argparse
 import json
@@ -121,26 +125,50 @@ def bench_shape(key, rounds, reps):
         "hip_wgrad": lambda: call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(ws), n, st()),
         "torch_wgrad": lambda: back(dy, x, w, [Cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [False, True, True]),
     }
+    # the tuned entries where the layer rule takes the layer, and the packer launch of each alone
+    codes = [int(lib().ipdm_conv2d_tuned_code(role, *geo)) for role in (0, 1)]
+    if min(codes) < 0:
+        raise _lib.IpdmError("ipdm_conv2d_tuned_code: %s" % lib().ipdm_last_error().decode())
+    keep = []
+    for role, op in ((0, "fprop"), (1, "dgrad")):
+        if not codes[role]:
+            continue
+        tn = lib().ipdm_conv2d_tuned_workspace_bytes(role, *geo)
+        tws = torch.empty(tn, dtype=torch.uint8, device=dev)
+        image = 1 if codes[role] in (1, 2, 9, 12) else 0
+        img = torch.empty(lib().ipdm_conv_image_bytes(image, role, Cin, Cout, k, s), dtype=torch.uint8, device=dev)
+        keep += [tws, img]
+        if role == 0:
+            arms["tuned_fprop"] = lambda tws=tws, tn=tn: call("ipdm_conv2d_fprop_tuned", ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(tws), tn, st())
+        else:
+            arms["tuned_dgrad"] = lambda tws=tws, tn=tn: call("ipdm_conv2d_dgrad_tuned", ptr(dy), ptr(w), ptr(dx), *geo, ptr(tws), tn, st())
+        arms["pack_" + op] = lambda image=image, role=role, img=img: call("ipdm_conv_pack_device", image, role, ptr(w), Cin, Cout, k, s,
+                                                                         ptr(img), st())
     out = take_turns(arms, rounds, reps)
     flop = 2.0 * Cin * Cout * k * k * y.shape[2] * y.shape[3]
     rec = {"shape": list(geo), "family": family(key), "flop_per_pass": flop, "workspace_bytes": int(n),
-           "wgrad_slabs": int(lib().ipdm_conv2d_wgrad_slabs(1, y.shape[2], y.shape[3])), "ms": out}
+           "wgrad_slabs": int(lib().ipdm_conv2d_wgrad_slabs(1, y.shape[2], y.shape[3])), "ms": out,
+           "tuned_codes": {"fprop": codes[0], "dgrad": codes[1]}}
     for op in ("fprop", "dgrad", "wgrad"):
         h, t = out["hip_" + op]["median_ms"], out["torch_" + op]["median_ms"]
         rec["hip_%s_TFLOPs" % op] = flop / (h * 1e-3) / 1e12
         rec["hip_over_torch_%s" % op] = h / t
+        if "tuned_" + op in out:
+            rec["tuned_%s_TFLOPs" % op] = flop / (out["tuned_" + op]["median_ms"] * 1e-3) / 1e12
+            rec["tuned_over_hip_%s" % op] = out["tuned_" + op]["median_ms"] / h
     return rec
 
 
-def bench_steps(opt, domain, rounds):
+def bench_steps(opt, domain, rounds, norm_backend="torch"):
     """One Trainer.step per round and arm, the arms taking turns; host clock around a step that ends in loss.item()."""
     import time
     import torch
     from ipdm_pytorch_amd.train import Trainer
     H, W = SIZES[domain]
     images = torch.rand((1, H, W)) * (4.0 if domain == "proj" else 0.3)
-    arms = {be: Trainer(opt, domain, seed=1, conv_backend=be) for be in ("hip", "torch")}
-    arms["torch"].model.load_state_dict(arms["hip"].model.state_dict())
+    arms = {be: Trainer(opt, domain, seed=1, conv_backend=be, norm_backend=norm_backend) for be in ("hip", "hip_tuned", "torch")}
+    for be in ("hip_tuned", "torch"):
+        arms[be].model.load_state_dict(arms["hip"].model.state_dict())
     z = torch.randn((1, 1, H, W), device=opt.device)
     ms, losses = {be: [] for be in arms}, {be: [] for be in arms}
     for r in range(rounds + 1):                    # round 0: warm-up
@@ -152,10 +180,23 @@ def bench_steps(opt, domain, rounds):
             if r:
                 ms[be].append(1e3 * (time.perf_counter() - t0))
             losses[be].append(loss)
-    return {"size": [H, W], "B": 1, "t": 25,
-            "step_ms": {be: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "n": len(v)} for be, v in ms.items()},
-            "hip_over_torch": statistics.median(ms["hip"]) / statistics.median(ms["torch"]), "losses": losses,
+    med = {be: statistics.median(v) for be, v in ms.items()}
+    spread = (max(ms["hip"]) - min(ms["hip"])) + (max(ms["hip_tuned"]) - min(ms["hip_tuned"]))
+    routes = arms["hip_tuned"].model.conv_routes((1, 1, H, W))
+    return {"size": [H, W], "B": 1, "t": 25, "norm_backend": norm_backend,
+            "step_ms": {be: {"median_ms": med[be], "min_ms": min(v), "max_ms": max(v), "n": len(v)} for be, v in ms.items()},
+            "hip_over_torch": med["hip"] / med["torch"], "tuned_over_torch": med["hip_tuned"] / med["torch"],
+            "tuned_over_hip": med["hip_tuned"] / med["hip"],
+            # the statement of the round: the gain over the hip arm against the two arms' min-to-max spreads added up
+            "gain_ms": med["hip"] - med["hip_tuned"], "spread_ms": spread, "gain_exceeds_spread": med["hip"] - med["hip_tuned"] > spread,
+            "losses": losses, "routes": {k: list(v) for k, v in routes.items()},
             "peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
+
+
+def dump(path, res):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(json.dumps(res, indent=1, sort_keys=True) + "\n")
 
 
 def main():
@@ -183,9 +224,13 @@ def main():
             rec = bench_shape(key, a.rounds, a.reps)
             rec["layers"] = len(names)
             layers.append(rec)
-            print("%s %-28s %-40s fprop %.3f / %.3f ms  dgrad %.3f / %.3f  wgrad %.3f / %.3f  (hip / torch)"
-                  % (d, "x".join(map(str, key)), rec["family"], rec["ms"]["hip_fprop"]["median_ms"], rec["ms"]["torch_fprop"]["median_ms"],
-                     rec["ms"]["hip_dgrad"]["median_ms"], rec["ms"]["torch_dgrad"]["median_ms"], rec["ms"]["hip_wgrad"]["median_ms"],
+            tm = lambda op: rec["ms"]["tuned_" + op]["median_ms"] if "tuned_" + op in rec["ms"] else float("nan")       # noqa: E731
+            pk = lambda op: rec["ms"]["pack_" + op]["median_ms"] if "pack_" + op in rec["ms"] else float("nan")        # noqa: E731
+            print("%s %-28s %-40s fprop %.3f / %.3f [code %d, pack %.3f] / %.3f ms  dgrad %.3f / %.3f [code %d, pack %.3f] / %.3f  "
+                  "wgrad %.3f / %.3f  (hip / tuned / torch)"
+                  % (d, "x".join(map(str, key)), rec["family"], rec["ms"]["hip_fprop"]["median_ms"], tm("fprop"), rec["tuned_codes"]["fprop"],
+                     pk("fprop"), rec["ms"]["torch_fprop"]["median_ms"], rec["ms"]["hip_dgrad"]["median_ms"], tm("dgrad"),
+                     rec["tuned_codes"]["dgrad"], pk("dgrad"), rec["ms"]["torch_dgrad"]["median_ms"], rec["ms"]["hip_wgrad"]["median_ms"],
                      rec["ms"]["torch_wgrad"]["median_ms"]), flush=True)
             torch.cuda.empty_cache()
         net = {"size": list(SIZES[d]), "distinct_shapes": len(layers), "layers": layers, "families": {}}
@@ -196,18 +241,41 @@ def main():
                 h = sum(r["ms"]["hip_" + op]["median_ms"] * r["layers"] for r in rows)
                 t = sum(r["ms"]["torch_" + op]["median_ms"] * r["layers"] for r in rows)
                 f[op] = {"hip_ms_per_step": h, "torch_ms_per_step": t, "hip_over_torch": h / t, "torch_faster": t < h}
+                if op != "wgrad":       # what conv_backend="hip_tuned" runs: the tuned entry where the layer is taken, the hip arm's elsewhere
+                    arm = lambda r: r["ms"]["tuned_" + op if "tuned_" + op in r["ms"] else "hip_" + op]       # noqa: E731
+                    f[op].update(tuned_ms_per_step=sum(arm(r)["median_ms"] * r["layers"] for r in rows),
+                                 tuned_layers=sum(r["layers"] for r in rows if "tuned_" + op in r["ms"]),
+                                 layers=sum(r["layers"] for r in rows),
+                                 pack_ms_per_step=sum(r["ms"]["pack_" + op]["median_ms"] * r["layers"] for r in rows if "pack_" + op in r["ms"]),
+                                 spread_ms=sum((r["ms"]["hip_" + op]["max_ms"] - r["ms"]["hip_" + op]["min_ms"] + arm(r)["max_ms"] - arm(r)["min_ms"])
+                                               * r["layers"] for r in rows))
+                    f[op]["tuned_over_hip"] = f[op]["tuned_ms_per_step"] / h
+                    f[op]["tuned_over_torch"] = f[op]["tuned_ms_per_step"] / t
+            gain = sum(f[op]["hip_ms_per_step"] - f[op]["tuned_ms_per_step"] for op in ("fprop", "dgrad"))
+            spread = sum(f[op]["spread_ms"] for op in ("fprop", "dgrad"))
+            f["fprop_plus_dgrad"] = {"hip_ms_per_step": sum(f[op]["hip_ms_per_step"] for op in ("fprop", "dgrad")),
+                                     "tuned_ms_per_step": sum(f[op]["tuned_ms_per_step"] for op in ("fprop", "dgrad")),
+                                     "torch_ms_per_step": sum(f[op]["torch_ms_per_step"] for op in ("fprop", "dgrad")),
+                                     "pack_ms_per_step": sum(f[op]["pack_ms_per_step"] for op in ("fprop", "dgrad")),
+                                     "gain_ms": gain, "spread_ms": spread, "gain_exceeds_spread": gain > spread}
             net["families"][fam] = f
         res["networks"][d] = net
+        if a.out:
+            dump(a.out + ".partial", res)
     for d in ("img", "proj"):
-        res["networks"][d]["trainer_step"] = bench_steps(opt, d, a.step_rounds)
-        s = res["networks"][d]["trainer_step"]
-        print("%s Trainer.step: hip %.1f ms, torch %.1f ms" % (d, s["step_ms"]["hip"]["median_ms"], s["step_ms"]["torch"]["median_ms"]), flush=True)
-        torch.cuda.empty_cache()
-    text = json.dumps(res, indent=1, sort_keys=True)
+        for nb in ("torch", "hip"):
+            key = "trainer_step" if nb == "torch" else "trainer_step_norm_hip"
+            s = res["networks"][d][key] = bench_steps(opt, d, a.step_rounds, nb)
+            pack = sum(f["fprop_plus_dgrad"]["pack_ms_per_step"] for f in res["networks"][d]["families"].values())
+            s["pack_ms_per_step"], s["pack_share_of_tuned_step"] = pack, pack / s["step_ms"]["hip_tuned"]["median_ms"]
+            print("%s Trainer.step (norm_backend=%s): hip %.1f ms, hip_tuned %.1f ms, torch %.1f ms; packing %.2f ms = %.1f %% of the tuned step"
+                  % (d, nb, s["step_ms"]["hip"]["median_ms"], s["step_ms"]["hip_tuned"]["median_ms"], s["step_ms"]["torch"]["median_ms"],
+                     pack, 100 * s["pack_share_of_tuned_step"]), flush=True)
+            torch.cuda.empty_cache()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+        dump(a.out, res)
+        if os.path.exists(a.out + ".partial"):
+            os.remove(a.out + ".partial")
     for d, net in res["networks"].items():
         print(d, json.dumps(net["families"], sort_keys=True))
 
