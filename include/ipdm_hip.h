@@ -389,6 +389,45 @@ int ipdm_conv2d_dgrad(const float *d_dy, const float *d_w, float *d_dx, int32_t 
 int ipdm_conv2d_wgrad(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
                       int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- the weight / bias gradient on kernels built for the trained layer shapes (csrc/conv_wgrad.hip), opt-in ----
+ * The arguments and the mathematics of ipdm_conv2d_wgrad (the backward of loss.backward(), Utils/train_test_utils.py:268, over
+ * the convolutions of Model/model.py), exact f32 on v_mfma_f32_16x16x4_f32.  IPDM_ABI_VERSION stays 5: additive entries, detected
+ * by symbol.
+ *
+ * Code.  1 streamed (a layer with <= 32 channels on at least one side: every wave of a workgroup owns a quarter of the pixels and
+ *   all accumulator blocks), 2 tiled (both sides wider: every wave owns a quarter of the 32 x 32-channel blocks), 0 not taken.
+ *   The code is a rule of (Cin, Cout, ksize, stride) alone -- the same for every B, H, W -- and is 0 only for a size past the
+ *   launch's addressing limits (more than 2^29 strips, more than 65535 channel groups): no layer of either network is excluded.
+ * Plan.  The output plane is cut into tiles of 256 pixels (TH rows x TW columns); a workgroup walks NT consecutive tiles of the
+ *   (sample, tile row, tile column) order (a strip) for one group of <= 32 output and <= cig input channels, and keeps its f32
+ *   accumulators over them.  A part is one such f32 chain: a wave's (code 1; NT * 64 pixels, part = 4 * strip + wave, the wave
+ *   owning pixels [64 wave, 64 wave + 64) of each tile in row-major tile order) or the workgroup's (code 2; NT * 256 pixels).
+ *   Within a chain the pixels are added in tile order, four consecutive pixels per MFMA.  Every number of the plan is a function
+ *   of the seven arguments alone, never of the device or its CU count: every device gives the same bits, two calls give the same.
+ * Rounding.  The f32 partials [part][Cout][Cin][k][k] (in d_ws) are folded by a second launch in float64: fold lane q of
+ *   the plan's `fold lanes` (8) adds parts q, q + 8, ... in that order, the lane sums are added in lane order, and the result is
+ *   rounded to float32 once.  db: a float64 sum of every wave's quarter tile (4 per strip), folded the same way, rounded
+ *   once.  No atomics, no memset.
+ * Errors.  Those of ipdm_conv2d_wgrad: IPDM_ERR_INVALID (a NULL pointer other than d_db, ksize not in {1,3}, stride not in {1,2},
+ *   stride 2 with ksize 1, a size < 1, a workspace not aligned to 16 bytes), IPDM_ERR_WORKSPACE (short workspace),
+ *   IPDM_ERR_UNSUPPORTED (code 0); all before any launch, with no allocation and no synchronisation.
+ * Bits.  NOT those of ipdm_conv2d_wgrad (another summation order); held to the same float64 gate. */
+/* 1 streamed, 2 tiled, 0 not taken (the layer stays on ipdm_conv2d_wgrad), -1 bad argument.  Host only, answers without a device. */
+int32_t ipdm_conv2d_wgrad_tuned_code(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride);
+/* Host only.  out[0..IPDM_WGRAD_PLAN_FIELDS): code, parts, pixels per part, longest f32 chain (pixels added into one f32
+ * accumulator before it leaves as a partial), TH, TW, NT, strips, output channels per group, input channels per group, output
+ * groups, input groups, tap split (1: the taps are never split), fold lanes.  All 0 for code 0.  Returns the code, -1 for a bad
+ * argument or n < IPDM_WGRAD_PLAN_FIELDS. */
+#define IPDM_WGRAD_PLAN_FIELDS 14
+int32_t ipdm_conv2d_wgrad_tuned_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride,
+                                     int32_t *out, int32_t n);
+/* d_ws of the call below: parts * Cout * Cin * k * k floats (rounded up to 16 bytes) + 4 * strips * Cout doubles; 0 for code <= 0 */
+size_t ipdm_conv2d_wgrad_tuned_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
+                                               int32_t stride);
+/* d_x [B,Cin,H,W], d_dy [B,Cout,Ho,Wo] -> d_dw [Cout,Cin,k,k], d_db [Cout] or NULL */
+int ipdm_conv2d_wgrad_tuned(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
+                            int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- the same forward and input gradient on the tuned inference kernels (csrc/conv_tuned.hip), opt-in ----
  * The wide layers' forward and input gradient through the inference dispatcher (the kernels of ipdm_conv_kernel_code's numbering),
  * with the packed weight images written on the DEVICE from the live [Cout,Cin,k,k] parameters in front of every launch.  A layer has

@@ -57,11 +57,15 @@ _FLAGS = [
     # launch per step); train_seed seeds the initial weights, the patch offsets, the timesteps and the noise of a run.
     ("conv_backend", str, "hip", None), ("norm_backend", str, "torch", None), ("attn_backend", str, "torch", None),
     ("optim_backend", str, "torch", None), ("train_seed", int, 0, None),
+    # the weight / bias gradient of the convolutions: "hip" = ipdm_conv2d_wgrad, "hip_tuned" = the streamed / tiled kernels of
+    # csrc/conv_wgrad.hip where their rule takes the layer (independent of conv_backend "hip" | "hip_tuned"; not with "torch")
+    ("wgrad_backend", str, "hip", None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 NORMAL_BACKENDS = ("sklearn", "hip")
 TRAIN_BACKENDS = dict(conv_backend=("hip", "hip_tuned", "torch"), norm_backend=("torch", "hip"), attn_backend=("torch", "hip"),
                       optim_backend=("torch", "hip"))
+WGRAD_BACKENDS = ("hip", "hip_tuned")
 
 
 def check_metrics_backend(value):
@@ -90,6 +94,20 @@ def check_train_backends(opt):
     return out
 
 
+def check_wgrad_backend(opt):
+    """The wgrad_backend key of a training run: {} at its default (or where the options lack the key), so that a default run
+    hands Trainer the four keywords of check_train_backends alone; {"wgrad_backend": value} otherwise.  An unknown value, and
+    any value but the default beside conv_backend="torch", is refused."""
+    value = getattr(opt, "wgrad_backend", WGRAD_BACKENDS[0])
+    if value not in WGRAD_BACKENDS:
+        raise ValueError("wgrad_backend must be one of %s, not %r" % (WGRAD_BACKENDS, value))
+    if value == WGRAD_BACKENDS[0]:
+        return {}
+    if getattr(opt, "conv_backend", "hip") == "torch":
+        raise ValueError("wgrad_backend=%r needs conv_backend \"hip\" or \"hip_tuned\", not \"torch\"" % (value,))
+    return {"wgrad_backend": value}
+
+
 def default_cfg(argv=None):
     """Config/default_config.py:7-172: argparse defaults, then --load_option_path JSON overlays every
     key that was not given on the command line."""
@@ -104,6 +122,8 @@ def default_cfg(argv=None):
             kw["choices"] = NORMAL_BACKENDS
         if name in TRAIN_BACKENDS:
             kw["choices"] = TRAIN_BACKENDS[name]
+        if name == "wgrad_backend":
+            kw["choices"] = WGRAD_BACKENDS
         parser.add_argument("--" + name, **kw)
     argv = sys.argv[1:] if argv is None else argv
     opt = parser.parse_args(argv)

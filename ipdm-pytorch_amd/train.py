@@ -53,6 +53,7 @@ CONV_BACKENDS = ("hip", "hip_tuned", "torch")
 NORM_BACKENDS = ("torch", "hip")
 ATTN_BACKENDS = ("torch", "hip")
 OPTIM_BACKENDS = ("torch", "hip")
+WGRAD_BACKENDS = ("hip", "hip_tuned")
 
 
 # ------------------------------------------------------------------------------------------------ convolution under autograd
@@ -89,9 +90,25 @@ def _tuned_workspace(role, geo, device):
     return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
 
 
+def _wgrad_code(geo):
+    """ipdm_conv2d_wgrad_tuned_code: 1 (streamed) or 2 (tiled) where csrc/conv_wgrad.hip takes the layer's weight / bias gradient,
+    0 where it stays on ipdm_conv2d_wgrad.  A negative answer is an error, never a reason to fall back."""
+    code = lib().ipdm_conv2d_wgrad_tuned_code(*geo)
+    if code < 0:
+        raise IpdmError("ipdm_conv2d_wgrad_tuned_code failed (%d): %s" % (code, lib().ipdm_last_error().decode()))
+    return code
+
+
+def _wgrad_workspace(geo, device):
+    need = lib().ipdm_conv2d_wgrad_tuned_workspace_bytes(*geo)
+    if need == 0:
+        raise IpdmError("conv2d: no workspace for a layer whose tuned weight-gradient code is non-zero (%r)" % (geo,))
+    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
+
+
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride, tuned):
+    def forward(ctx, x, w, b, stride, tuned, wgrad_tuned=False):
         x, w = x.contiguous(), w.contiguous()
         b = None if b is None else b.contiguous()
         geo = _geometry(x, w, stride)
@@ -108,7 +125,7 @@ class _Conv2d(torch.autograd.Function):
                 call("ipdm_conv2d_fprop", ptr(x), ptr(w), ptr(b), ptr(y), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
                      _lib.current_stream())
         ctx.save_for_backward(x, w)
-        ctx.geo, ctx.has_bias, ctx.tuned = geo, b is not None, tuned
+        ctx.geo, ctx.has_bias, ctx.tuned, ctx.wgrad_tuned = geo, b is not None, tuned, wgrad_tuned
         return y
 
     @staticmethod
@@ -133,12 +150,17 @@ class _Conv2d(torch.autograd.Function):
             if need_w or need_b:
                 dw = torch.empty_like(w)
                 db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if need_b else None
-                call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                     _lib.current_stream())
-        return dx, (dw if need_w else None), db, None, None
+                if ctx.wgrad_tuned and _wgrad_code(ctx.geo):
+                    wws = _wgrad_workspace(ctx.geo, x.device)
+                    call("ipdm_conv2d_wgrad_tuned", ptr(x), ptr(dy), ptr(dw), ptr(db), B, Cin, Cout, H, W, k, s, ptr(wws),
+                         wws.numel(), _lib.current_stream())
+                else:
+                    call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
+                         _lib.current_stream())
+        return dx, (dw if need_w else None), db, None, None, None
 
 
-def conv2d(x, w, b=None, stride=1, tuned=False):
+def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip"):
     """F.conv2d(x, w, b, stride, padding=k // 2) for the reference's layers (k 1 or 3; stride 2 with k 3 only), differentiable
     once: forward, input gradient and weight / bias gradient are HIP kernels on torch's current stream.  Only the gradients
     autograd asks for are computed (the stem's input gradient, the largest one, never is).
@@ -146,8 +168,14 @@ def conv2d(x, w, b=None, stride=1, tuned=False):
     tuned=True sends the forward and the input gradient of the layers ipdm_conv2d_tuned_code takes (the wide ones) through
     the inference dispatcher's kernels, their weight images packed on the device in front of each launch
     (ipdm_conv2d_fprop_tuned / ipdm_conv2d_dgrad_tuned); the layers it answers 0 for, and every weight / bias gradient, stay
-    on the entries above.  A failing query or call raises: there is no fall-back after a failure."""
-    return _Conv2d.apply(x, w, b, int(stride), bool(tuned))
+    on the entries above.  A failing query or call raises: there is no fall-back after a failure.
+
+    wgrad="hip_tuned" (independent of tuned=) sends the weight / bias gradient through ipdm_conv2d_wgrad_tuned (the streamed /
+    tiled kernels of csrc/conv_wgrad.hip) where ipdm_conv2d_wgrad_tuned_code is non-zero, and through ipdm_conv2d_wgrad where it
+    is 0; other bits than wgrad="hip", the same float64 gate.  Again a failing query or call raises."""
+    if wgrad not in WGRAD_BACKENDS:
+        raise ValueError("wgrad must be one of %s, not %r" % (WGRAD_BACKENDS, wgrad))
+    return _Conv2d.apply(x, w, b, int(stride), bool(tuned), wgrad == "hip_tuned")
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm (+SiLU) under autograd
@@ -292,7 +320,7 @@ class Conv(nn.Module):
 
     def __init__(self, cin, cout, k, stride=1, bias=True, backend="hip"):
         super().__init__()
-        self.stride, self.backend = stride, backend
+        self.stride, self.backend, self.wgrad = stride, backend, "hip"      # wgrad: set by TrainUNet(wgrad_backend=...)
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k))
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if bias:
@@ -303,7 +331,7 @@ class Conv(nn.Module):
 
     def forward(self, x):
         if self.backend in ("hip", "hip_tuned"):
-            return conv2d(x, self.weight, self.bias, self.stride, tuned=self.backend == "hip_tuned")
+            return conv2d(x, self.weight, self.bias, self.stride, tuned=self.backend == "hip_tuned", wgrad=self.wgrad)
         return F.conv2d(x, self.weight, self.bias, stride=self.stride, padding=self.weight.shape[-1] // 2)
 
 
@@ -405,7 +433,7 @@ class TrainUNet(nn.Module):
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(8, 16),
                  dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True, num_heads=4, pre_downsample_times=1,
-                 conv_backend="hip", norm_backend="torch", attn_backend="torch"):
+                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip"):
         super().__init__()
         if dropout:
             raise NotImplementedError("dropout is never instantiated by the reference harness (Model/model.py:198)")
@@ -417,6 +445,11 @@ class TrainUNet(nn.Module):
             raise ValueError("norm_backend must be one of %s, not %r" % (NORM_BACKENDS, norm_backend))
         if attn_backend not in ATTN_BACKENDS:
             raise ValueError("attn_backend must be one of %s, not %r" % (ATTN_BACKENDS, attn_backend))
+        if wgrad_backend not in WGRAD_BACKENDS:
+            raise ValueError("wgrad_backend must be one of %s, not %r" % (WGRAD_BACKENDS, wgrad_backend))
+        if wgrad_backend != "hip" and conv_backend == "torch":
+            raise ValueError("wgrad_backend=%r needs conv_backend \"hip\" or \"hip_tuned\": conv_backend=\"torch\" leaves the "
+                             "weight gradient to torch" % (wgrad_backend,))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks, self.num_heads = num_res_blocks, num_heads
         self.attention_resolutions, self.channel_mult = tuple(attention_resolutions), tuple(channel_mult)
@@ -453,6 +486,10 @@ class TrainUNet(nn.Module):
                     ds //= 2
                 self.up_blocks.append(_Stage(layers))
         self.out = nn.Sequential(_norm(ch), nn.SiLU(), Conv(ch, out_channels, 3, backend=be))
+        self.wgrad_backend = wgrad_backend
+        for m in self.modules():
+            if isinstance(m, Conv):
+                m.wgrad = wgrad_backend
 
     def unet_kwargs(self):
         """The constructor arguments of a UNetModel of the same topology."""
@@ -471,17 +508,25 @@ class TrainUNet(nn.Module):
         conv_backend="hip_tuned"; 0: that pass stays on conv_grad.hip's entry (every pass does under the other backends).
         Host only: the walk follows forward() on shapes, and the codes come from ipdm_conv2d_tuned_code (option table
         included)."""
+        tuned = self.conv_backend == "hip_tuned"
+        return self._conv_walk(shape, lambda geo: (_tuned_code(0, geo), _tuned_code(1, geo)) if tuned else (0, 0))
+
+    def wgrad_routes(self, shape):
+        """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name -> the
+        code of its weight / bias gradient under wgrad_backend="hip_tuned" (ipdm_conv2d_wgrad_tuned_code: 1 streamed, 2 tiled;
+        0: the layer stays on ipdm_conv2d_wgrad, as every layer does under the default).  Host only."""
+        tuned = self.wgrad_backend == "hip_tuned"
+        return self._conv_walk(shape, lambda geo: _wgrad_code(geo) if tuned else 0)
+
+    def _conv_walk(self, shape, code):
+        """name -> code((B, Cin, Cout, H, W, k, stride)) of every convolution, the walk following forward() on shapes."""
         B, _, H, W = (int(v) for v in shape)
         names = {id(m): n for n, m in self.named_modules()}
         routes = collections.OrderedDict()
 
         def conv(m, h, w):
-            if self.conv_backend != "hip_tuned":
-                routes[names[id(m)]] = (0, 0)
-                return
             cout, cin, k = int(m.weight.shape[0]), int(m.weight.shape[1]), int(m.weight.shape[2])
-            geo = (B, cin, cout, h, w, k, int(m.stride))
-            routes[names[id(m)]] = (_tuned_code(0, geo), _tuned_code(1, geo))
+            routes[names[id(m)]] = code((B, cin, cout, h, w, k, int(m.stride)))
 
         def stage(st, h, w, size):
             for layer in st:
@@ -723,7 +768,8 @@ class Trainer:
     reference's constructor defaults 2 and 4), that domain's GaussianDiffusion, and Adam as the reference builds it:
     torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip")."""
 
-    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch"):
+    def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch",
+                 wgrad_backend="hip"):
         from .diffusion import GaussianDiffusion, NoiseSource
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
@@ -737,7 +783,8 @@ class Trainer:
         self.device = torch.device(opt.device)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
-            self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend, **kw).to(self.device)
+            self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend,
+                                   wgrad_backend=wgrad_backend, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
         adam = HipAdam if optim_backend == "hip" else torch.optim.Adam
@@ -861,14 +908,14 @@ class progressive_domain_trainer:
     Single process: the reference's train() has no gradient all-reduce either.  The reference has no EMA."""
 
     def __init__(self, opt, result_save_path=None):
-        from .config import check_train_backends
+        from .config import check_train_backends, check_wgrad_backend
         if opt.mode not in ("train_img", "train_proj"):
             raise ValueError("progressive_domain_trainer runs mode 'train_img' or 'train_proj', not %r (progressive_domain_denoiser "
                              "runs the test_* modes)" % (opt.mode,))
         self.opt, self.opt_temp = opt, copy.deepcopy(opt)
         self.domain = "img" if opt.mode == "train_img" else "proj"
         self.rank = 0
-        backends = check_train_backends(opt)
+        backends = dict(check_train_backends(opt), **check_wgrad_backend(opt))
         self.train_seed = int(getattr(opt, "train_seed", 0))
         self.result_save_path = result_save_path
         run = "%s_%s" % (opt.model_name, opt.run_name)

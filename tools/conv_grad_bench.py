@@ -8,15 +8,20 @@ in one process, device time between two events around `--reps` back-to-back call
   tuned  ipdm_conv2d_fprop_tuned / ipdm_conv2d_dgrad_tuned (csrc/conv_tuned.hip: the device packer + the inference dispatcher's
          kernel) on the layers ipdm_conv2d_tuned_code takes -- conv_backend="hip_tuned"; elsewhere that backend runs the hip
          arm's entry, and the per-step sums say so -- and, as arms of their own, the packer launches alone (pack_fprop, pack_dgrad)
+         ipdm_conv2d_wgrad_tuned (csrc/conv_wgrad.hip: the streamed / tiled weight gradient, with the bias gradient) on the
+         layers ipdm_conv2d_wgrad_tuned_code takes -- wgrad_backend="hip_tuned"; on the streamed layers (code 1) also a
+         device-to-device copy of the bytes of X and dY, the floor of a kernel that reads both once (copy_floor)
   torch  torch's own convolution on the same device: F.conv2d, and aten.convolution_backward asked for the input gradient
          alone / for the weight and bias gradients alone
 
 and one whole Trainer.step per network under the three conv_backend arms (same images, timesteps and draws), with
-norm_backend "torch" and "hip".
+norm_backend "torch" and "hip", and under conv_backend="hip_tuned" with wgrad_backend "hip" and "hip_tuned" beside the torch arm.
+--ops restricts the per-layer arms (e.g. --ops wgrad: the weight-gradient arms alone).
 
-    python tools/conv_grad_bench.py --out profiles/r28_conv_grad_bench.json
+    python tools/conv_grad_bench.py --out profiles/r29_conv_grad_bench.json
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -99,7 +104,7 @@ def take_turns(arms, rounds, reps):
     return {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "n": len(v)} for k, v in ms.items()}
 
 
-def bench_shape(key, rounds, reps):
+def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
     import torch
     import torch.nn.functional as F
     from ipdm_pytorch_amd import _lib
@@ -125,13 +130,28 @@ def bench_shape(key, rounds, reps):
         "hip_wgrad": lambda: call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(ws), n, st()),
         "torch_wgrad": lambda: back(dy, x, w, [Cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [False, True, True]),
     }
+    arms = {k: v for k, v in arms.items() if k.split("_")[1] in ops}
+    # the tuned weight gradient where its rule takes the layer, and on the streamed layers the copy of X and dY
+    wcode = int(lib().ipdm_conv2d_wgrad_tuned_code(*geo))
+    if wcode < 0:
+        raise _lib.IpdmError("ipdm_conv2d_wgrad_tuned_code: %s" % lib().ipdm_last_error().decode())
+    wplan = (ctypes.c_int32 * 14)()
+    wn = 0
+    if wcode and "wgrad" in ops:
+        lib().ipdm_conv2d_wgrad_tuned_plan(*geo, wplan, 14)
+        wn = lib().ipdm_conv2d_wgrad_tuned_workspace_bytes(*geo)
+        wws = torch.empty(wn, dtype=torch.uint8, device=dev)
+        arms["tuned_wgrad"] = lambda: call("ipdm_conv2d_wgrad_tuned", ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(wws), wn, st())
+        if wcode == 1:
+            x2, dy2 = torch.empty_like(x), torch.empty_like(dy)
+            arms["copy_floor"] = lambda: (x2.copy_(x), dy2.copy_(dy))
     # the tuned entries where the layer rule takes the layer, and the packer launch of each alone
     codes = [int(lib().ipdm_conv2d_tuned_code(role, *geo)) for role in (0, 1)]
     if min(codes) < 0:
         raise _lib.IpdmError("ipdm_conv2d_tuned_code: %s" % lib().ipdm_last_error().decode())
     keep = []
     for role, op in ((0, "fprop"), (1, "dgrad")):
-        if not codes[role]:
+        if not codes[role] or op not in ops:
             continue
         tn = lib().ipdm_conv2d_tuned_workspace_bytes(role, *geo)
         tws = torch.empty(tn, dtype=torch.uint8, device=dev)
@@ -148,8 +168,16 @@ def bench_shape(key, rounds, reps):
     flop = 2.0 * Cin * Cout * k * k * y.shape[2] * y.shape[3]
     rec = {"shape": list(geo), "family": family(key), "flop_per_pass": flop, "workspace_bytes": int(n),
            "wgrad_slabs": int(lib().ipdm_conv2d_wgrad_slabs(1, y.shape[2], y.shape[3])), "ms": out,
-           "tuned_codes": {"fprop": codes[0], "dgrad": codes[1]}}
-    for op in ("fprop", "dgrad", "wgrad"):
+           "tuned_codes": {"fprop": codes[0], "dgrad": codes[1], "wgrad": wcode}, "wgrad_tuned_workspace_bytes": int(wn),
+           "wgrad_tuned_plan": {"parts": int(wplan[1]), "chain": int(wplan[3]), "TH": int(wplan[4]), "TW": int(wplan[5]), "NT": int(wplan[6]),
+                                "strips": int(wplan[7])}}
+    if "copy_floor" in out:
+        rec["copy_floor_bytes"] = 4 * (x.numel() + dy.numel())
+        rec["copy_floor_GBps"] = 2 * rec["copy_floor_bytes"] / (out["copy_floor"]["median_ms"] * 1e-3) / 1e9       # read + write
+        rec["tuned_wgrad_over_copy_floor"] = out["tuned_wgrad"]["median_ms"] / out["copy_floor"]["median_ms"]
+    if "tuned_wgrad" in out:
+        rec["tuned_over_torch_wgrad"] = out["tuned_wgrad"]["median_ms"] / out["torch_wgrad"]["median_ms"]
+    for op in ops:
         h, t = out["hip_" + op]["median_ms"], out["torch_" + op]["median_ms"]
         rec["hip_%s_TFLOPs" % op] = flop / (h * 1e-3) / 1e12
         rec["hip_over_torch_%s" % op] = h / t
@@ -157,6 +185,40 @@ def bench_shape(key, rounds, reps):
             rec["tuned_%s_TFLOPs" % op] = flop / (out["tuned_" + op]["median_ms"] * 1e-3) / 1e12
             rec["tuned_over_hip_%s" % op] = out["tuned_" + op]["median_ms"] / h
     return rec
+
+
+def bench_wgrad_steps(opt, domain, rounds, norm_backend="torch"):
+    """The same for wgrad_backend off and on under conv_backend="hip_tuned", beside the torch arm."""
+    import time
+    import torch
+    from ipdm_pytorch_amd.train import Trainer
+    H, W = SIZES[domain]
+    images = torch.rand((1, H, W)) * (4.0 if domain == "proj" else 0.3)
+    arms = {"wgrad_hip": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend),
+            "wgrad_hip_tuned": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend, wgrad_backend="hip_tuned"),
+            "torch": Trainer(opt, domain, seed=1, conv_backend="torch", norm_backend=norm_backend)}
+    for be in ("wgrad_hip_tuned", "torch"):
+        arms[be].model.load_state_dict(arms["wgrad_hip"].model.state_dict())
+    z = torch.randn((1, 1, H, W), device=opt.device)
+    ms, losses = {be: [] for be in arms}, {be: [] for be in arms}
+    for r in range(rounds + 1):                    # round 0: warm-up
+        for be, tr in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss = tr.step(images, t=[25], noise=z)
+            torch.cuda.synchronize()
+            if r:
+                ms[be].append(1e3 * (time.perf_counter() - t0))
+            losses[be].append(loss)
+    med = {be: statistics.median(v) for be, v in ms.items()}
+    spread = (max(ms["wgrad_hip"]) - min(ms["wgrad_hip"])) + (max(ms["wgrad_hip_tuned"]) - min(ms["wgrad_hip_tuned"]))
+    routes = arms["wgrad_hip_tuned"].model.wgrad_routes((1, 1, H, W))
+    gain = med["wgrad_hip"] - med["wgrad_hip_tuned"]
+    return {"size": [H, W], "B": 1, "t": 25, "conv_backend": "hip_tuned", "norm_backend": norm_backend,
+            "step_ms": {be: {"median_ms": med[be], "min_ms": min(v), "max_ms": max(v), "n": len(v)} for be, v in ms.items()},
+            "off_over_torch": med["wgrad_hip"] / med["torch"], "on_over_torch": med["wgrad_hip_tuned"] / med["torch"],
+            "gain_ms": gain, "spread_ms": spread, "gain_exceeds_spread": gain > spread,
+            "losses": losses, "routes": dict(routes), "peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
 
 
 def bench_steps(opt, domain, rounds, norm_backend="torch"):
@@ -205,6 +267,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3, help="back-to-back calls per timed interval")
     ap.add_argument("--step-rounds", type=int, default=3)
+    ap.add_argument("--ops", nargs="+", default=["fprop", "dgrad", "wgrad"], choices=["fprop", "dgrad", "wgrad"],
+                    help="the per-layer arms to run")
+    ap.add_argument("--no-conv-steps", action="store_true", help="skip the Trainer.step table of the conv_backend arms")
+    ap.add_argument("--no-steps", action="store_true", help="skip both Trainer.step tables")
     ap.add_argument("--list", action="store_true", help="print the shapes and stop (needs no GPU)")
     a = ap.parse_args()
     import torch
@@ -217,27 +283,28 @@ def main():
         return
     if not torch.cuda.is_available():
         sys.exit("conv_grad_bench needs a GPU: a CPU run measures nothing")
-    res = {"device": torch.cuda.get_device_name(0), "B": 1, "rounds": a.rounds, "reps": a.reps, "networks": {}}
+    res = {"device": torch.cuda.get_device_name(0), "B": 1, "rounds": a.rounds, "reps": a.reps, "ops": list(a.ops), "networks": {}}
     for d in ("img", "proj"):
         layers = []
         for key, names in shapes[d].items():
-            rec = bench_shape(key, a.rounds, a.reps)
+            rec = bench_shape(key, a.rounds, a.reps, tuple(a.ops))
             rec["layers"] = len(names)
             layers.append(rec)
             tm = lambda op: rec["ms"]["tuned_" + op]["median_ms"] if "tuned_" + op in rec["ms"] else float("nan")       # noqa: E731
+            hm = lambda arm: rec["ms"][arm]["median_ms"] if arm in rec["ms"] else float("nan")                       # noqa: E731
             pk = lambda op: rec["ms"]["pack_" + op]["median_ms"] if "pack_" + op in rec["ms"] else float("nan")        # noqa: E731
             print("%s %-28s %-40s fprop %.3f / %.3f [code %d, pack %.3f] / %.3f ms  dgrad %.3f / %.3f [code %d, pack %.3f] / %.3f  "
-                  "wgrad %.3f / %.3f  (hip / tuned / torch)"
-                  % (d, "x".join(map(str, key)), rec["family"], rec["ms"]["hip_fprop"]["median_ms"], tm("fprop"), rec["tuned_codes"]["fprop"],
-                     pk("fprop"), rec["ms"]["torch_fprop"]["median_ms"], rec["ms"]["hip_dgrad"]["median_ms"], tm("dgrad"),
-                     rec["tuned_codes"]["dgrad"], pk("dgrad"), rec["ms"]["torch_dgrad"]["median_ms"], rec["ms"]["hip_wgrad"]["median_ms"],
-                     rec["ms"]["torch_wgrad"]["median_ms"]), flush=True)
+                  "wgrad %.3f / %.3f [code %d, copy floor %.3f] / %.3f  (hip / tuned / torch)"
+                  % (d, "x".join(map(str, key)), rec["family"], hm("hip_fprop"), tm("fprop"), rec["tuned_codes"]["fprop"],
+                     pk("fprop"), hm("torch_fprop"), hm("hip_dgrad"), tm("dgrad"),
+                     rec["tuned_codes"]["dgrad"], pk("dgrad"), hm("torch_dgrad"), hm("hip_wgrad"), tm("wgrad"), rec["tuned_codes"]["wgrad"],
+                     hm("copy_floor"), hm("torch_wgrad")), flush=True)
             torch.cuda.empty_cache()
         net = {"size": list(SIZES[d]), "distinct_shapes": len(layers), "layers": layers, "families": {}}
         for fam in sorted({r["family"] for r in layers}):
             rows = [r for r in layers if r["family"] == fam]
             f = {"shapes": len(rows)}
-            for op in ("fprop", "dgrad", "wgrad"):
+            for op in a.ops:
                 h = sum(r["ms"]["hip_" + op]["median_ms"] * r["layers"] for r in rows)
                 t = sum(r["ms"]["torch_" + op]["median_ms"] * r["layers"] for r in rows)
                 f[op] = {"hip_ms_per_step": h, "torch_ms_per_step": t, "hip_over_torch": h / t, "torch_faster": t < h}
@@ -251,6 +318,23 @@ def main():
                                                * r["layers"] for r in rows))
                     f[op]["tuned_over_hip"] = f[op]["tuned_ms_per_step"] / h
                     f[op]["tuned_over_torch"] = f[op]["tuned_ms_per_step"] / t
+                else:       # what wgrad_backend="hip_tuned" runs: the tuned entry where its rule takes the layer
+                    arm = lambda r: r["ms"]["tuned_wgrad" if "tuned_wgrad" in r["ms"] else "hip_wgrad"]              # noqa: E731
+                    tw = sum(arm(r)["median_ms"] * r["layers"] for r in rows)
+                    sp = sum((r["ms"]["hip_wgrad"]["max_ms"] - r["ms"]["hip_wgrad"]["min_ms"] + arm(r)["max_ms"] - arm(r)["min_ms"])
+                             * r["layers"] for r in rows)
+                    f[op].update(tuned_ms_per_step=tw, tuned_layers=sum(r["layers"] for r in rows if "tuned_wgrad" in r["ms"]),
+                                 layers=sum(r["layers"] for r in rows), tuned_over_hip=tw / h, tuned_over_torch=tw / t,
+                                 gain_ms=h - tw, spread_ms=sp, gain_exceeds_spread=h - tw > sp,
+                                 copy_floor_ms_per_step=sum(r["ms"]["copy_floor"]["median_ms"] * r["layers"] for r in rows if "copy_floor" in r["ms"]),
+                                 streamed_ms_per_step=sum(r["ms"]["tuned_wgrad"]["median_ms"] * r["layers"] for r in rows if "copy_floor" in r["ms"]),
+                                 tiled_flop_per_step=sum(r["flop_per_pass"] * r["layers"] for r in rows if r["tuned_codes"]["wgrad"] == 2),
+                                 tiled_ms_per_step=sum(r["ms"]["tuned_wgrad"]["median_ms"] * r["layers"] for r in rows if r["tuned_codes"]["wgrad"] == 2))
+                    if f[op]["tiled_ms_per_step"] > 0:
+                        f[op]["tiled_TFLOPs"] = f[op]["tiled_flop_per_step"] / (f[op]["tiled_ms_per_step"] * 1e-3) / 1e12
+            if "fprop" not in a.ops or "dgrad" not in a.ops:
+                net["families"][fam] = f
+                continue
             gain = sum(f[op]["hip_ms_per_step"] - f[op]["tuned_ms_per_step"] for op in ("fprop", "dgrad"))
             spread = sum(f[op]["spread_ms"] for op in ("fprop", "dgrad"))
             f["fprop_plus_dgrad"] = {"hip_ms_per_step": sum(f[op]["hip_ms_per_step"] for op in ("fprop", "dgrad")),
@@ -263,6 +347,20 @@ def main():
         if a.out:
             dump(a.out + ".partial", res)
     for d in ("img", "proj"):
+        if a.no_steps:
+            break
+        for nb in ("torch", "hip"):
+            key = "trainer_step_wgrad" if nb == "torch" else "trainer_step_wgrad_norm_hip"
+            s = res["networks"][d][key] = bench_wgrad_steps(opt, d, a.step_rounds, nb)
+            print("%s Trainer.step (conv_backend=hip_tuned, norm_backend=%s): wgrad_backend hip %.1f ms, hip_tuned %.1f ms, torch arm %.1f ms; "
+                  "gain %.1f ms, spread %.1f ms" % (d, nb, s["step_ms"]["wgrad_hip"]["median_ms"], s["step_ms"]["wgrad_hip_tuned"]["median_ms"],
+                                                   s["step_ms"]["torch"]["median_ms"], s["gain_ms"], s["spread_ms"]), flush=True)
+            torch.cuda.empty_cache()
+            if a.out:
+                dump(a.out + ".partial", res)
+    for d in ("img", "proj"):
+        if a.no_steps or a.no_conv_steps or "fprop" not in a.ops or "dgrad" not in a.ops:
+            break
         for nb in ("torch", "hip"):
             key = "trainer_step" if nb == "torch" else "trainer_step_norm_hip"
             s = res["networks"][d][key] = bench_steps(opt, d, a.step_rounds, nb)
