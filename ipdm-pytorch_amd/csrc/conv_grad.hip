@@ -23,6 +23,7 @@
 //   tap, and writes its partial [slab][Cout][Cin][k][k] to workspace with plain stores.  A second kernel folds the slabs in
 //   float64 in slab order and rounds once.  No float atomics anywhere.  db = sum dY per cout: float64, fixed order.
 #include "common.h"
+#include "conv_train.h"
 
 namespace ipdm {
 namespace {
@@ -240,26 +241,11 @@ __global__ __launch_bounds__(CG_THREADS) void conv_grad_bias_kernel(const float 
     if (tid == 0) db[co] = (float)sh[0];
 }
 
-struct Geo {
-    int B, Cin, Cout, H, W, ks, stride, Ho, Wo, T;
-};
-
-// the ABI's argument check of the three calls and the two queries; 0 or IPDM_ERR_INVALID (with the error text set)
-int geometry(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride, Geo *g)
+// the ABI's argument check of the three calls and the workspace query; 0 or IPDM_ERR_INVALID (with the error text set)
+int geometry(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride, TrainConvGeo *g)
 {
-    IPDM_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, "%s: B, Cin, Cout, H, W must be >= 1 (got %d %d %d %d %d)", who,
-                 B, Cin, Cout, H, W);
-    IPDM_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3 (got %d)", who, ksize);
-    IPDM_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2 (got %d)", who, stride);
-    IPDM_REQUIRE(!(stride == 2 && ksize == 1), "%s: stride 2 goes with ksize 3 only (Downsample)", who);
-    const int pad = ksize / 2;
-    g->B = B; g->Cin = Cin; g->Cout = Cout; g->H = H; g->W = W; g->ks = ksize; g->stride = stride;
-    g->Ho = (H + 2 * pad - ksize) / stride + 1;
-    g->Wo = (W + 2 * pad - ksize) / stride + 1;
-    g->T = ksize * ksize;
-    IPDM_REQUIRE((long)Cin * H * W < (1L << 31) && (long)Cout * g->Ho * g->Wo < (1L << 31),
-                 "%s: a sample of more than 2^31 elements is not supported", who);
-    return IPDM_OK;
+    if (int rc = train_conv_geometry(who, B, Cin, Cout, H, W, ksize, stride, g)) return rc;
+    return train_conv_sample_limit(who, *g);
 }
 
 int slab_len_of(long K)
@@ -270,11 +256,11 @@ int slab_len_of(long K)
 }
 int slabs_of(long K) { const int len = slab_len_of(K); return (int)((K + len - 1) / len); }
 
-size_t reorder_bytes(const Geo &g) { return (size_t)g.Cout * g.Cin * g.T * sizeof(float); }
-size_t wgrad_bytes(const Geo &g) { return (size_t)slabs_of((long)g.B * g.Ho * g.Wo) * reorder_bytes(g); }
+size_t reorder_bytes(const TrainConvGeo &g) { return (size_t)g.Cout * g.Cin * g.T * sizeof(float); }
+size_t wgrad_bytes(const TrainConvGeo &g) { return (size_t)slabs_of((long)g.B * g.Ho * g.Wo) * reorder_bytes(g); }
 
 template <int MODE>
-int launch_igemm(const Geo &g, const float *src, const float *w, const float *bias, float *dst, float *wr, hipStream_t st)
+int launch_igemm(const TrainConvGeo &g, const float *src, const float *w, const float *bias, float *dst, float *wr, hipStream_t st)
 {
     const size_t n = (size_t)g.Cout * g.Cin * g.T;
     conv_grad_reorder_kernel<MODE == 1><<<cdiv((long)n, 256), 256, 0, st>>>(w, wr, g.Cin, g.Cout, g.T);
@@ -298,6 +284,30 @@ int launch_igemm(const Geo &g, const float *src, const float *w, const float *bi
 }
 
 }  // namespace
+
+int train_conv_geometry(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride,
+                        TrainConvGeo *g)
+{
+    IPDM_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, "%s: B, Cin, Cout, H, W must be >= 1 (got %d %d %d %d %d)", who,
+                 B, Cin, Cout, H, W);
+    IPDM_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3 (got %d)", who, ksize);
+    IPDM_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2 (got %d)", who, stride);
+    IPDM_REQUIRE(!(stride == 2 && ksize == 1), "%s: stride 2 goes with ksize 3 only (Downsample)", who);
+    const int pad = ksize / 2;
+    g->B = B; g->Cin = Cin; g->Cout = Cout; g->H = H; g->W = W; g->ks = ksize; g->stride = stride;
+    g->Ho = (H + 2 * pad - ksize) / stride + 1;
+    g->Wo = (W + 2 * pad - ksize) / stride + 1;
+    g->T = ksize * ksize;
+    return IPDM_OK;
+}
+
+int train_conv_sample_limit(const char *who, const TrainConvGeo &g)
+{
+    IPDM_REQUIRE((long)g.Cin * g.H * g.W < (1L << 31) && (long)g.Cout * g.Ho * g.Wo < (1L << 31),
+                 "%s: a sample of more than 2^31 elements is not supported", who);
+    return IPDM_OK;
+}
+
 }  // namespace ipdm
 
 using namespace ipdm;
@@ -315,7 +325,7 @@ int32_t ipdm_conv2d_wgrad_slabs(int32_t B, int32_t Ho, int32_t Wo)
 
 size_t ipdm_conv2d_grad_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride)
 {
-    Geo g;
+    TrainConvGeo g;
     if (geometry("ipdm_conv2d_grad_workspace_bytes", B, Cin, Cout, H, W, ksize, stride, &g) != IPDM_OK) return 0;
     const size_t a = reorder_bytes(g), b = wgrad_bytes(g);
     return a > b ? a : b;
@@ -324,7 +334,7 @@ size_t ipdm_conv2d_grad_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, in
 int ipdm_conv2d_fprop(const float *d_x, const float *d_w, const float *d_b, float *d_y, int32_t B, int32_t Cin, int32_t Cout,
                       int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream)
 {
-    Geo g;
+    TrainConvGeo g;
     IPDM_REQUIRE(d_x && d_w && d_y && d_ws, "ipdm_conv2d_fprop: NULL pointer");
     if (int rc = geometry("ipdm_conv2d_fprop", B, Cin, Cout, H, W, ksize, stride, &g)) return rc;
     if (ws_bytes < reorder_bytes(g)) {
@@ -337,7 +347,7 @@ int ipdm_conv2d_fprop(const float *d_x, const float *d_w, const float *d_b, floa
 int ipdm_conv2d_dgrad(const float *d_dy, const float *d_w, float *d_dx, int32_t B, int32_t Cin, int32_t Cout, int32_t H,
                       int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream)
 {
-    Geo g;
+    TrainConvGeo g;
     IPDM_REQUIRE(d_dy && d_w && d_dx && d_ws, "ipdm_conv2d_dgrad: NULL pointer");
     if (int rc = geometry("ipdm_conv2d_dgrad", B, Cin, Cout, H, W, ksize, stride, &g)) return rc;
     if (ws_bytes < reorder_bytes(g)) {
@@ -350,7 +360,7 @@ int ipdm_conv2d_dgrad(const float *d_dy, const float *d_w, float *d_dx, int32_t 
 int ipdm_conv2d_wgrad(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
                       int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream)
 {
-    Geo g;
+    TrainConvGeo g;
     IPDM_REQUIRE(d_x && d_dy && d_dw && d_ws, "ipdm_conv2d_wgrad: NULL pointer");
     if (int rc = geometry("ipdm_conv2d_wgrad", B, Cin, Cout, H, W, ksize, stride, &g)) return rc;
     if (ws_bytes < wgrad_bytes(g)) {

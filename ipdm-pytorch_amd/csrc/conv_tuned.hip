@@ -18,6 +18,7 @@
 // The entries make no allocation and no synchronisation: images and the plan's K-split buffer live in the caller's workspace.
 #include <cstdint>
 #include "conv_layer.h"
+#include "conv_train.h"
 #include "kernel_util.h"      // row_slot
 
 namespace ipdm {
@@ -161,18 +162,15 @@ constexpr int IMG_PLAIN = 0, IMG_WINO = 1;
 int role_of(const char *who, int role, int B, int Cin, int Cout, int H, int W, int ks, int stride, Role *r, bool *taken)
 {
     IPDM_REQUIRE(role == 0 || role == 1, "%s: role must be 0 (fprop) or 1 (dgrad), got %d", who, role);
-    IPDM_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, "%s: B, Cin, Cout, H, W must be >= 1 (got %d %d %d %d %d)", who, B, Cin,
-                 Cout, H, W);
-    IPDM_REQUIRE(ks == 1 || ks == 3, "%s: ksize must be 1 or 3 (got %d)", who, ks);
-    IPDM_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2 (got %d)", who, stride);
-    IPDM_REQUIRE(!(stride == 2 && ks == 1), "%s: stride 2 goes with ksize 3 only (Downsample)", who);
-    r->B = B; r->H = H; r->W = W; r->ks = ks;
-    r->Ci = role ? Cout : Cin; r->Co = role ? Cin : Cout;
-    r->stride = role ? 1 : stride;
-    r->il = conv_weight_interleave(r->Co, ks, r->stride);
+    TrainConvGeo g;
+    if (int rc = train_conv_geometry(who, B, Cin, Cout, H, W, ks, stride, &g)) return rc;
+    r->B = g.B; r->H = g.H; r->W = g.W; r->ks = g.ks;
+    r->Ci = role ? g.Cout : g.Cin; r->Co = role ? g.Cin : g.Cout;
+    r->stride = role ? 1 : g.stride;
+    r->il = conv_weight_interleave(r->Co, r->ks, r->stride);
     r->cout_pad = conv_cout_pad(r->Co, r->il);
-    r->wino_ok = conv_wino_shape_ok(r->Co, r->Ci, ks, r->stride, r->il);
-    *taken = r->il != 0 && !(role == 1 && stride == 2);
+    r->wino_ok = conv_wino_shape_ok(r->Co, r->Ci, r->ks, r->stride, r->il);
+    *taken = r->il != 0 && !(role == 1 && g.stride == 2);
     return IPDM_OK;
 }
 

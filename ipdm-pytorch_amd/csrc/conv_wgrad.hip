@@ -28,6 +28,7 @@
 // 912 or 57 floats start at any alignment.  FOLLOW-UP: the tiled form reaches a third of the f32 MFMA rate; the next stage's
 // loads could be in registers while the current one multiplies, and a 64-cout tile would halve the B reads per MFMA.
 #include "common.h"
+#include "conv_train.h"
 
 namespace ipdm {
 namespace {
@@ -46,7 +47,8 @@ constexpr int WT_SE = 8;                // staging batch of the X window: elemen
 constexpr int WT_DP = 8;                // staging batch of the dY tile: planes per wave (x 4 elements per lane)
 
 struct WPlan {
-    int code, B, Cin, Cout, H, W, Ho, Wo, ks, stride, T;
+    TrainConvGeo g;
+    int code;
     int TW, TH, twlog, XH, XW, XWP, XPS, tiles_x, tiles_y, NT, strips, cig, ncog, ncig, parts, chain;
     long tiles;
     unsigned magic;
@@ -270,20 +272,10 @@ int rule_code(int Cin, int Cout) { return (Cin <= 32 || Cout <= 32) ? 1 : 2; }
 // argument check of the four entries (the geometry of ipdm_conv2d_wgrad) and the plan; IPDM_OK or IPDM_ERR_INVALID
 int make_plan(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride, WPlan *p)
 {
-    IPDM_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, "%s: B, Cin, Cout, H, W must be >= 1 (got %d %d %d %d %d)", who,
-                 B, Cin, Cout, H, W);
-    IPDM_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3 (got %d)", who, ksize);
-    IPDM_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2 (got %d)", who, stride);
-    IPDM_REQUIRE(!(stride == 2 && ksize == 1), "%s: stride 2 goes with ksize 3 only (Downsample)", who);
-    const int pad = ksize / 2;
-    p->B = B; p->Cin = Cin; p->Cout = Cout; p->H = H; p->W = W; p->ks = ksize; p->stride = stride;
-    p->Ho = (H + 2 * pad - ksize) / stride + 1;
-    p->Wo = (W + 2 * pad - ksize) / stride + 1;
-    p->T = ksize * ksize;
-    IPDM_REQUIRE((long)Cin * H * W < (1L << 31) && (long)Cout * p->Ho * p->Wo < (1L << 31),
-                 "%s: a sample of more than 2^31 elements is not supported", who);
+    if (int rc = train_conv_geometry(who, B, Cin, Cout, H, W, ksize, stride, &p->g)) return rc;
+    if (int rc = train_conv_sample_limit(who, p->g)) return rc;
     p->code = rule_code(Cin, Cout);
-    p->TW = p->Wo > 32 ? 64 : p->Wo > 16 ? 32 : 16;
+    p->TW = p->g.Wo > 32 ? 64 : p->g.Wo > 16 ? 32 : 16;
     p->twlog = p->TW == 64 ? 6 : p->TW == 32 ? 5 : 4;
     p->TH = WT_TILE_PIX / p->TW;
     p->XH = (p->TH - 1) * stride + ksize;
@@ -295,8 +287,8 @@ int make_plan(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, 
     p->XPS = p->XH * p->XWP;
     while (p->XPS % 32 != (ksize == 1 ? 4 : stride == 1 ? 18 : 30)) ++p->XPS;
     p->magic = (unsigned)((1ULL << 32) / (unsigned)p->XWP + 1);
-    p->tiles_x = cdiv(p->Wo, p->TW);
-    p->tiles_y = cdiv(p->Ho, p->TH);
+    p->tiles_x = cdiv(p->g.Wo, p->TW);
+    p->tiles_y = cdiv(p->g.Ho, p->TH);
     p->tiles = (long)B * p->tiles_x * p->tiles_y;
     p->cig = ksize == 1 ? 64 : stride == 2 ? 16 : 32;
     p->ncog = cdiv(Cout, WT_COG);
@@ -317,7 +309,7 @@ int make_plan(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, 
     p->parts = p->code == 1 ? 4 * p->strips : p->strips;
     const int nci = Cin < p->cig ? Cin : p->cig, nco = Cout < WT_COG ? Cout : WT_COG;
     p->lds_bytes = ((size_t)(nci + 1) * p->XPS + (size_t)(nco + 1) * WT_DPS) * sizeof(float);
-    p->part_elems = (size_t)Cout * Cin * p->T;
+    p->part_elems = (size_t)Cout * Cin * p->g.T;
     p->db_offset = align_up((size_t)p->parts * p->part_elems * sizeof(float), 16);
     p->ws_bytes = p->db_offset + (size_t)p->strips * 4 * Cout * sizeof(double);
     return IPDM_OK;
@@ -392,7 +384,7 @@ int ipdm_conv2d_wgrad_tuned(const float *d_x, const float *d_dy, float *d_dw, fl
     a.x = d_x; a.dy = d_dy;
     a.part = (float *)d_ws;
     a.dbpart = d_db ? (double *)((char *)d_ws + p.db_offset) : nullptr;
-    a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.Ho = p.Ho; a.Wo = p.Wo;
+    a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.Ho = p.g.Ho; a.Wo = p.g.Wo;
     a.TW = p.TW; a.twlog = p.twlog; a.TH = p.TH; a.XH = p.XH; a.XW = p.XWP; a.XPS = p.XPS;
     a.tiles_x = p.tiles_x; a.tiles_per_sample = p.tiles_x * p.tiles_y; a.NT = p.NT; a.cig = p.cig;
     a.tiles = p.tiles; a.magic = p.magic;

@@ -18,6 +18,8 @@
               (opt-in) is "hip" with the forward and the input gradient of the wide layers on the inference dispatcher's
               tuned kernels, their weight images packed on the device (csrc/conv_tuned.hip; conv2d(..., tuned=True));
               conv_routes(shape) reports which kernel each convolution takes.
+  conv_route  which entry, kernel code and workspace a pass (fprop, dgrad, wgrad) of a layer takes under those options: the one
+              place that decides it, for conv2d, conv_routes / wgrad_routes and tools/conv_grad_bench.py alike.
   HipAdam     torch.optim.Adam as the reference builds it, with the update of a whole param group as one launch
               (ipdm_adam_step, csrc/adam.hip); state and state_dict() have torch.optim.Adam's layout, so checkpoints move
               between the two in both directions.
@@ -67,43 +69,51 @@ def _geometry(x, w, stride):
     return int(B), int(Cin), int(w.shape[0]), int(H), int(W), int(w.shape[2]), int(stride)
 
 
-def _workspace(geo, device):
-    need = lib().ipdm_conv2d_grad_workspace_bytes(*geo)
+def _scratch(nbytes, device):
+    """Uninitialised device bytes for one launch: every workspace of this file (torch's caching allocator)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+ConvRoute = collections.namedtuple("ConvRoute", "entry code workspace_bytes")
+
+# pass -> (conv_grad.hip's entry, the tuned entry, its code query, its workspace query, the queries' leading arguments)
+_CONV_PASSES = {
+    "fprop": ("ipdm_conv2d_fprop", "ipdm_conv2d_fprop_tuned", "ipdm_conv2d_tuned_code", "ipdm_conv2d_tuned_workspace_bytes", (0,)),
+    "dgrad": ("ipdm_conv2d_dgrad", "ipdm_conv2d_dgrad_tuned", "ipdm_conv2d_tuned_code", "ipdm_conv2d_tuned_workspace_bytes", (1,)),
+    "wgrad": ("ipdm_conv2d_wgrad", "ipdm_conv2d_wgrad_tuned", "ipdm_conv2d_wgrad_tuned_code",
+              "ipdm_conv2d_wgrad_tuned_workspace_bytes", ()),
+}
+
+
+def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None):
+    """The entry that runs `pass_` ("fprop", "dgrad" or "wgrad") of the layer geo = (B, Cin, Cout, H, W, k, stride), the kernel code
+    it will take and the workspace it asks for: the one place that knows which of the training convolutions' entries a pass goes to.
+
+    fprop and dgrad go to the tuned entry (csrc/conv_tuned.hip: the inference dispatcher's kernels) where `tuned` is set and
+    ipdm_conv2d_tuned_code of that role is non-zero; wgrad goes to ipdm_conv2d_wgrad_tuned (csrc/conv_wgrad.hip: 1 streamed, 2
+    tiled) where `wgrad_tuned` is set and ipdm_conv2d_wgrad_tuned_code is non-zero.  Every other pass stays on csrc/conv_grad.hip's
+    entry with code 0 and ipdm_conv2d_grad_workspace_bytes, the one size that serves all three of them.  A negative code raises,
+    and so does a workspace of 0 bytes for the entry chosen: a refusal is never a reason to take the other entry.  Nothing is
+    remembered between calls (the tuned codes follow the option table).
+
+    shared: a route of the same layer made just before.  Where it and this one both end on conv_grad.hip's entries its size is
+    taken over unasked -- the backward's two passes then make one query and share one allocation."""
+    default, entry, code_query, bytes_query, lead = _CONV_PASSES[pass_]
+    code = 0
+    if (wgrad_tuned if pass_ == "wgrad" else tuned):
+        code = getattr(lib(), code_query)(*lead, *geo)
+        if code < 0:
+            raise IpdmError("%s failed (%d): %s" % (code_query, code, lib().ipdm_last_error().decode()))
+    if code:
+        need = getattr(lib(), bytes_query)(*lead, *geo)
+    elif shared is not None and shared.code == 0:
+        entry, need = default, shared.workspace_bytes
+    else:
+        entry, bytes_query = default, "ipdm_conv2d_grad_workspace_bytes"
+        need = lib().ipdm_conv2d_grad_workspace_bytes(*geo)
     if need == 0:
-        raise IpdmError("conv2d: %s" % lib().ipdm_last_error().decode())
-    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
-
-
-def _tuned_code(role, geo):
-    """ipdm_conv2d_tuned_code: the kernel the tuned entry of `role` (0 fprop, 1 dgrad) will run on this layer, 0 where the layer
-    stays on conv_grad.hip's entry.  A negative answer is an error, never a reason to fall back."""
-    code = lib().ipdm_conv2d_tuned_code(role, *geo)
-    if code < 0:
-        raise IpdmError("ipdm_conv2d_tuned_code failed (%d): %s" % (code, lib().ipdm_last_error().decode()))
-    return code
-
-
-def _tuned_workspace(role, geo, device):
-    need = lib().ipdm_conv2d_tuned_workspace_bytes(role, *geo)
-    if need == 0:
-        raise IpdmError("conv2d: no tuned workspace for a layer whose tuned code is non-zero (role %d, %r)" % (role, geo))
-    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
-
-
-def _wgrad_code(geo):
-    """ipdm_conv2d_wgrad_tuned_code: 1 (streamed) or 2 (tiled) where csrc/conv_wgrad.hip takes the layer's weight / bias gradient,
-    0 where it stays on ipdm_conv2d_wgrad.  A negative answer is an error, never a reason to fall back."""
-    code = lib().ipdm_conv2d_wgrad_tuned_code(*geo)
-    if code < 0:
-        raise IpdmError("ipdm_conv2d_wgrad_tuned_code failed (%d): %s" % (code, lib().ipdm_last_error().decode()))
-    return code
-
-
-def _wgrad_workspace(geo, device):
-    need = lib().ipdm_conv2d_wgrad_tuned_workspace_bytes(*geo)
-    if need == 0:
-        raise IpdmError("conv2d: no workspace for a layer whose tuned weight-gradient code is non-zero (%r)" % (geo,))
-    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
+        raise IpdmError("conv2d: %s answers 0 bytes for %s of %r: %s" % (bytes_query, entry, geo, lib().ipdm_last_error().decode()))
+    return ConvRoute(entry, code, need)
 
 
 class _Conv2d(torch.autograd.Function):
@@ -116,14 +126,9 @@ class _Conv2d(torch.autograd.Function):
         pad = k // 2
         y = torch.empty((B, Cout, (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            if tuned and _tuned_code(0, geo):
-                ws = _tuned_workspace(0, geo, x.device)
-                call("ipdm_conv2d_fprop_tuned", ptr(x), ptr(w), ptr(b), ptr(y), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                     _lib.current_stream())
-            else:
-                ws = _workspace(geo, x.device)
-                call("ipdm_conv2d_fprop", ptr(x), ptr(w), ptr(b), ptr(y), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                     _lib.current_stream())
+            route = conv_route("fprop", geo, tuned=tuned)
+            ws = _scratch(route.workspace_bytes, x.device)
+            call(route.entry, ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(ws), ws.numel(), _lib.current_stream())
         ctx.save_for_backward(x, w)
         ctx.geo, ctx.has_bias, ctx.tuned, ctx.wgrad_tuned = geo, b is not None, tuned, wgrad_tuned
         return y
@@ -132,31 +137,25 @@ class _Conv2d(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        B, Cin, Cout, H, W, k, s = ctx.geo
+        geo, Cout = ctx.geo, ctx.geo[2]
         dy = dy.contiguous()
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         dx = dw = db = None
         with torch.cuda.device(x.device):
-            ws = _workspace(ctx.geo, x.device)
-            if need_x:
+            dgrad = conv_route("dgrad", geo, tuned=ctx.tuned) if need_x else None
+            wgrad = conv_route("wgrad", geo, wgrad_tuned=ctx.wgrad_tuned, shared=dgrad) if need_w or need_b else None
+            # a workspace per pass that runs; the passes that stay on conv_grad.hip share one (one query sizes it for both)
+            plain = [r for r in (dgrad, wgrad) if r is not None and r.code == 0]
+            plain_ws = _scratch(plain[0].workspace_bytes, x.device) if plain else None
+            if dgrad is not None:
                 dx = torch.empty_like(x)
-                if ctx.tuned and _tuned_code(1, ctx.geo):
-                    tws = _tuned_workspace(1, ctx.geo, x.device)
-                    call("ipdm_conv2d_dgrad_tuned", ptr(dy), ptr(w), ptr(dx), B, Cin, Cout, H, W, k, s, ptr(tws), tws.numel(),
-                         _lib.current_stream())
-                else:
-                    call("ipdm_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                         _lib.current_stream())
-            if need_w or need_b:
+                ws = _scratch(dgrad.workspace_bytes, x.device) if dgrad.code else plain_ws
+                call(dgrad.entry, ptr(dy), ptr(w), ptr(dx), *geo, ptr(ws), ws.numel(), _lib.current_stream())
+            if wgrad is not None:
                 dw = torch.empty_like(w)
                 db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if need_b else None
-                if ctx.wgrad_tuned and _wgrad_code(ctx.geo):
-                    wws = _wgrad_workspace(ctx.geo, x.device)
-                    call("ipdm_conv2d_wgrad_tuned", ptr(x), ptr(dy), ptr(dw), ptr(db), B, Cin, Cout, H, W, k, s, ptr(wws),
-                         wws.numel(), _lib.current_stream())
-                else:
-                    call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), B, Cin, Cout, H, W, k, s, ptr(ws), ws.numel(),
-                         _lib.current_stream())
+                ws = _scratch(wgrad.workspace_bytes, x.device) if wgrad.code else plain_ws
+                call(wgrad.entry, ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(ws), ws.numel(), _lib.current_stream())
         return dx, (dw if need_w else None), db, None, None, None
 
 
@@ -168,11 +167,13 @@ def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip"):
     tuned=True sends the forward and the input gradient of the layers ipdm_conv2d_tuned_code takes (the wide ones) through
     the inference dispatcher's kernels, their weight images packed on the device in front of each launch
     (ipdm_conv2d_fprop_tuned / ipdm_conv2d_dgrad_tuned); the layers it answers 0 for, and every weight / bias gradient, stay
-    on the entries above.  A failing query or call raises: there is no fall-back after a failure.
+    on the entries above.
 
     wgrad="hip_tuned" (independent of tuned=) sends the weight / bias gradient through ipdm_conv2d_wgrad_tuned (the streamed /
     tiled kernels of csrc/conv_wgrad.hip) where ipdm_conv2d_wgrad_tuned_code is non-zero, and through ipdm_conv2d_wgrad where it
-    is 0; other bits than wgrad="hip", the same float64 gate.  Again a failing query or call raises."""
+    is 0; other bits than wgrad="hip", the same float64 gate.
+
+    conv_route decides each pass.  A failing query or call raises: there is no fall-back after a failure."""
     if wgrad not in WGRAD_BACKENDS:
         raise ValueError("wgrad must be one of %s, not %r" % (WGRAD_BACKENDS, wgrad))
     return _Conv2d.apply(x, w, b, int(stride), bool(tuned), wgrad == "hip_tuned")
@@ -183,7 +184,7 @@ def _gn_workspace(geo, device):
     need = lib().ipdm_gn_act_workspace_bytes(*geo)
     if need == 0:
         raise IpdmError("group_norm_act: %s" % lib().ipdm_last_error().decode())
-    return torch.empty(need, dtype=torch.uint8, device=device)       # torch's caching allocator
+    return _scratch(need, device)
 
 
 class _GroupNormAct(torch.autograd.Function):
@@ -273,7 +274,7 @@ class _Attention(torch.autograd.Function):
             need = lib().ipdm_attn_train_workspace_bytes(*ctx.geo)
             if need == 0:
                 raise IpdmError("attention: %s" % lib().ipdm_last_error().decode())
-            ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)       # torch's caching allocator
+            ws = _scratch(need, qkv.device)
             call("ipdm_attn_bgrad", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), *ctx.geo, ptr(ws), ws.numel(),
                  _lib.current_stream())
         return dqkv, None, None
@@ -506,17 +507,16 @@ class TrainUNet(nn.Module):
         """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name ->
         (fprop code, dgrad code), the kernels of ipdm_conv_kernel_code's numbering its forward and input gradient take under
         conv_backend="hip_tuned"; 0: that pass stays on conv_grad.hip's entry (every pass does under the other backends).
-        Host only: the walk follows forward() on shapes, and the codes come from ipdm_conv2d_tuned_code (option table
-        included)."""
+        Host only: the walk follows forward() on shapes, and the codes are conv_route's (option table included)."""
         tuned = self.conv_backend == "hip_tuned"
-        return self._conv_walk(shape, lambda geo: (_tuned_code(0, geo), _tuned_code(1, geo)) if tuned else (0, 0))
+        return self._conv_walk(shape, lambda geo: tuple(conv_route(p, geo, tuned=tuned).code for p in ("fprop", "dgrad")))
 
     def wgrad_routes(self, shape):
         """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name -> the
         code of its weight / bias gradient under wgrad_backend="hip_tuned" (ipdm_conv2d_wgrad_tuned_code: 1 streamed, 2 tiled;
         0: the layer stays on ipdm_conv2d_wgrad, as every layer does under the default).  Host only."""
         tuned = self.wgrad_backend == "hip_tuned"
-        return self._conv_walk(shape, lambda geo: _wgrad_code(geo) if tuned else 0)
+        return self._conv_walk(shape, lambda geo: conv_route("wgrad", geo, wgrad_tuned=tuned).code)
 
     def _conv_walk(self, shape, code):
         """name -> code((B, Cin, Cout, H, W, k, stride)) of every convolution, the walk following forward() on shapes."""

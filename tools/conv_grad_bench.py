@@ -109,6 +109,7 @@ def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
     import torch.nn.functional as F
     from ipdm_pytorch_amd import _lib
     from ipdm_pytorch_amd._lib import call, lib, ptr
+    from ipdm_pytorch_amd.train import conv_route
     Cin, Cout, H, W, k, s = key
     dev, p = "cuda:0", k // 2
     geo = (1, Cin, Cout, H, W, k, s)
@@ -118,57 +119,48 @@ def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
     y = F.conv2d(x, w, b, stride=s, padding=p)
     dy = torch.randn_like(y)
     dx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
-    n = lib().ipdm_conv2d_grad_workspace_bytes(*geo)
-    ws = torch.empty(n, dtype=torch.uint8, device=dev)
     st = _lib.current_stream
     back = torch.ops.aten.convolution_backward
+    operands = {"fprop": (ptr(x), ptr(w), ptr(b), ptr(y)), "dgrad": (ptr(dy), ptr(w), ptr(dx)), "wgrad": (ptr(x), ptr(dy), ptr(dw), ptr(db))}
+
+    def launch(op, route):
+        """One call of the pass through the route's entry, on a workspace of the route's size."""
+        ws = torch.empty(route.workspace_bytes, dtype=torch.uint8, device=dev)
+        return lambda: call(route.entry, *operands[op], *geo, ptr(ws), route.workspace_bytes, st())
+
+    # hip: conv_grad.hip's entries; tuned: what conv_backend="hip_tuned" / wgrad_backend="hip_tuned" run, an arm where that is another entry
+    hip = {op: conv_route(op, geo) for op in ("fprop", "dgrad", "wgrad")}
+    tuned = {op: conv_route(op, geo, tuned=True, wgrad_tuned=True) for op in hip}
     arms = {
-        "hip_fprop": lambda: call("ipdm_conv2d_fprop", ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(ws), n, st()),
+        "hip_fprop": launch("fprop", hip["fprop"]),
         "torch_fprop": lambda: F.conv2d(x, w, b, stride=s, padding=p),
-        "hip_dgrad": lambda: call("ipdm_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), *geo, ptr(ws), n, st()),
+        "hip_dgrad": launch("dgrad", hip["dgrad"]),
         "torch_dgrad": lambda: back(dy, x, w, [Cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [True, False, False]),
-        "hip_wgrad": lambda: call("ipdm_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(ws), n, st()),
+        "hip_wgrad": launch("wgrad", hip["wgrad"]),
         "torch_wgrad": lambda: back(dy, x, w, [Cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [False, True, True]),
     }
     arms = {k: v for k, v in arms.items() if k.split("_")[1] in ops}
-    # the tuned weight gradient where its rule takes the layer, and on the streamed layers the copy of X and dY
-    wcode = int(lib().ipdm_conv2d_wgrad_tuned_code(*geo))
-    if wcode < 0:
-        raise _lib.IpdmError("ipdm_conv2d_wgrad_tuned_code: %s" % lib().ipdm_last_error().decode())
     wplan = (ctypes.c_int32 * 14)()
-    wn = 0
-    if wcode and "wgrad" in ops:
-        lib().ipdm_conv2d_wgrad_tuned_plan(*geo, wplan, 14)
-        wn = lib().ipdm_conv2d_wgrad_tuned_workspace_bytes(*geo)
-        wws = torch.empty(wn, dtype=torch.uint8, device=dev)
-        arms["tuned_wgrad"] = lambda: call("ipdm_conv2d_wgrad_tuned", ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(wws), wn, st())
-        if wcode == 1:
-            x2, dy2 = torch.empty_like(x), torch.empty_like(dy)
-            arms["copy_floor"] = lambda: (x2.copy_(x), dy2.copy_(dy))
-    # the tuned entries where the layer rule takes the layer, and the packer launch of each alone
-    codes = [int(lib().ipdm_conv2d_tuned_code(role, *geo)) for role in (0, 1)]
-    if min(codes) < 0:
-        raise _lib.IpdmError("ipdm_conv2d_tuned_code: %s" % lib().ipdm_last_error().decode())
-    keep = []
-    for role, op in ((0, "fprop"), (1, "dgrad")):
-        if not codes[role] or op not in ops:
+    for role, op in enumerate(("fprop", "dgrad", "wgrad")):
+        if not tuned[op].code or op not in ops:
             continue
-        tn = lib().ipdm_conv2d_tuned_workspace_bytes(role, *geo)
-        tws = torch.empty(tn, dtype=torch.uint8, device=dev)
-        image = 1 if codes[role] in (1, 2, 9, 12) else 0
-        img = torch.empty(lib().ipdm_conv_image_bytes(image, role, Cin, Cout, k, s), dtype=torch.uint8, device=dev)
-        keep += [tws, img]
-        if role == 0:
-            arms["tuned_fprop"] = lambda tws=tws, tn=tn: call("ipdm_conv2d_fprop_tuned", ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(tws), tn, st())
-        else:
-            arms["tuned_dgrad"] = lambda tws=tws, tn=tn: call("ipdm_conv2d_dgrad_tuned", ptr(dy), ptr(w), ptr(dx), *geo, ptr(tws), tn, st())
-        arms["pack_" + op] = lambda image=image, role=role, img=img: call("ipdm_conv_pack_device", image, role, ptr(w), Cin, Cout, k, s,
-                                                                         ptr(img), st())
+        arms["tuned_" + op] = launch(op, tuned[op])
+        if op == "wgrad":       # the plan, and on the streamed layers (code 1) the copy of X and dY
+            lib().ipdm_conv2d_wgrad_tuned_plan(*geo, wplan, 14)
+            if tuned[op].code == 1:
+                x2, dy2 = torch.empty_like(x), torch.empty_like(dy)
+                arms["copy_floor"] = lambda: (x2.copy_(x), dy2.copy_(dy))
+        else:                   # the packer launch alone, of the image the code's kernel reads (csrc/conv_tuned.hip: reads_wino)
+            image = 1 if tuned[op].code in (1, 2, 9, 12) else 0
+            img = torch.empty(lib().ipdm_conv_image_bytes(image, role, Cin, Cout, k, s), dtype=torch.uint8, device=dev)
+            arms["pack_" + op] = lambda image=image, role=role, img=img: call("ipdm_conv_pack_device", image, role, ptr(w), Cin, Cout, k, s,
+                                                                             ptr(img), st())
     out = take_turns(arms, rounds, reps)
     flop = 2.0 * Cin * Cout * k * k * y.shape[2] * y.shape[3]
-    rec = {"shape": list(geo), "family": family(key), "flop_per_pass": flop, "workspace_bytes": int(n),
+    rec = {"shape": list(geo), "family": family(key), "flop_per_pass": flop, "workspace_bytes": int(hip["wgrad"].workspace_bytes),
            "wgrad_slabs": int(lib().ipdm_conv2d_wgrad_slabs(1, y.shape[2], y.shape[3])), "ms": out,
-           "tuned_codes": {"fprop": codes[0], "dgrad": codes[1], "wgrad": wcode}, "wgrad_tuned_workspace_bytes": int(wn),
+           "tuned_codes": {op: tuned[op].code for op in tuned},
+           "wgrad_tuned_workspace_bytes": int(tuned["wgrad"].workspace_bytes) if "tuned_wgrad" in arms else 0,
            "wgrad_tuned_plan": {"parts": int(wplan[1]), "chain": int(wplan[3]), "TH": int(wplan[4]), "TW": int(wplan[5]), "NT": int(wplan[6]),
                                 "strips": int(wplan[7])}}
     if "copy_floor" in out:
