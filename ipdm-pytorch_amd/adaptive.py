@@ -1,15 +1,15 @@
 """The adaptive pass schedule's decision (t_start=None; Model/model.py:582-613), taken per slice: which branch every slice of a
 batch takes after the ts=20 probe pass, and which slices can run the remaining passes together.  Pure Python -- no torch, no
-GPU -- so that the decision is testable on its own; diffusion.guided_reverse_process (option adaptive_per_slice) consumes it.
+GPU -- so that the decision is testable on its own.  The thresholds and the (t_list, eta) tables live HERE only.
 
 The reference decides ONCE per batch: proj mode on delt.max() over the whole batch (:596-609), img mode on the single
-`noise_strength` string (:582-590).  Here every slice decides on its own value by the same thresholds and tables."""
+`noise_strength` string (:582-590): diffusion.guided_reverse_process asks `schedule` for that one value.  Under its option
+adaptive_per_slice every slice decides on its own value by the same thresholds and tables (`adaptive_groups`)."""
 from collections import namedtuple
 
 # branch -> (t_list, eta); proj: Model/model.py:596-609, img: :582-590
-PROJ_BRANCHES = {"high": ((30, 25, 20), 0.6), "mid": ((20, 18, 15), 0.5), "low": ((15, 15, 15), 0.5)}
-IMG_BRANCHES = {"high": ((15, 15, 15), 0.6), "mid": ((15, 12, 10), 0.55), "low": ((10, 10, 10), 0.5)}
-BRANCHES = {"proj": PROJ_BRANCHES, "img": IMG_BRANCHES}
+BRANCHES = {"proj": {"high": ((30, 25, 20), 0.6), "mid": ((20, 18, 15), 0.5), "low": ((15, 15, 15), 0.5)},
+            "img": {"high": ((15, 15, 15), 0.6), "mid": ((15, 12, 10), 0.55), "low": ((10, 10, 10), 0.5)}}
 PROJ_HIGH, PROJ_MID = 30, 4.5            # emax >= 30: high; >= 4.5: mid; else low (the reference's `>=`)
 
 # draws of the longest branch after the probe pass (ts + 1 per pass): under adaptive_per_slice a noise source is advanced by
@@ -28,6 +28,13 @@ def img_branch(noise_strength):
     """Branch of one slice from its noise_strength entry: "high", "mid", anything else ("low", None) the short schedule --
     the reference's if / elif / else."""
     return noise_strength if noise_strength in ("high", "mid") else "low"
+
+
+def schedule(mode, value):
+    """(t_list, eta, branch name) for ONE value: an emax in proj mode, a noise_strength entry in img mode."""
+    name = proj_branch(value) if mode == "proj" else img_branch(value)
+    t_list, eta = BRANCHES[mode][name]
+    return list(t_list), eta, name
 
 
 def adaptive_groups(mode, emax=None, noise_strength=None, batch=None):

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import call, lib, ptr
-from .adaptive import MAX_DRAWS, adaptive_groups, branch_names
+from .adaptive import MAX_DRAWS, adaptive_groups, branch_names, schedule
 
 # np.polyfit coefficients of the guidance curves (Utils/train_test_utils.py:842-865), highest power
 # first; values as produced by the reference (tests/golden/misc.npz holds the same numbers).
@@ -55,6 +55,41 @@ def ddim_sequence(method, timesteps, t_start, n):
     seq, prev = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
     call("ipdm_ddim_sequence", str(method).encode(), int(timesteps), int(t_start), n, seq, prev)
     return list(seq[:n]), list(prev[:n])
+
+
+GUIDE_CONSTANT, GUIDE_CURVE, GUIDE_MAP = 0, 1, 2      # ipdm_reverse_args.guidance
+
+
+def pass_rule(it, constant):
+    """What outer pass `it` of guided_reverse_process is (Model/model.py:550-562, :622-635): (guidance code of its steps, the
+    guide is updated after it, x is reset to img after it).  `constant`: constant_guidance is given, and every pass is alike;
+    otherwise pass 0 probes under the cosine curve and leaves the guide alone, the later passes take the map it produced."""
+    if constant:
+        return GUIDE_CONSTANT, True, False
+    return (GUIDE_CURVE, False, True) if it == 0 else (GUIDE_MAP, True, False)
+
+
+def lambda_ladder(lambda_max, lambda_min, n_pass):
+    """condition_lambda of the sparse sampler, pass by pass (Model/model.py:742-743), as numpy makes it."""
+    import numpy as np
+    step = (lambda_max - lambda_min) / n_pass
+    return np.arange(lambda_max, lambda_min - step, -step)
+
+
+def _report(x, normal, transformer):
+    """An iterate as it is reported: through the inverse power transform under opt.normal (Model/model.py:616-619)."""
+    if not normal:
+        return x
+    from .normalize import yeo_johnson_inverse_transform
+    return yeo_johnson_inverse_transform(x.contiguous(), transformer).to(torch.float32)
+
+
+def _append_average(iters):
+    """Model/model.py:637-638: the mean of the last two REPORTED iterates joins the list when there are two."""
+    if len(iters) > 1:
+        avg = torch.empty_like(iters[-1])
+        _dcall(avg, "ipdm_axpbypcz", ptr(iters[-1]), ptr(iters[-2]), None, ptr(avg), avg.numel(), 0.5, 0.5, 0.0)
+        iters.append(avg)
 
 
 def _one_timestep(t):
@@ -146,6 +181,21 @@ class InjectedNoise:
         return z
 
 
+def _bind_noise(args, noise, n_draws, like, keep):
+    """Binds the next `n_draws` draws of `noise` to the argument struct of a native call (ReverseArgs, SparseArgs) and returns
+    the form they took.  A NoiseSource goes in as (seed, slice_id0, draw0) and is advanced: NOISE_COUNTER.  Any other noise
+    object is asked for the draws, in order, shaped like `like`, and they are stacked behind d_noise (parity mode):
+    NOISE_INJECTED; `keep` collects the tensor the struct points to."""
+    if isinstance(noise, NoiseSource):
+        args.seed, args.slice_id0, args.draw0 = noise.seed, noise.slice_id0, noise.draw
+        noise.draw += n_draws
+        return _lib.NOISE_COUNTER
+    z = torch.stack([noise.next_like(like) for _ in range(n_draws)]).to(like.device, torch.float32).contiguous()
+    keep.append(z)
+    args.d_noise = z.data_ptr()
+    return _lib.NOISE_INJECTED
+
+
 class GaussianDiffusion:
     """Mirror of Model/model.py:376-642 (cosine schedule only -- the only one the harness builds,
     Utils/train_test_utils.py:221-223,243-245)."""
@@ -163,7 +213,6 @@ class GaussianDiffusion:
         # ipdm_reverse_pass / ipdm_sparse_reverse, csrc/sampler.hip) instead of the Python ones below: same bits, one C call per
         # process (explicit t_start, sparse) or per pass (adaptive)
         self.native_loop = _NATIVE_REVERSE
-        self._rws = {}
 
     def __del__(self):
         try:
@@ -180,12 +229,20 @@ class GaussianDiffusion:
         call("ipdm_schedule_coeffs", self._h, int(t), C.byref(out))
         return tuple(out)
 
-    def _workspace(self, key, nbytes, device):
+    def _cached(self, key, nbytes, device):
+        """The scratch buffer of `key` on `device`: at least `nbytes`, kept between calls, replaced only by a larger one."""
         w = self._ws.get((key, device))
         if w is None or w.numel() < nbytes:
             w = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
             self._ws[(key, device)] = w
         return w
+
+    def _net_scratch(self, query, model, B, H, W, device):
+        """Scratch of an entry that runs the library's UNet, sized by its own query (`ipdm_reverse_workspace_bytes`: the native
+        loops, `ipdm_eps_loss_workspace_bytes`: the objective) and cached by (query, B, H, W, device)."""
+        with torch.cuda.device(device):
+            need = getattr(lib(), query)(model._ensure(), B, H, W)
+        return self._cached((query, B, H, W), need, device)
 
     # ---- Model/model.py:438-445
     def q_sample(self, x_start, t, noise):
@@ -205,17 +262,6 @@ class GaussianDiffusion:
         return out
 
     # ---- Model/model.py:645-652, per slice
-    def _loss_workspace(self, model, B, H, W, device):
-        """Scratch of ipdm_eps_loss, cached by (device, B, H, W)."""
-        with torch.cuda.device(device):
-            need = lib().ipdm_eps_loss_workspace_bytes(model._ensure(), B, H, W)
-        key = ("loss", device, B, H, W)
-        w = self._rws.get(key)
-        if w is None or w.numel() < need:
-            w = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-            self._rws[key] = w
-        return w
-
     def _loss_native(self, model, x):
         """ipdm_eps_loss serves the library's own one-channel UNetModel on the device of x."""
         from .unet import UNetModel
@@ -256,7 +302,7 @@ class GaussianDiffusion:
             H, W = x.shape[2], x.shape[3]
             for lo in range(0, B, _lib.SLICE_IDS_MAX):
                 k = min(B - lo, _lib.SLICE_IDS_MAX)
-                ws = self._loss_workspace(model, k, H, W, x.device)
+                ws = self._net_scratch("ipdm_eps_loss_workspace_bytes", model, k, H, W, x.device)
                 _dcall(x, "ipdm_eps_loss", self._h, model._ensure(), ptr(x[lo:lo + k]), (C.c_int32 * k)(*ts[lo:lo + k]),
                        ptr(sse[lo:lo + k]), k, H, W, noise.seed if z is None else 0,
                        (C.c_int64 * k)(*ids[lo:lo + k]) if z is None else None, draw if z is None else 0,
@@ -266,7 +312,7 @@ class GaussianDiffusion:
             pred = model(x_t, torch.tensor(ts, dtype=torch.long, device=x.device)).to(torch.float32).contiguous()
             if pred.shape != x.shape:
                 raise ValueError("eps_losses: the model returned %s for an input of %s" % (tuple(pred.shape), tuple(x.shape)))
-            ws = self._workspace("sse", lib().ipdm_eps_sse_workspace_bytes(B), x.device)
+            ws = self._cached("sse", lib().ipdm_eps_sse_workspace_bytes(B), x.device)
             _dcall(x, "ipdm_eps_sse", ptr(pred), ptr(z), ptr(sse), B, n, ptr(ws), ws.numel())
         return sse / float(n)
 
@@ -284,7 +330,7 @@ class GaussianDiffusion:
         x_t = x_t.contiguous()
         if eps_pred is None:
             eps_pred = model(x_t, int(t))
-        ws = self._workspace("step", lib().ipdm_ddpm_workspace_bytes(B), x_t.device)
+        ws = self._cached("step", lib().ipdm_ddpm_workspace_bytes(B), x_t.device)
         out = torch.empty_like(x_t)
         if isinstance(lambda_, torch.Tensor) and lambda_.dim() > 0:
             lm = lambda_.to(x_t.device, torch.float32).contiguous()
@@ -302,7 +348,7 @@ class GaussianDiffusion:
         ks = int(kernel_size)
         Lam = torch.empty((B, 1, H // ks, W // ks), dtype=torch.float32, device=x.device)
         emax = torch.empty((B,), dtype=torch.float32, device=x.device)
-        ws = self._workspace("guid", lib().ipdm_guidance_workspace_bytes(B, H, W), x.device)
+        ws = self._cached("guid", lib().ipdm_guidance_workspace_bytes(B, H, W), x.device)
         p1, p2 = CURVE_COEFFS[mode]
         a1 = (C.c_double * 5)(*p1)
         a2 = (C.c_double * 3)(*p2)
@@ -326,21 +372,9 @@ class GaussianDiffusion:
         d = model._device
         return d.type == "cuda" and (d.index is None or d.index == img.device.index)
 
-    def _reverse_workspace(self, model, B, H, W, device):
-        """Scratch of ipdm_reverse_pass / ipdm_guided_reverse, cached by (device, B, H, W)."""
-        with torch.cuda.device(device):
-            need = lib().ipdm_reverse_workspace_bytes(model._ensure(), B, H, W)
-        key = (device, B, H, W)
-        w = self._rws.get(key)
-        if w is None or w.numel() < need:
-            w = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-            self._rws[key] = w
-        return w
-
     def _reverse_args(self, mode, clip, guidance, constant_guidance, lambda_ratio, eta, kwargs, noise, n_draws, like, keep):
-        """ipdm_reverse_args of one native call that consumes `n_draws` draws.  A NoiseSource goes in as (seed, slice_id0,
-        draw); any other noise object is asked for the draws, in order, and they are stacked (parity mode).  `keep`
-        collects the tensors the struct points to."""
+        """ipdm_reverse_args of one native call that consumes `n_draws` draws of `noise` (_bind_noise).  `keep` collects the
+        tensors the struct points to."""
         a = _lib.ReverseArgs()
         a.mode = 0 if mode == "img" else 1
         a.clip = 1 if clip else 0
@@ -354,13 +388,7 @@ class GaussianDiffusion:
         if guidance != 0 and ("kernel_size_" + mode) in kwargs:
             a.kernel_size = int(kwargs["kernel_size_" + mode])
             a.amplitude = float(kwargs["amplitude_" + mode])
-        if isinstance(noise, NoiseSource):
-            a.seed, a.slice_id0, a.draw0 = noise.seed, noise.slice_id0, noise.draw
-            noise.draw += n_draws
-        else:
-            z = torch.stack([noise.next_like(like) for _ in range(n_draws)]).to(like.device, torch.float32).contiguous()
-            keep.append(z)
-            a.d_noise = z.data_ptr()
+        _bind_noise(a, noise, n_draws, like, keep)
         ldct = kwargs.get("ldct")
         if mode == "img" and ldct is not None:
             ld = ldct.to(like.device, torch.float32).contiguous()
@@ -375,9 +403,10 @@ class GaussianDiffusion:
         n_pass = len(t_start)
         n_out = n_pass + (1 if n_pass > 1 else 0)
         keep = []
-        a = self._reverse_args(mode, clip, 0 if constant_guidance is not None else 1, constant_guidance, lambda_ratio, eta,
-                               kwargs, noise, sum(int(t) + 1 for t in t_start), img, keep)
-        ws = self._reverse_workspace(model, B, H, W, img.device)
+        guidance = pass_rule(0, constant_guidance is not None)[0]       # of pass 0: the call goes on to the map by itself
+        a = self._reverse_args(mode, clip, guidance, constant_guidance, lambda_ratio, eta, kwargs, noise,
+                               sum(int(t) + 1 for t in t_start), img, keep)
+        ws = self._net_scratch("ipdm_reverse_workspace_bytes", model, B, H, W, img.device)
         out = torch.empty((n_out,) + tuple(img.shape), dtype=torch.float32, device=img.device)
         ts = (C.c_int32 * n_pass)(*[int(t) for t in t_start])
         used = C.c_int64()
@@ -385,15 +414,15 @@ class GaussianDiffusion:
                C.byref(used), ptr(ws), ws.numel())
         return [out[k] for k in range(n_out)]
 
-    def _native_pass(self, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs):
+    def _native_pass(self, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise):
         """One outer pass (q_sample, ts guided steps, the clamp) in ONE call (ipdm_reverse_pass)."""
         B, _, H, W = x.shape
-        guidance = 0 if constant_guidance is not None else (1 if it == 0 else 2)
+        guidance = pass_rule(it, constant_guidance is not None)[0]
         keep = []
         a = self._reverse_args(mode, clip, guidance, constant_guidance, lambda_ratio, eta, {}, noise, int(ts) + 1, x, keep)
-        ws = self._reverse_workspace(model, B, H, W, x.device)
+        ws = self._net_scratch("ipdm_reverse_workspace_bytes", model, B, H, W, x.device)
         out = torch.empty_like(x)
-        lm = Lam.contiguous() if guidance == 2 else None
+        lm = Lam.contiguous() if guidance == GUIDE_MAP else None
         mh, mw = (lm.shape[-2], lm.shape[-1]) if lm is not None else (0, 0)
         if getattr(noise, "slice_ids", None) is not None:       # a group of slices that is no run of consecutive ones
             _dcall(x, "ipdm_reverse_pass_ids", self._h, model._ensure(), ptr(x), ptr(guide), ptr(lm), mh, mw, ptr(out), B, H, W,
@@ -403,21 +432,21 @@ class GaussianDiffusion:
                    C.byref(a), ptr(ws), ws.numel())
         return out
 
-    def _one_pass(self, native, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs,
+    def _one_pass(self, native, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise,
                   reverse_states):
         """One outer pass (Model/model.py:537-573): q_sample at ts, ts guided steps, the clamp -- one native call, or the Python
         loop over the op-level entries.  `reverse_states`: a list that receives every step's state (save_states), or None."""
         if native:
-            return self._native_pass(model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs)
+            return self._native_pass(model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise)
+        guidance = pass_rule(it, constant_guidance is not None)[0]
         x = self.q_sample(x, ts, noise.next_like(x))
         for i in reversed(range(ts)):
-            if constant_guidance is None:
-                if it == 0:
-                    l_s = cosine_lambda(ts, lambda_ratio, i)
-                else:
-                    l_s = self.lambda_ratio(Lam, i, ts)
-            else:
+            if guidance == GUIDE_CONSTANT:
                 l_s = constant_guidance
+            elif guidance == GUIDE_CURVE:
+                l_s = cosine_lambda(ts, lambda_ratio, i)
+            else:
+                l_s = self.lambda_ratio(Lam, i, ts)
             x = self.p_sample_condition(model, x, guide, i, clip_denoised=clip, lambda_=l_s, noise=noise.next_like(x))
             if reverse_states is not None:
                 reverse_states.append(x.detach().cpu().numpy())
@@ -453,19 +482,16 @@ class GaussianDiffusion:
             gnoise = noise.child(rows, draw0)
             tr = kwargs.get("transformer")
             if normal:
-                from .normalize import SliceTransformers, yeo_johnson_inverse_transform
+                from .normalize import SliceTransformers
                 if isinstance(tr, SliceTransformers):
                     tr = SliceTransformers([tr[r] for r in rows])
             x, guide, iters = img_g, img_g, []       # after the probe pass: x is reset to img, the guide is still img (:619-622)
-            for k, ts in enumerate(g.t_list):
-                x = self._one_pass(native, model, x, guide, Lam_g, ts, 1 + k, clip, lambda_ratio, g.eta, mode, None, gnoise, kwargs,
-                                   None)
-                iters.append(yeo_johnson_inverse_transform(x.contiguous(), tr).to(torch.float32) if normal else x)
-                if k + 1 < len(g.t_list):
+            for it, ts in enumerate(g.t_list, 1):
+                x = self._one_pass(native, model, x, guide, Lam_g, ts, it, clip, lambda_ratio, g.eta, mode, None, gnoise, None)
+                iters.append(_report(x, normal, tr))
+                if it < len(g.t_list):          # (every pass here is a map pass, pass_rule; the last one's update has no reader)
                     guide = self._guide_update(mode, g.eta, x, img_g, ld_g)
-            avg = torch.empty_like(iters[-1])
-            _dcall(avg, "ipdm_axpbypcz", ptr(iters[-1]), ptr(iters[-2]), None, ptr(avg), avg.numel(), 0.5, 0.5, 0.0)
-            iters.append(avg)
+            _append_average(iters)
             for k, r in enumerate(iters):
                 if idx is None:
                     outs[k][lo:hi].copy_(r)
@@ -491,10 +517,9 @@ class GaussianDiffusion:
         if kwargs.get("only_convertor"):
             return [img], None, None
         normal = bool(kwargs.get("normal"))        # iterates are reported through the inverse power transform (:616-617)
+        constant = constant_guidance is not None
         noise = noise if noise is not None else NoiseSource(0)
         img = img.to(torch.float32).contiguous()
-        B = img.shape[0]
-        n = img.numel()
         x = img.clone()
         guide = img.clone()
         iters_out, reverse_states = [], []
@@ -509,89 +534,62 @@ class GaussianDiffusion:
         native = self._use_native(model, img, save_states)
         if native and not adaptive and t_list and getattr(noise, "slice_ids", None) is None:
             raw = self._native_process(model, img, t_list, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs)
-            if not normal:
-                return raw, reverse_states, noise_strength
-            from .normalize import yeo_johnson_inverse_transform
-            iters_out = [yeo_johnson_inverse_transform(r.contiguous(), kwargs["transformer"]).to(torch.float32)
-                         for r in raw[:len(t_list)]]
-            if len(iters_out) > 1:      # the average is taken over the REPORTED (transformed) iterates, as below
-                avg = torch.empty_like(iters_out[-1])
-                _dcall(avg, "ipdm_axpbypcz", ptr(iters_out[-1]), ptr(iters_out[-2]), None, ptr(avg), n, 0.5, 0.5, 0.0)
-                iters_out.append(avg)
-            return iters_out, reverse_states, noise_strength
-        it = 0
+            if normal:      # the call's own average is of the raw iterates: it is taken again over the REPORTED ones, as below
+                raw = [_report(r, True, kwargs["transformer"]) for r in raw[:len(t_list)]]
+                _append_average(raw)
+            return raw, reverse_states, noise_strength
         Lam = None
         ldct = kwargs.get("ldct")
+        it = 0
         while t_list:
             ts = t_list.pop(0)
             # (native: the adaptive schedule takes one call per pass, the between-pass decisions below stay here)
-            x = self._one_pass(native, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise, kwargs,
+            x = self._one_pass(native, model, x, guide, Lam, ts, it, clip, lambda_ratio, eta, mode, constant_guidance, noise,
                                reverse_states if save_states else None)
-            if it == 0 and constant_guidance is None:
-                if mode == "img":
-                    Lam, emax = self.guidance_map(x, img, "img", kwargs["kernel_size_img"], kwargs["amplitude_img"])
-                    if per_slice:
-                        groups = adaptive_groups("img", noise_strength=kwargs.get("noise_strength"), batch=B)
-                    elif adaptive:
-                        ns = kwargs.get("noise_strength")
-                        if ns == "high":
-                            t_list, eta = [15, 15, 15], 0.6
-                        elif ns == "mid":
-                            t_list, eta = [15, 12, 10], 0.55
-                        else:
-                            t_list, eta = [10, 10, 10], 0.5
-                else:
-                    Lam, emax = self.guidance_map(x, img, "proj", kwargs["kernel_size_proj"], kwargs["amplitude_proj"])
-                    if per_slice:       # ONE device->host copy of B floats; every slice decides for itself, no rank_max
-                        groups = adaptive_groups("proj", emax=emax.cpu().tolist(), batch=B)
-                    elif adaptive:
-                        m = float(emax.max().item())       # the one device->host scalar of adaptive mode
-                        # the reference decides on the whole batch's maximum (delt.max(), :596-609); when the batch is
-                        # sharded over ranks the decision must not depend on the sharding: `rank_max` (a scalar MAX
-                        # all-reduce, handed in by the denoiser under torch.distributed) makes it global again
-                        if kwargs.get("rank_max") is not None:
-                            m = float(kwargs["rank_max"](m))
-                        if m >= 30:
-                            t_list, noise_strength, eta = [30, 25, 20], "high", 0.6
-                        elif m >= 4.5:
-                            t_list, noise_strength, eta = [20, 18, 15], "mid", 0.5
-                        else:
-                            t_list, noise_strength, eta = [15, 15, 15], "low", 0.5
+            if it == 0 and not constant:
+                Lam, emax = self.guidance_map(x, img, mode, kwargs["kernel_size_" + mode], kwargs["amplitude_" + mode])
                 if per_slice:
+                    # every slice decides for itself: ONE device->host copy of B floats in proj mode, `rank_max` is not called
+                    groups = adaptive_groups(mode, emax=emax.cpu().tolist() if mode == "proj" else None,
+                                             noise_strength=kwargs.get("noise_strength"), batch=img.shape[0])
                     if not hasattr(noise, "skip_to"):
                         raise TypeError("adaptive_per_slice needs a noise source with skip_to (NoiseSource, InjectedNoise), not "
                                         "%s" % type(noise).__name__)
                     noise_strength = branch_names(groups)
                     draw_end = noise.draw + MAX_DRAWS[mode]
-                    if len(groups) == 1:        # one branch for all: the batch goes on as it is, launch for launch
-                        t_list, eta = list(groups[0].t_list), groups[0].eta
-                    else:
+                    if len(groups) > 1:
                         outs = self._grouped_passes(native, model, img, Lam, ldct, groups, clip, lambda_ratio, mode, noise,
                                                     noise.draw, kwargs)
                         noise.skip_to(draw_end)
                         return outs, reverse_states, noise_strength
-            if normal:
-                from .normalize import yeo_johnson_inverse_transform
-                iters_out.append(yeo_johnson_inverse_transform(x.contiguous(), kwargs["transformer"]).to(torch.float32))
-            else:
-                iters_out.append(x)
-            if constant_guidance is None:
-                if it >= 1:
-                    guide = self._guide_update(mode, eta, x, img, ldct)
-                if it == 0:
-                    x = img.clone()
-            else:
+                    t_list, eta = list(groups[0].t_list), groups[0].eta     # one branch for all: the batch goes on as it is
+                elif adaptive:
+                    t_list, eta, noise_strength = self._batch_schedule(mode, emax, kwargs)
+            iters_out.append(_report(x, normal, kwargs["transformer"] if normal else None))
+            _, update, reset = pass_rule(it, constant)
+            if update:          # (after the last pass too, as the reference: nobody reads that guide)
                 guide = self._guide_update(mode, eta, x, img, ldct)
+            if reset:
+                x = img.clone()
             it += 1
-        if len(iters_out) > 1:
-            avg = torch.empty_like(iters_out[-1])
-            _dcall(avg, "ipdm_axpbypcz", ptr(iters_out[-1]), ptr(iters_out[-2]), None, ptr(avg), n, 0.5, 0.5, 0.0)
-            iters_out.append(avg)
+        _append_average(iters_out)
         if draw_end is not None:
             noise.skip_to(draw_end)
-        if adaptive:
-            return iters_out[1:], reverse_states, noise_strength
-        return iters_out, reverse_states, noise_strength
+        return (iters_out[1:] if adaptive else iters_out), reverse_states, noise_strength
+
+    def _batch_schedule(self, mode, emax, kwargs):
+        """The decision after the probe pass, taken ONCE for the batch as the reference takes it (Model/model.py:582-613):
+        (t_list, eta, noise_strength as it is returned)."""
+        if mode == "img":
+            t_list, eta, _ = schedule("img", kwargs.get("noise_strength"))
+            return t_list, eta, None            # the reference sets noise_strength in proj mode only
+        m = float(emax.max().item())            # the one device->host scalar of adaptive mode
+        # the reference decides on the whole batch's maximum (delt.max(), :596-609); when the batch is sharded over ranks the
+        # decision must not depend on the sharding: `rank_max` (a scalar MAX all-reduce, handed in by the denoiser under
+        # torch.distributed) makes it global again
+        if kwargs.get("rank_max") is not None:
+            m = float(kwargs["rank_max"](m))
+        return schedule("proj", m)
 
     # ---- Model/model.py:654-725
     @torch.no_grad()
@@ -611,7 +609,7 @@ class GaussianDiffusion:
         x = sample_img.to(torch.float32).contiguous()
         cond = condition.to(torch.float32).contiguous()
         B = x.shape[0]
-        ws = self._workspace("step", lib().ipdm_ddpm_workspace_bytes(B), x.device)
+        ws = self._cached("step", lib().ipdm_ddpm_workspace_bytes(B), x.device)
         for i in range(ddim_timesteps):
             t, tp = int(seq[i]), int(prev_seq[i])
             eps_pred = model(x, t)
@@ -630,7 +628,6 @@ class GaussianDiffusion:
                                       eta=0.5, clip_denoised=True, noise=None):
         """The sparse (DDIM) sampler: same signature and return value (list of per-pass results) as the reference.  Under
         `native_loop` the library's own UNetModel runs it in one call (ipdm_sparse_reverse): same bits, same draw count."""
-        import numpy as np
         noise = noise if noise is not None else NoiseSource(0)
         condition = condition.to(torch.float32).contiguous()
         if self._sparse_native_ok(model, condition, t_start, ddim_timesteps, ddim_discr_method, noise):
@@ -638,9 +635,7 @@ class GaussianDiffusion:
                                        ddim_discr_method, ddim_eta, eta, clip_denoised, noise)
         sample_img = self.q_sample(condition, t_start[0], noise.next_like(condition))
         condition_ = condition.clone()
-        n_it = len(t_start)
-        step = (condition_lambda_max - condition_lambda_min) / n_it
-        lam = np.arange(condition_lambda_max, condition_lambda_min - step, -step)
+        lam = lambda_ladder(condition_lambda_max, condition_lambda_min, len(t_start))
         result = []
         for i, t in enumerate(t_start):
             sample_img = self.ddim_sample(sample_img=sample_img, model=model, condition=condition, t_start=t,
@@ -673,9 +668,7 @@ class GaussianDiffusion:
                        clip_denoised, noise):
         """The whole sparse process in ONE call (ipdm_sparse_reverse); the guidance ladder and the draw accounting stay here,
         the timestep sequences come from ipdm_ddim_sequence."""
-        import numpy as np
-        step = (lambda_max - lambda_min) / len(t_start)
-        lam = np.arange(lambda_max, lambda_min - step, -step)          # Model/model.py:742-743
+        lam = lambda_ladder(lambda_max, lambda_min, len(t_start))
         B, _, H, W = condition.shape
         n_pass = len(t_start)
         steps = [int(ddim_timesteps[i]) for i in range(n_pass)]
@@ -688,14 +681,8 @@ class GaussianDiffusion:
         a = _lib.SparseArgs()
         a.clip_denoised, a.ddim_eta, a.eta = (1 if clip_denoised else 0), float(ddim_eta), float(eta)
         keep = []
-        if isinstance(noise, NoiseSource):
-            a.noise, a.seed, a.slice_id0, a.draw0 = _lib.NOISE_COUNTER, noise.seed, noise.slice_id0, noise.draw
-            noise.draw += n_draws
-        else:       # parity mode: the draws in order, stacked as _reverse_args does
-            z = torch.stack([noise.next_like(condition) for _ in range(n_draws)]).to(condition.device, torch.float32).contiguous()
-            keep.append(z)
-            a.noise, a.d_noise = _lib.NOISE_INJECTED, z.data_ptr()
-        ws = self._reverse_workspace(model, B, H, W, condition.device)
+        a.noise = _bind_noise(a, noise, n_draws, condition, keep)
+        ws = self._net_scratch("ipdm_reverse_workspace_bytes", model, B, H, W, condition.device)
         out = torch.empty((n_pass,) + tuple(condition.shape), dtype=torch.float32, device=condition.device)
         used = C.c_int64()
         _dcall(condition, "ipdm_sparse_reverse", self._h, model._ensure(), ptr(condition), ptr(out), B, H, W, int(t_start[0]),

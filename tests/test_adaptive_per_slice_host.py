@@ -228,3 +228,61 @@ def test_injected_noise_children():
     assert src.draw == 5 and torch.equal(src.next_like(like), draws[5])
     with pytest.raises(TypeError):
         InjectedNoise(iter(draws)).child([0], 0)
+
+
+# =========================================================================== 5. the whole-batch decision (the default)
+# Model/model.py:582-613 written out: input -> (t_list, eta, noise_strength as RETURNED: the branch name in proj mode, None in
+# img mode, where the reference never sets it).  "other" is the one entry the reference does not serve (its if / elif chain
+# leaves the list empty and the process ends after the probe); here it has always taken the short schedule, as None does.
+NAN = float("nan")
+PROJ_WHOLE_BATCH = [(0.0, [15, 15, 15], 0.5, "low"), (4.4999, [15, 15, 15], 0.5, "low"), (4.5, [20, 18, 15], 0.5, "mid"),
+                    (29.999, [20, 18, 15], 0.5, "mid"), (30.0, [30, 25, 20], 0.6, "high"), (1e9, [30, 25, 20], 0.6, "high"),
+                    (NAN, [15, 15, 15], 0.5, "low")]                  # nan >= x is false twice: the last branch
+IMG_WHOLE_BATCH = [("high", [15, 15, 15], 0.6, None), ("mid", [15, 12, 10], 0.55, None), ("low", [10, 10, 10], 0.5, None),
+                   (None, [10, 10, 10], 0.5, None), ("other", [10, 10, 10], 0.5, None)]
+
+
+def _whole_batch_decision(monkeypatch, mode, emax=None, **kwargs):
+    """guided_reverse_process(t_start=None) on host tensors with every device operation stubbed out: what remains is the
+    control flow.  Returns (the passes after the ts=20 probe, the eta of the three guide updates, the returned noise_strength)."""
+    import itertools
+    import torch
+    from ipdm_pytorch_amd import diffusion
+    gd = diffusion.GaussianDiffusion(1000, "cosine", 1)
+    passes, scales = [], []
+    monkeypatch.setattr(gd, "q_sample", lambda x, t, noise: (passes.append(int(t)), x)[1])
+    monkeypatch.setattr(gd, "p_sample_condition", lambda model, x, *a, **k: x)
+    monkeypatch.setattr(gd, "lambda_ratio", lambda Lam, i, ts: 0.5)
+    monkeypatch.setattr(gd, "guidance_map", lambda x, img, m, ks, amp: (None, torch.tensor([emax or 0.0], dtype=torch.float64)))
+    # _dcall(tensor, entry, *arguments) with ipdm_axpbypcz's arguments (x, y, z, out, n, a, b, c: out = a x + b y + c z): a, at
+    # index 5, is the eta of a guide update (three of them: after passes 1, 2 and 3) and 0.5 in the final average (the fourth call)
+    monkeypatch.setattr(diffusion, "_dcall", lambda t, name, *a: scales.append(a[5]) if name == "ipdm_axpbypcz" else None)
+    img = torch.zeros((1, 1, 4, 4))
+    res, _, ns = gd.guided_reverse_process(
+        model=lambda x, t: x, img=img, t_start=None, clip=False, mode=mode, constant_guidance=None, ldct=img, only_convertor=False,
+        normal=False, kernel_size_proj=4, amplitude_proj=7, kernel_size_img=4, amplitude_img=30,
+        noise=diffusion.InjectedNoise(itertools.repeat(img)), **kwargs)
+    assert passes[0] == 20 and len(res) == 4 and len(scales) == 4 and scales[-1] == 0.5
+    assert scales[0] == scales[1] == scales[2]
+    return passes[1:], scales[0], ns
+
+
+@pytest.mark.parametrize("emax,t_list,eta,reported", PROJ_WHOLE_BATCH)
+def test_whole_batch_decision_proj_is_the_reference_s_table(monkeypatch, emax, t_list, eta, reported):
+    assert _whole_batch_decision(monkeypatch, "proj", emax=emax, noise_strength=None) == (t_list, eta, reported)
+    g, = adaptive_groups("proj", emax=[emax])                 # the per-slice decision of a batch of one
+    assert (list(g.t_list), g.eta, g.branch) == (t_list, eta, reported)
+
+
+@pytest.mark.parametrize("noise_strength,t_list,eta,reported", IMG_WHOLE_BATCH)
+def test_whole_batch_decision_img_is_the_reference_s_table(monkeypatch, noise_strength, t_list, eta, reported):
+    assert _whole_batch_decision(monkeypatch, "img", noise_strength=noise_strength) == (t_list, eta, reported)
+    g, = adaptive_groups("img", noise_strength=noise_strength, batch=1)
+    assert (list(g.t_list), g.eta) == (t_list, eta)
+
+
+def test_whole_batch_decision_takes_rank_max_before_the_thresholds(monkeypatch):
+    """`rank_max` (the MAX all-reduce over ranks) is applied to the batch maximum, and the decision is taken on its result."""
+    seen = []
+    got = _whole_batch_decision(monkeypatch, "proj", emax=1.0, noise_strength=None, rank_max=lambda m: (seen.append(m), 31.0)[1])
+    assert seen == [1.0] and got == ([30, 25, 20], 0.6, "high")
