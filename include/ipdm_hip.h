@@ -421,6 +421,21 @@ int32_t ipdm_conv2d_wgrad_tuned_code(int32_t B, int32_t Cin, int32_t Cout, int32
 #define IPDM_WGRAD_PLAN_FIELDS 14
 int32_t ipdm_conv2d_wgrad_tuned_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride,
                                      int32_t *out, int32_t n);
+/* Host only, answers without a device; an additional entry (IPDM_ABI_VERSION stays 5, detected by symbol).  What the launcher of
+ * ipdm_conv2d_wgrad_tuned decides beyond the plan, read from the one host function the launch switches on:
+ *   out[0..3] the kernel instantiation <KS, S, MBW, NBW>: kernel size, stride, 16-output-channel blocks and 16-column (input
+ *             channel, tap) blocks a wave holds
+ *   out[4]    1 = the streamed form (code 1), 0 = the tiled form (code 2)
+ *   out[5]    staging planes per wave of the X window (2 or 4)
+ *   out[6]    workgroups whose four waves all take the straight-line multiply loop (every block holds channels)
+ *   out[7]    workgroups with at least one wave in the guarded loop (out[6] + out[7] = strips * output groups * input groups;
+ *             both saturate at INT32_MAX)
+ *   out[8]    1 if some strip holds tiles of more than one sample
+ * All 0 for code 0.  Returns the code, -1 for a bad argument or n < IPDM_WGRAD_LAUNCH_FIELDS.  Test aid: a test asserts the launch
+ * class it covers (instantiation, TW, NT, loop) from this and the plan query. */
+#define IPDM_WGRAD_LAUNCH_FIELDS 9
+int32_t ipdm_conv2d_wgrad_tuned_launch(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride,
+                                       int32_t *out, int32_t n);
 /* d_ws of the call below: parts * Cout * Cin * k * k floats (rounded up to 16 bytes) + 4 * strips * Cout doubles; 0 for code <= 0 */
 size_t ipdm_conv2d_wgrad_tuned_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
                                                int32_t stride);

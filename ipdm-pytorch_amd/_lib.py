@@ -128,6 +128,7 @@ PROTOTYPES = {
     "ipdm_conv2d_wgrad": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
     "ipdm_conv2d_wgrad_tuned_code": (_i32, [_i32] * 7),
     "ipdm_conv2d_wgrad_tuned_plan": (_i32, [_i32] * 7 + [C.POINTER(_i32), _i32]),
+    "ipdm_conv2d_wgrad_tuned_launch": (_i32, [_i32] * 7 + [C.POINTER(_i32), _i32]),
     "ipdm_conv2d_wgrad_tuned_workspace_bytes": (_sz, [_i32] * 7),
     "ipdm_conv2d_wgrad_tuned": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
     "ipdm_conv2d_tuned_code": (_i32, [_i32] * 8),

@@ -65,6 +65,9 @@ struct WArgs {
     unsigned magic;
 };
 
+// staging planes per wave: the instantiations for <= 8 (1x1: 16) input channels take fewer (read by the kernel and by the query)
+constexpr int staging_planes(int KS, int NBW, bool PIX) { return (PIX && NBW <= (KS == 3 ? 5 : 1)) ? 2 : 4; }
+
 // The multiply loop of one tile: n k-steps of four pixels from k-step ks0 on.  FULL: all MBW x NBW blocks of the wave hold
 // channels -- the body is straight-line, so the LDS reads of a k-step are issued together and ahead of its MFMAs; otherwise
 // blocks past (mcnt, ncnt) are skipped by wave-uniform guards (ragged channel groups, layers narrower than the instantiation).
@@ -105,7 +108,7 @@ template <int KS, int S, int MBW, int NBW, bool PIX>
 __global__ __launch_bounds__(WT_THREADS) void conv_wgrad_kernel(const WArgs a)
 {
     constexpr int T = KS * KS, P = KS / 2;
-    constexpr int WT_SP = (PIX && NBW <= (KS == 3 ? 5 : 1)) ? 2 : 4;   // the instantiations for <= 8 (1x1: 16) input channels: fewer planes per wave
+    constexpr int WT_SP = staging_planes(KS, NBW, PIX);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
     const int co0 = blockIdx.y * WT_COG, ci0 = blockIdx.z * a.cig;
@@ -315,6 +318,37 @@ int make_plan(const char *who, int32_t B, int32_t Cin, int32_t Cout, int32_t H, 
     return IPDM_OK;
 }
 
+// The instantiation <KS, S, MBW, NBW, PIX> a plan launches, and what its workgroups meet: the launch below switches on it and the
+// query ipdm_conv2d_wgrad_tuned_launch reports it.  Streamed: the smallest that holds the layer's blocks -- 1 or 2 blocks of 16
+// output channels, and the (input channel, tap) blocks of min(Cin, cig) channels.  Tiled: one per (ksize, stride).
+struct WInst {
+    int KS, S, MBW, NBW, PIX;
+};
+
+WInst pick_instantiation(const WPlan &p)
+{
+    const int Cin = p.g.Cin, Cout = p.g.Cout, ksize = p.g.ks, stride = p.g.stride;
+    if (p.code == 1) {
+        const int mbw = Cout <= 16 ? 1 : 2;
+        if (ksize == 1) return {1, 1, mbw, Cin <= 16 ? 1 : 4, 1};
+        if (stride == 1) return {3, 1, mbw, Cin <= 8 ? 5 : Cin <= 16 ? 9 : 18, 1};
+        return {3, 2, mbw, Cin <= 8 ? 5 : 9, 1};
+    }
+    if (ksize == 1) return {1, 1, 1, 2, 0};
+    if (stride == 1) return {3, 1, 1, 9, 0};
+    return {3, 2, 1, 5, 0};
+}
+
+// the kernel's `full` of one wave of the workgroup of channel groups (y, z): every block of the wave holds channels
+bool wave_is_full(const WPlan &p, const WInst &i, int y, int z, int wave)
+{
+    const int nco = p.g.Cout - y * WT_COG < WT_COG ? p.g.Cout - y * WT_COG : WT_COG;
+    const int nci = p.g.Cin - z * p.cig < p.cig ? p.g.Cin - z * p.cig : p.cig;
+    const int nmb = (nco + 15) >> 4, nnb = (nci * p.g.T + 15) >> 4;
+    const int mb0 = i.PIX ? 0 : (wave & 1), nb0 = i.PIX ? 0 : (wave >> 1) * i.NBW;
+    return mb0 + i.MBW <= nmb && nb0 + i.NBW <= nnb;
+}
+
 template <int KS, int S, int MBW, int NBW, bool PIX>
 int launch(const WPlan &p, const WArgs &a, hipStream_t st)
 {
@@ -354,6 +388,40 @@ int32_t ipdm_conv2d_wgrad_tuned_plan(int32_t B, int32_t Cin, int32_t Cout, int32
     return p.code;
 }
 
+int32_t ipdm_conv2d_wgrad_tuned_launch(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride,
+                                       int32_t *out, int32_t n)
+{
+    WPlan p;
+    if (!out || n < IPDM_WGRAD_LAUNCH_FIELDS) {
+        set_error("ipdm_conv2d_wgrad_tuned_launch: out must hold %d fields (got %d)", IPDM_WGRAD_LAUNCH_FIELDS, n);
+        return -1;
+    }
+    if (make_plan("ipdm_conv2d_wgrad_tuned_launch", B, Cin, Cout, H, W, ksize, stride, &p) != IPDM_OK) return -1;
+    for (int i = 0; i < IPDM_WGRAD_LAUNCH_FIELDS; ++i) out[i] = 0;
+    if (!p.code) return 0;
+    const WInst w = pick_instantiation(p);
+    // `full` is a property of the wave and the workgroup's channel groups, the same in every strip
+    long full_groups = 0, guarded_groups = 0;
+    // (all groups but the last of a side hold the same channel count: the last and one other stand for all)
+    for (int ylast = 0; ylast < 2; ++ylast)
+        for (int zlast = 0; zlast < 2; ++zlast) {
+            const long count = (long)(ylast ? 1 : p.ncog - 1) * (zlast ? 1 : p.ncig - 1);
+            if (!count) continue;
+            bool all = true;
+            for (int wave = 0; wave < 4; ++wave) all = all && wave_is_full(p, w, ylast ? p.ncog - 1 : 0, zlast ? p.ncig - 1 : 0, wave);
+            (all ? full_groups : guarded_groups) += count;
+        }
+    const auto clamp = [](long v) { return (int32_t)(v > INT32_MAX ? INT32_MAX : v); };
+    // a strip [t0, t0 + NT) holds tiles of two samples where a sample's first tile is not a strip's first: tile b * tiles_per_sample
+    // for some b in [1, B) is no multiple of NT, which b = 1 decides
+    const long tps = (long)p.tiles_x * p.tiles_y;
+    const int32_t f[IPDM_WGRAD_LAUNCH_FIELDS] = {w.KS, w.S, w.MBW, w.NBW, w.PIX, staging_planes(w.KS, w.NBW, w.PIX != 0),
+                                                 clamp(full_groups * p.strips), clamp(guarded_groups * p.strips),
+                                                 B > 1 && tps % p.NT != 0 ? 1 : 0};
+    for (int i = 0; i < IPDM_WGRAD_LAUNCH_FIELDS; ++i) out[i] = f[i];
+    return p.code;
+}
+
 size_t ipdm_conv2d_wgrad_tuned_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
                                                int32_t stride)
 {
@@ -388,21 +456,22 @@ int ipdm_conv2d_wgrad_tuned(const float *d_x, const float *d_dy, float *d_dw, fl
     a.TW = p.TW; a.twlog = p.twlog; a.TH = p.TH; a.XH = p.XH; a.XW = p.XWP; a.XPS = p.XPS;
     a.tiles_x = p.tiles_x; a.tiles_per_sample = p.tiles_x * p.tiles_y; a.NT = p.NT; a.cig = p.cig;
     a.tiles = p.tiles; a.magic = p.magic;
-    int rc;
-    if (p.code == 1) {
-        // the instantiation is the smallest that holds the layer's blocks: 1 or 2 blocks of 16 output channels, and the
-        // (input channel, tap) blocks of min(Cin, cig) channels
-        const bool one = Cout <= 16;
-#define IPDM_WG_LAUNCH(KS_, S_, NB_) (one ? launch<KS_, S_, 1, NB_, true>(p, a, st) : launch<KS_, S_, 2, NB_, true>(p, a, st))
-        if (ksize == 1) rc = Cin <= 16 ? IPDM_WG_LAUNCH(1, 1, 1) : IPDM_WG_LAUNCH(1, 1, 4);
-        else if (stride == 1) rc = Cin <= 8 ? IPDM_WG_LAUNCH(3, 1, 5) : Cin <= 16 ? IPDM_WG_LAUNCH(3, 1, 9) : IPDM_WG_LAUNCH(3, 1, 18);
-        else rc = Cin <= 8 ? IPDM_WG_LAUNCH(3, 2, 5) : IPDM_WG_LAUNCH(3, 2, 9);
-#undef IPDM_WG_LAUNCH
-    } else {
-        if (ksize == 1) rc = launch<1, 1, 1, 2, false>(p, a, st);
-        else if (stride == 1) rc = launch<3, 1, 1, 9, false>(p, a, st);
-        else rc = launch<3, 2, 1, 5, false>(p, a, st);
-    }
+    // the 17 instantiations: the one pick_instantiation names, or none
+    const WInst w = pick_instantiation(p);
+    int rc = IPDM_ERR_UNSUPPORTED;
+    bool found = false;
+#define IPDM_WG_IS(KS_, S_, MB_, NB_, PIX_) (w.KS == KS_ && w.S == S_ && w.MBW == MB_ && w.NBW == NB_ && w.PIX == (PIX_ ? 1 : 0))
+#define IPDM_WG_ONE(KS_, S_, MB_, NB_, PIX_) \
+    if (!found && IPDM_WG_IS(KS_, S_, MB_, NB_, PIX_)) { found = true; rc = launch<KS_, S_, MB_, NB_, PIX_>(p, a, st); }
+#define IPDM_WG_STREAMED(KS_, S_, NB_) IPDM_WG_ONE(KS_, S_, 1, NB_, true) IPDM_WG_ONE(KS_, S_, 2, NB_, true)
+    IPDM_WG_STREAMED(1, 1, 1) IPDM_WG_STREAMED(1, 1, 4)
+    IPDM_WG_STREAMED(3, 1, 5) IPDM_WG_STREAMED(3, 1, 9) IPDM_WG_STREAMED(3, 1, 18)
+    IPDM_WG_STREAMED(3, 2, 5) IPDM_WG_STREAMED(3, 2, 9)
+    IPDM_WG_ONE(1, 1, 1, 2, false) IPDM_WG_ONE(3, 1, 1, 9, false) IPDM_WG_ONE(3, 2, 1, 5, false)
+#undef IPDM_WG_STREAMED
+#undef IPDM_WG_ONE
+#undef IPDM_WG_IS
+    IPDM_REQUIRE(found, "ipdm_conv2d_wgrad_tuned: no kernel <%d,%d,%d,%d,%d> was built", w.KS, w.S, w.MBW, w.NBW, w.PIX);
     if (rc) return rc;
     conv_wgrad_fold_kernel<float><<<cdiv((long)p.part_elems, 32), WT_THREADS, 0, st>>>(a.part, d_dw, p.part_elems, p.parts);
     IPDM_LAUNCH_CHECK();

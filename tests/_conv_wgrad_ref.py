@@ -1,6 +1,7 @@
 """Shared by tests/test_conv_wgrad_host.py and tests/test_gpu_conv_wgrad.py: the shapes csrc/conv_wgrad.hip is tested on with the
-code and the plan properties each was chosen for, their inputs and float64 / float32 references, the plan query as a dict, and a
-numpy restatement of the kernels' summation order built from the plan fields alone."""
+code and the plan properties each was chosen for, their inputs and float64 / float32 references, the plan query and the launch
+query as dicts, the launch class of a shape (the key of the coverage rule), and a numpy restatement of the kernels' summation order
+built from the plan fields alone."""
 import ctypes
 import functools
 
@@ -10,6 +11,7 @@ import torch
 from ipdm_pytorch_amd import synth
 
 FIELDS = ("code", "parts", "part_pixels", "chain", "TH", "TW", "NT", "strips", "cog", "cig", "ncog", "ncig", "tap_split", "fold_lanes")
+LAUNCH_FIELDS = ("KS", "S", "MBW", "NBW", "streamed", "staging_planes", "wgs_full", "wgs_guarded", "crosses_sample")
 CHAIN_MAX = 1024          # WG_CHAIN_MAX of csrc/conv_wgrad.hip: the longest f32 chain any plan may name
 TILE_PIX = 256
 
@@ -31,6 +33,65 @@ NEW_SHAPES = {
 }
 
 
+def _cls(code, inst, TW, NT, loop, cross=True, last=True, rw=True):
+    """A case chosen for a launch class a production step runs: the instantiation <KS, S, MBW, NBW>, the tile width, NT, and
+    which multiply loops its workgroups take ("straight": every wave of every workgroup; "guarded": no workgroup all
+    straight-line; "both").  Every such case has a ragged last tile row and, but for `rw`, tile column; `cross`: a strip holds
+    tiles of two samples; `last`: the last strip is short."""
+    return code, dict(inst=inst, TW=TW, NT=NT, has_full=loop != "guarded", has_guarded=loop != "straight", crosses_sample=cross,
+                      ragged_last_strip=last, ragged_w=rw, ragged_h=True)
+
+
+# The launch classes of the production layers (tools/conv_grad_bench.conv_shapes at B = 1 and 8) that the shapes above do not run,
+# each at the smallest shape that reaches it: NT >= 2, so the accumulators are carried over tiles, the staging loop and its barrier
+# pair run again and db adds per tile; B > 1 with a tile count per sample that NT does not divide, so a strip crosses a sample.
+# One tile column of 35 (17) live pixels keeps a shape small but leaves the right of a window unread: the stride-2 windows of the
+# wide tiles, which no other case stages, get three shapes that read every column (a window wrong past column 64 passed without).
+# tests/test_conv_wgrad_host.py fails when a production class has no case here.
+PRODUCTION_SHAPES = {
+    # streamed, TW = 64, NT = 2
+    (3, 4, 8, 681, 35, 1, 1): _cls(1, (1, 1, 1, 1), 64, 2, "straight"),
+    (3, 16, 128, 169, 35, 1, 1): _cls(1, (1, 1, 2, 1), 64, 2, "straight"),
+    (3, 24, 16, 681, 35, 1, 1): _cls(1, (1, 1, 1, 4), 64, 2, "guarded"),
+    (3, 144, 16, 225, 35, 1, 1): _cls(1, (1, 1, 1, 4), 64, 2, "both"),               # three input groups, the last ragged
+    (3, 1, 4, 681, 35, 3, 1): _cls(1, (3, 1, 1, 5), 64, 2, "guarded"),
+    (3, 8, 8, 681, 35, 3, 1): _cls(1, (3, 1, 1, 5), 64, 2, "straight"),
+    (3, 12, 8, 681, 35, 3, 1): _cls(1, (3, 1, 1, 9), 64, 2, "guarded"),
+    (3, 16, 16, 681, 35, 3, 1): _cls(1, (3, 1, 1, 9), 64, 2, "straight"),
+    (3, 24, 16, 681, 35, 3, 1): _cls(1, (3, 1, 1, 18), 64, 2, "guarded"),
+    (3, 32, 16, 681, 35, 3, 1): _cls(1, (3, 1, 1, 18), 64, 2, "straight"),
+    (3, 144, 16, 137, 35, 3, 1): _cls(1, (3, 1, 1, 18), 64, 2, "both"),              # five input groups, the last ragged
+    (2, 1, 64, 513, 35, 3, 1): _cls(1, (3, 1, 2, 5), 64, 2, "guarded", last=False),  # the img stem: two output groups
+    (3, 16, 128, 169, 35, 3, 1): _cls(1, (3, 1, 2, 9), 64, 2, "straight"),
+    (2, 64, 1, 513, 35, 3, 1): _cls(1, (3, 1, 1, 18), 64, 2, "straight", last=False),   # the eps conv: two input groups
+    (3, 8, 8, 465, 261, 3, 2): _cls(1, (3, 2, 1, 5), 64, 2, "straight"),             # stride 2 at the 9 x 129 window, all of its width
+    (3, 16, 16, 1361, 69, 3, 2): _cls(1, (3, 2, 1, 9), 64, 2, "straight"),
+    # streamed, an odd NT as the narrow proj layers run (7), and the one production class with NT = 1
+    (3, 4, 8, 2401, 35, 1, 1): _cls(1, (1, 1, 1, 1), 64, 7, "straight"),
+    (1, 16, 16, 41, 75, 3, 2): _cls(1, (3, 2, 1, 9), 64, 1, "straight", cross=False, last=False),
+    # tiled, NT = 4: chains of 1024, the longest a plan may name.  <3,2,1,5> tiled: 9 column blocks of a 16-channel group over two
+    # wave pairs of 5 -- the second pair is always guarded
+    (3, 128, 256, 41, 70, 1, 1): _cls(2, (1, 1, 1, 2), 64, 4, "straight"),
+    (3, 256, 256, 81, 17, 1, 1): _cls(2, (1, 1, 1, 2), 32, 4, "straight"),
+    (2, 144, 128, 169, 35, 1, 1): _cls(2, (1, 1, 1, 2), 64, 4, "both"),
+    (3, 64, 64, 169, 70, 3, 1): _cls(2, (3, 1, 1, 9), 64, 4, "straight"),
+    (3, 128, 128, 169, 17, 3, 1): _cls(2, (3, 1, 1, 9), 32, 4, "straight"),
+    (3, 144, 128, 33, 70, 3, 1): _cls(2, (3, 1, 1, 9), 64, 4, "both"),
+    (3, 64, 64, 337, 69, 3, 2): _cls(2, (3, 2, 1, 5), 64, 4, "guarded"),             # stride 2 at the 9 x 129 window, pitch 138
+    (3, 128, 128, 161, 33, 3, 2): _cls(2, (3, 2, 1, 5), 32, 4, "guarded"),           # stride 2 at the 17 x 65 window, pitch 74
+    # tiled, NT = 3 and NT = 1 (the 1 x 1 layers at the coarse levels)
+    (2, 128, 128, 209, 35, 1, 1): _cls(2, (1, 1, 1, 2), 64, 3, "straight"),
+    (2, 128, 128, 417, 17, 1, 1): _cls(2, (1, 1, 1, 2), 32, 3, "straight"),
+    (2, 64, 64, 385, 35, 3, 1): _cls(2, (3, 1, 1, 9), 64, 3, "straight"),
+    (2, 64, 64, 769, 17, 3, 1): _cls(2, (3, 1, 1, 9), 32, 3, "straight"),
+    (2, 64, 64, 193, 139, 3, 2): _cls(2, (3, 2, 1, 5), 64, 3, "guarded"),            # the 9 x 129 window, all of its width (Wo = 70)
+    (2, 64, 64, 833, 64, 3, 2): _cls(2, (3, 2, 1, 5), 32, 3, "guarded", rw=False),   # the 17 x 65 window, all of it: 64 -> 32, as trained
+    (1, 64, 64, 9, 40, 1, 1): _cls(2, (1, 1, 1, 2), 64, 1, "straight", cross=False, last=False),
+    (1, 64, 64, 17, 20, 1, 1): _cls(2, (1, 1, 1, 2), 32, 1, "straight", cross=False, last=False),
+}
+NEW_SHAPES.update(PRODUCTION_SHAPES)
+
+
 def out_hw(geo):
     B, Cin, Cout, H, W, k, s = geo
     return (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
@@ -47,13 +108,45 @@ def plan(geo):
     return p
 
 
+def launch(geo):
+    """ipdm_conv2d_wgrad_tuned_launch as a dict (host only): what the launcher decides beyond the plan."""
+    from ipdm_pytorch_amd import _lib
+    out = (ctypes.c_int32 * len(LAUNCH_FIELDS))()
+    code = _lib.lib().ipdm_conv2d_wgrad_tuned_launch(*geo, out, len(LAUNCH_FIELDS))
+    assert code >= 0, _lib.lib().ipdm_last_error().decode()
+    q = dict(zip(LAUNCH_FIELDS, (int(v) for v in out)))
+    q["inst"] = tuple(q[k] for k in ("KS", "S", "MBW", "NBW"))
+    return q
+
+
+def nt_class(code, NT):
+    """The NT key of a launch class: 1 or more than one tile per strip; the tiled code apart at its longest chain."""
+    return "1" if NT == 1 else "2+" if code == 1 else "2..3" if NT < CHAIN_MAX // TILE_PIX else "4"
+
+
+def launch_classes(geo):
+    """{(instantiation, streamed, TW, NT key, loop)}: one class per kind of multiply loop ("straight" / "guarded") that some
+    workgroup of the launch takes -- from the two queries, nothing restated."""
+    p, q = plan(geo), launch(geo)
+    assert p["code"] in (1, 2) and q["streamed"] == (1 if p["code"] == 1 else 0), (geo, p, q)
+    assert q["wgs_full"] + q["wgs_guarded"] == p["strips"] * p["ncog"] * p["ncig"], (geo, p, q)
+    loops = [name for name, n in (("straight", q["wgs_full"]), ("guarded", q["wgs_guarded"])) if n]
+    return {(q["inst"], q["streamed"], p["TW"], nt_class(p["code"], p["NT"]), loop) for loop in loops}
+
+
 def check_case(geo, code, props):
     """The case bookkeeping: the plan must say what the case was chosen for."""
-    p = plan(geo)
+    p, q = plan(geo), launch(geo)
     Ho, Wo = out_hw(geo)
     assert p["code"] == code, (geo, p)
     for key, want in props.items():
-        if key == "ragged_w":
+        if key in ("inst", "crosses_sample"):
+            assert q[key] == want, (geo, key, p, q)
+        elif key == "has_full":
+            assert (q["wgs_full"] > 0) == want, (geo, key, p, q)
+        elif key == "has_guarded":
+            assert (q["wgs_guarded"] > 0) == want, (geo, key, p, q)
+        elif key == "ragged_w":
             assert (Wo % p["TW"] != 0) == want, (geo, key, p)
         elif key == "ragged_h":
             assert (Ho % p["TH"] != 0) == want, (geo, key, p)
@@ -95,6 +188,13 @@ def wgrad_reference(geo, x, dy):
     for r, a, y32 in ref.values():
         assert r.dtype == torch.float64 and a.dtype == torch.float64 and y32.dtype == torch.float32
     return ref
+
+
+def exact_reference(geo, x, dy):
+    """(dW, db) in float64 alone: what the whole-number case compares with (no conditioning, no float32 arbiter)."""
+    B, Cin, Cout, H, W, k, s = geo
+    dw = torch.nn.grad.conv2d_weight(x.double(), (Cout, Cin, k, k), dy.double(), stride=s, padding=k // 2)
+    return dw, dy.double().sum((0, 2, 3))
 
 
 @functools.lru_cache(maxsize=None)
@@ -142,12 +242,13 @@ def fold(parts, lanes):
     return total
 
 
-def restate(geo, x, dy):
+def restate(geo, x, dy, elements=None):
     """(dW, db) in the kernels' summation order, from the plan fields: float32 products, one sequential float32 chain per part in
     MFMA k order (four consecutive pixels of a tile row per instruction, added one after the other; np.cumsum adds in index
     order, and a staged zero leaves a float32 sum as it is), the parts folded in float64 in the fold's order, one rounding.  db:
     a float64 sum per wave quarter (4 per strip) folded the same way; the order of the float64 additions inside a quarter is
-    not restated (it moves the sum by 2^-53 of its terms)."""
+    not restated (it moves the sum by 2^-53 of its terms).  elements: a list of (co, ci, ky, kx) -- dW is then the 1-D tensor of
+    those positions alone (a wide layer has too many for a numpy loop)."""
     B, Cin, Cout, H, W, k, s = geo
     p = plan(geo)
     Ho, Wo = out_hw(geo)
@@ -158,15 +259,22 @@ def restate(geo, x, dy):
     xp = np.zeros((B, Cin, H + 2 * pad, W + 2 * pad), np.float32)
     xp[:, :, pad:pad + H, pad:pad + W] = x.numpy()
     dyn = np.ascontiguousarray(dy.numpy().transpose(1, 0, 2, 3)).reshape(Cout, B * Ho * Wo)
-    dw = np.zeros((Cout, Cin, k, k), np.float32)
-    for ci in range(Cin):
-        for ky in range(k):
-            for kx in range(k):
-                xs = np.ascontiguousarray(xp[:, ci, ky:ky + (Ho - 1) * s + 1:s, kx:kx + (Wo - 1) * s + 1:s]).reshape(B * Ho * Wo)
-                for co in range(Cout):
-                    prod = (dyn[co] * xs).astype(np.float32)
-                    run = np.cumsum(np.where(live, prod[safe], np.float32(0)), axis=1, dtype=np.float32)
-                    dw[co, ci, ky, kx] = np.float32(fold(run[:, -1], p["fold_lanes"]))
+
+    def one(co, ci, ky, kx):
+        xs = np.ascontiguousarray(xp[:, ci, ky:ky + (Ho - 1) * s + 1:s, kx:kx + (Wo - 1) * s + 1:s]).reshape(B * Ho * Wo)
+        prod = (dyn[co] * xs).astype(np.float32)
+        run = np.cumsum(np.where(live, prod[safe], np.float32(0)), axis=1, dtype=np.float32)
+        return np.float32(fold(run[:, -1], p["fold_lanes"]))
+
+    if elements is None:
+        dw = np.zeros((Cout, Cin, k, k), np.float32)
+        for ci in range(Cin):
+            for ky in range(k):
+                for kx in range(k):
+                    for co in range(Cout):
+                        dw[co, ci, ky, kx] = one(co, ci, ky, kx)
+    else:
+        dw = np.array([one(*e) for e in elements], np.float32)
     q = chain_index(geo, dict(p, code=1, parts=4 * p["strips"], chain=64 * p["NT"]))
     dq = np.where(q >= 0, dyn.astype(np.float64)[:, np.where(q >= 0, q, 0)], 0.0).sum(2)           # [Cout, 4 strips]
     db = np.array([np.float32(fold(dq[co], p["fold_lanes"])) for co in range(Cout)], np.float32)

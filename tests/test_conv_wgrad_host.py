@@ -1,6 +1,6 @@
 """CPU: the tuned weight gradient (csrc/conv_wgrad.hip, wgrad_backend="hip_tuned") without a device -- the exports and the ctypes
-table, the python surface, the code and the plan as functions of the arguments alone, the refusals before any launch, and the
-yardstick: a numpy restatement of the kernels' summation order (tests/_conv_wgrad_ref.restate: float32 products, a float32
+table, the python surface, the code and the plan as functions of the arguments alone, the launch query and the coverage rule
+(every launch class of a production layer is the class of a GPU case), the refusals before any launch, and the yardstick: a numpy restatement of the kernels' summation order (tests/_conv_wgrad_ref.restate: float32 products, a float32
 chain of the plan's length per part, the parts folded in float64, one rounding) goes through the gate the device is held to,
 against the same arbiter (torch's float32 conv2d_weight on the CPU).  If the restatement passes with room, a miss on the
 device is the kernel's."""
@@ -15,8 +15,8 @@ from tests import _conv_wgrad_ref as wr
 from tests._accuracy import M_ELEM, R_RMS, measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = ("ipdm_conv2d_wgrad_tuned_code", "ipdm_conv2d_wgrad_tuned_plan", "ipdm_conv2d_wgrad_tuned_workspace_bytes",
-           "ipdm_conv2d_wgrad_tuned")
+ENTRIES = ("ipdm_conv2d_wgrad_tuned_code", "ipdm_conv2d_wgrad_tuned_plan", "ipdm_conv2d_wgrad_tuned_launch",
+           "ipdm_conv2d_wgrad_tuned_workspace_bytes", "ipdm_conv2d_wgrad_tuned")
 ERR_INVALID, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -3, -4
 # layers of the production networks whose weight gradient the rule leaves on ipdm_conv2d_wgrad on purpose: none
 EXCLUDED = ()
@@ -35,6 +35,7 @@ def test_error_codes_are_the_header_s():
         m = re.search(r"#define\s+%s\s+\(?(-?\d+)" % name, text)
         assert m and int(m.group(1)) == value, name
     assert "#define IPDM_WGRAD_PLAN_FIELDS %d" % len(wr.FIELDS) in text
+    assert "#define IPDM_WGRAD_LAUNCH_FIELDS %d" % len(wr.LAUNCH_FIELDS) in text
 
 
 def test_exports_and_ctypes_table():
@@ -172,6 +173,74 @@ def test_plan_covers_k_once_and_names_its_chain_and_workspace():
         wr.check_case(geo, code, props)
 
 
+def test_launch_query_is_the_kernel_s_own_decision():
+    """ipdm_conv2d_wgrad_tuned_launch against the kernel text read by hand, on shapes whose answer is plain: the block counts
+    of a wave (`full` in conv_wgrad_kernel), the staging planes, and a strip over two samples counted tile by tile."""
+    lib = _lib().lib()
+    # 12 -> 8, 3 x 3: 108 columns = 7 blocks of 16 < NBW 9: every workgroup guarded; 16 -> 16: 144 columns = 9 blocks: none
+    q, strips = wr.launch((1, 12, 8, 29, 63, 3, 1)), wr.plan((1, 12, 8, 29, 63, 3, 1))["strips"]
+    assert q["inst"] == (3, 1, 1, 9) and q["streamed"] == 1 and q["staging_planes"] == 4 and (q["wgs_full"], q["wgs_guarded"]) == (0, strips)
+    q = wr.launch((1, 16, 16, 29, 63, 3, 1))
+    assert q["inst"] == (3, 1, 1, 9) and (q["wgs_full"], q["wgs_guarded"]) == (strips, 0) and strips == 8
+    # <= 8 (1 x 1: <= 16) input channels: two staging planes per wave
+    assert wr.launch((1, 8, 4, 40, 36, 1, 1))["staging_planes"] == 2 and wr.launch((1, 4, 8, 23, 19, 3, 1))["staging_planes"] == 2
+    assert wr.launch((1, 24, 8, 40, 36, 1, 1))["staging_planes"] == 4 and wr.launch((1, 64, 64, 48, 40, 3, 1))["staging_planes"] == 4
+    # 144 -> 128, 1 x 1 tiled: input groups of 64, 64, 16: the last has one column block, the second wave pair starts at block 2
+    p, q = wr.plan((2, 144, 128, 169, 35, 1, 1)), wr.launch((2, 144, 128, 169, 35, 1, 1))
+    assert q["inst"] == (1, 1, 1, 2) and q["streamed"] == 0
+    assert (q["wgs_full"], q["wgs_guarded"]) == (p["strips"] * 4 * 2, p["strips"] * 4 * 1)
+    # crosses_sample, tile by tile
+    for geo in list(wr.NEW_SHAPES) + [(8,) + tuple(k) for k in production_shapes()]:
+        p, q = wr.plan(geo), wr.launch(geo)
+        Ho, Wo = wr.out_hw(geo)
+        tps = -(-Ho // p["TH"]) * -(-Wo // p["TW"])
+        crosses = any(t0 // tps != (min(t0 + p["NT"], geo[0] * tps) - 1) // tps for t0 in range(0, geo[0] * tps, p["NT"]))
+        assert q["crosses_sample"] == int(crosses), (geo, p, q)
+        assert q["wgs_full"] + q["wgs_guarded"] == p["strips"] * p["ncog"] * p["ncig"]
+    # refusals: those of the plan query; code 0 is all zeros
+    out = (C.c_int32 * len(wr.LAUNCH_FIELDS))()
+    assert lib.ipdm_conv2d_wgrad_tuned_launch(1, 4, 4, 8, 8, 5, 1, out, len(wr.LAUNCH_FIELDS)) == -1
+    assert lib.ipdm_conv2d_wgrad_tuned_launch(1, 4, 4, 8, 8, 3, 1, out, len(wr.LAUNCH_FIELDS) - 1) == -1
+    assert lib.ipdm_conv2d_wgrad_tuned_launch(1, 4, 4, 8, 8, 3, 1, None, len(wr.LAUNCH_FIELDS)) == -1
+    assert lib.ipdm_conv2d_wgrad_tuned_launch(1, 1, 32 * 65536, 1, 1, 1, 1, out, len(wr.LAUNCH_FIELDS)) == 0 and not any(out)
+
+
+def gpu_cases():
+    """The shapes tests/test_gpu_conv_wgrad.py launches (without importing a GPU test module's device state: plain data)."""
+    from tests.test_gpu_conv_grad import SHAPES
+    return list(SHAPES) + list(wr.NEW_SHAPES)
+
+
+def uncovered(cases):
+    """The launch classes of the production layers at B = 1 and B = 8 that no shape of `cases` launches."""
+    have = set().union(*(wr.launch_classes(geo) for geo in cases))
+    want = {}
+    for key in production_shapes():
+        for B in (1, 8):
+            for c in wr.launch_classes((B,) + tuple(key)):
+                want.setdefault(c, (B,) + tuple(key))
+    return {c: geo for c, geo in want.items() if c not in have}, want
+
+
+def test_every_production_launch_class_has_a_gpu_case():
+    """A launch class is (instantiation <KS, S, MBW, NBW>, streamed or tiled, TW, NT == 1 or more -- the tiled code: 1, 2..3, 4,
+    its longest chain --, straight-line or guarded loop), from the two queries.  Every class a production layer launches at
+    B = 1 or B = 8 is the class of a shape the GPU test runs; a new instantiation or tile rule fails here until it has a case.
+    The list is tight: without either of two of its cases a class is uncovered."""
+    cases = gpu_cases()
+    missing, want = uncovered(cases)
+    assert len(want) >= 28
+    assert not missing, "production launch classes without a GPU case (class: first layer): %s" % missing
+    for code in (1, 2):
+        assert any(wr.plan(g)["code"] == code and wr.launch(g)["crosses_sample"] and wr.plan(g)["NT"] >= 2 for g in cases), code
+    # every production case says what it is there for, and the classes it claims are production's
+    for geo, (code, props) in wr.PRODUCTION_SHAPES.items():
+        wr.check_case(geo, code, props)
+        assert wr.launch_classes(geo) & set(want), geo
+    for gone in ((3, 16, 128, 169, 35, 3, 1), (3, 128, 128, 161, 33, 3, 2)):
+        assert gone in cases and uncovered([g for g in cases if g != gone])[0], gone
+
+
 def test_the_entry_refuses_before_the_device():
     lib = _lib().lib()
     d, big = C.c_void_p(256), 1 << 40
@@ -199,23 +268,33 @@ def test_the_entry_refuses_before_the_device():
     assert wr.plan(huge) == dict.fromkeys(wr.FIELDS, 0)
 
 
-# one streamed shape, one tiled shape (both sides wider than 32 channels) and the long-chain shape
-YARDSTICK = [(1, 12, 8, 29, 63, 3, 1), (1, 34, 33, 40, 70, 3, 1), wr.LONG]
+# one streamed shape, one tiled shape (both sides wider than 32 channels), the long-chain shape, and a tiled shape at NT = 4: the
+# tiled chain of 1024 every wide production layer runs
+TILED_LONG = (3, 128, 256, 41, 70, 1, 1)
+YARDSTICK = [(1, 12, 8, 29, 63, 3, 1), (1, 34, 33, 40, 70, 3, 1), wr.LONG, TILED_LONG]
+# a fixed sample of dW positions for a layer too wide to restate whole: 64 (co, ci, ky, kx), spread over both channel ranges
+SAMPLE = {TILED_LONG: [((37 * i + 5) % 256, (53 * i + 7) % 128, 0, 0) for i in range(64)]}
 
 
 @pytest.mark.parametrize("geo", YARDSTICK, ids=["x".join(map(str, g)) for g in YARDSTICK])
 def test_restated_summation_order_passes_the_gate_the_kernels_are_held_to(geo):
     """Measured (rms ratio, of 4 / elementwise ratio, of 8): 12 -> 8 at 29 x 63, chains of 64: dW 0.19 / 0.108, db 0.29 / 0.021;
     34 -> 33 at 40 x 70, chains of 256: dW 0.42 / 0.383, db 0.18 / 0.026; 4 -> 4 at 3300 x 300, chains of 1024 -- the longest a
-    plan may name: dW 0.04 / 0.036, db 0.14 / 0.000.  An order under the gate, so a miss on the device is the kernel's."""
+    plan may name: dW 0.04 / 0.036, db 0.14 / 0.000; 128 -> 256 at 3 x 41 x 70, 1 x 1, TILED chains of 1024 (NT = 4, 64 sampled
+    positions of dW, all of db): dW 0.69 / 0.302, db 0.19 / 0.018.  An order under the gate, so a miss on the device is the kernel's."""
     p = wr.plan(geo)
-    assert p["code"] == (2 if geo == YARDSTICK[1] else 1)
-    if geo == wr.LONG:
+    assert p["code"] == (2 if geo in (YARDSTICK[1], TILED_LONG) else 1)
+    if geo in (wr.LONG, TILED_LONG):
         assert p["chain"] == wr.CHAIN_MAX
     (x, dy), ref = wr.reference(geo, 8100 + YARDSTICK.index(geo))
-    dw, db = wr.restate(geo, x, dy)
+    elements = SAMPLE.get(geo)
+    dw, db = wr.restate(geo, x, dy, elements=elements)
     for what, got in (("dw", dw), ("db", db)):
         r, a, y32 = ref[what]
+        if what == "dw" and elements is not None:
+            assert len(set(elements)) == len(elements) <= 64
+            at = tuple(torch.tensor(v) for v in zip(*elements))
+            r, a, y32 = r[at], a[at], y32[at]
         assert got.shape == r.shape and got.dtype == torch.float32
         rr, er = measure(got, y32, r, a)
         print("conv_wgrad restated %s %s chains of %d: rms %.2f (<= %g)  elem %.3f (<= %g)" % (what, "x".join(map(str, geo)), p["chain"],

@@ -1,7 +1,9 @@
 """GPU: the tuned weight / bias gradient (csrc/conv_wgrad.hip: ipdm_conv2d_wgrad_tuned, and train.conv2d(..., wgrad="hip_tuned"))
 on every shape of tests/test_gpu_conv_grad.SHAPES plus the shapes of tests/_conv_wgrad_ref.NEW_SHAPES, each of which names the
-code and the plan properties it is there for (the test fails if the plan says otherwise).  Per shape, with dW, db and the
-workspace NaN before every call:
+code and the plan properties it is there for (the test fails if the plan says otherwise).  PRODUCTION_SHAPES among them name a
+launch class a production step runs -- instantiation, tile width, NT, straight-line or guarded loop, a strip over two samples --
+asserted in front of every launch from ipdm_conv2d_wgrad_tuned_plan and ipdm_conv2d_wgrad_tuned_launch.  Per shape, with dW, db
+and the workspace NaN before every call:
 
   gate     dW and db on the float64 gate of tests/test_gpu_conv_grad.gate (r float64 conv2d_weight, a the same on absolute
            values, y32 torch float32 on the CPU)
@@ -92,10 +94,13 @@ def test_whole_numbers_give_the_float64_result_exactly(geo):
     assert B * Ho * Wo * 16 < 2 ** 24
     x, dy = wr.make_inputs(geo, seed_of(geo) + 5, integers=True)
     assert float(x.abs().max()) <= 4 and float(dy.abs().max()) <= 4 and bool((x == x.round()).all()) and len(x.unique()) > 3
-    r = wr.wgrad_reference(geo, x, dy)
+    code, props = CASES[geo]
+    wr.check_case(geo, code, props)
+    rdw, rdb = wr.exact_reference(geo, x, dy)
     dw, db = run(geo, x.to(DEV), dy.to(DEV))
-    assert torch.equal(dw.cpu().double(), r["dw"][0]), (geo, int((dw.cpu().double() != r["dw"][0]).sum()))
-    assert torch.equal(db.cpu().double(), r["db"][0]), geo
+    bad = (dw.cpu().double() != rdw).nonzero()
+    assert torch.equal(dw.cpu().double(), rdw), (geo, len(bad), "first wrong (co, ci, ky, kx): %s" % bad[:8].tolist())
+    assert torch.equal(db.cpu().double(), rdb), (geo, (db.cpu().double() - rdb).tolist())
 
 
 def test_refusals_before_any_launch():
@@ -114,7 +119,10 @@ def test_refusals_before_any_launch():
     assert bool(torch.isnan(dw).all())
 
 
-AUTOGRAD = [g for g in GEOS if g != wr.LONG]
+# every shape chosen for its geometry, and of the production launch classes (NT >= 2, a strip over two samples) one streamed and
+# one tiled: the autograd path adds nothing to them that depends on the class
+AUTOGRAD = [g for g in GEOS if g != wr.LONG and g not in wr.PRODUCTION_SHAPES] + [(3, 16, 128, 169, 35, 1, 1), (3, 128, 256, 41, 70, 1, 1)]
+assert all(g in wr.PRODUCTION_SHAPES and wr.PRODUCTION_SHAPES[g][1]["NT"] >= 2 for g in AUTOGRAD[-2:])
 
 
 @pytest.mark.parametrize("geo", AUTOGRAD, ids=["x".join(str(v) for v in g) for g in AUTOGRAD])
