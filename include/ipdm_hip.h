@@ -443,6 +443,42 @@ size_t ipdm_conv2d_wgrad_tuned_workspace_bytes(int32_t B, int32_t Cin, int32_t C
 int ipdm_conv2d_wgrad_tuned(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
                             int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- the weight / bias gradient of the wide 3 x 3 stride-1 layers in the Winograd F(3 x 3, 2 x 2) domain
+ * (csrc/conv_wgrad_wino.hip), opt-in ----
+ * The arguments and the mathematics of ipdm_conv2d_wgrad_tuned, exact f32 on v_mfma_f32_16x16x4_f32, 16 multiply-adds per 2 x 2
+ * output pixels instead of 36.  IPDM_ABI_VERSION stays 5: additive entries, detected by symbol.
+ *
+ * Code.  3 where the layer is taken: ksize 3, stride 1, both channel counts wider than 32 (where ipdm_conv2d_wgrad_tuned_code
+ *   answers 2); 0 otherwise.  A rule of (Cin, Cout, ksize, stride) alone -- the same for every B, H, W -- and 0 besides only past
+ *   the launch's addressing limits (2^31 - 1025 tiles or more, more than 65535 channel groups on a side).
+ * Plan.  Tiles of 2 x 2 output pixels, (sample, tile row, tile column) order, ceil(H/2) x ceil(W/2) per sample.  A workgroup owns
+ *   32 output x 32 input channels and walks one part: `chain` consecutive tiles (min(1024, all tiles rounded up to a stage)), a
+ *   stage of 16 at a time; a tile past the last adds zeros.  Within a stage, k-step ks = 0..3 adds tiles ks, ks + 4, ks + 8,
+ *   ks + 12 in one MFMA.  Every number is a function of the seven arguments alone, never of the device.
+ * Rounding.  U = A dy A^T and V = B^T x B in float32; the f32 partials [part][16][Cout][Cin] (in d_ws) are added in float64 in
+ *   part order by a second launch, which applies G^T . G in float64 and rounds once.  db: float64 throughout (a lane's four
+ *   pixels, its stages, the sixteen tile lanes by a fixed butterfly, the parts in part order), rounded once.  No atomics, no memset.
+ * Errors.  Those of ipdm_conv2d_wgrad_tuned, all before any launch; the text starts with the entry's name.
+ * Bits.  NOT those of ipdm_conv2d_wgrad_tuned; held to the same float64 gate. */
+/* 3 taken, 0 not taken (the layer goes on as without the option), -1 bad argument.  Host only, answers without a device. */
+int32_t ipdm_conv2d_wgrad_wino_code(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride);
+/* Host only.  out[0..IPDM_WGRAD_WINO_PLAN_FIELDS): code, tile rows, tile columns, tiles per stage, tiles per part (`chain`: the
+ * longest run added into one f32 accumulator), parts, output channels per group, input channels per group, output groups, input
+ * groups, rows (1: a workgroup multiplies all sixteen xi; 4, where parts * output groups * input groups < 256: the row form,
+ * four workgroups per part and pair of groups, each with the four xi of one row of the transformed window; same sums, same order;
+ * 0, where all tiles fit one stage of 16: the sum itself in float64, pixels in (sample, row, column) order, one rounding -- over so
+ * few tiles Winograd's cross-term rounding has nothing to average against; d_ws is required and sized as always, and not touched).
+ * All 0 for code 0.  Returns the code, -1 for a bad argument or n < IPDM_WGRAD_WINO_PLAN_FIELDS. */
+#define IPDM_WGRAD_WINO_PLAN_FIELDS 11
+int32_t ipdm_conv2d_wgrad_wino_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride,
+                                    int32_t *out, int32_t n);
+/* d_ws of the call below: parts * 16 * Cout * Cin floats (rounded up to 16 bytes) + parts * Cout doubles; 0 for code <= 0 */
+size_t ipdm_conv2d_wgrad_wino_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
+                                              int32_t stride);
+/* d_x [B,Cin,H,W], d_dy [B,Cout,H,W] -> d_dw [Cout,Cin,3,3], d_db [Cout] or NULL */
+int ipdm_conv2d_wgrad_wino(const float *d_x, const float *d_dy, float *d_dw, float *d_db, int32_t B, int32_t Cin, int32_t Cout,
+                           int32_t H, int32_t W, int32_t ksize, int32_t stride, void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- the same forward and input gradient on the tuned inference kernels (csrc/conv_tuned.hip), opt-in ----
  * The wide layers' forward and input gradient through the inference dispatcher (the kernels of ipdm_conv_kernel_code's numbering),
  * with the packed weight images written on the DEVICE from the live [Cout,Cin,k,k] parameters in front of every launch.  A layer has

@@ -131,6 +131,10 @@ PROTOTYPES = {
     "ipdm_conv2d_wgrad_tuned_launch": (_i32, [_i32] * 7 + [C.POINTER(_i32), _i32]),
     "ipdm_conv2d_wgrad_tuned_workspace_bytes": (_sz, [_i32] * 7),
     "ipdm_conv2d_wgrad_tuned": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "ipdm_conv2d_wgrad_wino_code": (_i32, [_i32] * 7),
+    "ipdm_conv2d_wgrad_wino_plan": (_i32, [_i32] * 7 + [C.POINTER(_i32), _i32]),
+    "ipdm_conv2d_wgrad_wino_workspace_bytes": (_sz, [_i32] * 7),
+    "ipdm_conv2d_wgrad_wino": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
     "ipdm_conv2d_tuned_code": (_i32, [_i32] * 8),
     "ipdm_conv2d_tuned_workspace_bytes": (_sz, [_i32] * 8),
     "ipdm_conv2d_fprop_tuned": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),

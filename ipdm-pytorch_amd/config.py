@@ -60,6 +60,9 @@ _FLAGS = [
     # the weight / bias gradient of the convolutions: "hip" = ipdm_conv2d_wgrad, "hip_tuned" = the streamed / tiled kernels of
     # csrc/conv_wgrad.hip where their rule takes the layer (independent of conv_backend "hip" | "hip_tuned"; not with "torch")
     ("wgrad_backend", str, "hip", None),
+    # under wgrad_backend="hip_tuned": the wide 3 x 3 stride-1 layers' weight gradient in the Winograd F(3 x 3, 2 x 2) domain
+    # (csrc/conv_wgrad_wino.hip) where ipdm_conv2d_wgrad_wino_code takes the layer
+    ("wgrad_wino", bool, False, None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 NORMAL_BACKENDS = ("sklearn", "hip")
@@ -106,6 +109,17 @@ def check_wgrad_backend(opt):
     if getattr(opt, "conv_backend", "hip") == "torch":
         raise ValueError("wgrad_backend=%r needs conv_backend \"hip\" or \"hip_tuned\", not \"torch\"" % (value,))
     return {"wgrad_backend": value}
+
+
+def check_wgrad_wino(opt):
+    """The wgrad_wino key of a training run: {} at its default (or where the options lack the key), so that a default run hands
+    Trainer the four keywords of check_train_backends alone; {"wgrad_wino": True} otherwise.  It is refused unless
+    wgrad_backend is "hip_tuned": the option chooses among that backend's kernels."""
+    if not getattr(opt, "wgrad_wino", False):
+        return {}
+    if getattr(opt, "wgrad_backend", WGRAD_BACKENDS[0]) != "hip_tuned":
+        raise ValueError("wgrad_wino needs wgrad_backend=\"hip_tuned\", not %r" % (getattr(opt, "wgrad_backend", WGRAD_BACKENDS[0]),))
+    return {"wgrad_wino": True}
 
 
 def default_cfg(argv=None):

@@ -85,7 +85,11 @@ _CONV_PASSES = {
 }
 
 
-def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None):
+# the weight gradient's entry in front of the tuned one under wgrad_wino: (entry, its code query, its workspace query)
+_WGRAD_WINO = ("ipdm_conv2d_wgrad_wino", "ipdm_conv2d_wgrad_wino_code", "ipdm_conv2d_wgrad_wino_workspace_bytes")
+
+
+def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None, wgrad_wino=False):
     """The entry that runs `pass_` ("fprop", "dgrad" or "wgrad") of the layer geo = (B, Cin, Cout, H, W, k, stride), the kernel code
     it will take and the workspace it asks for: the one place that knows which of the training convolutions' entries a pass goes to.
 
@@ -96,11 +100,21 @@ def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None):
     and so does a workspace of 0 bytes for the entry chosen: a refusal is never a reason to take the other entry.  Nothing is
     remembered between calls (the tuned codes follow the option table).
 
+    wgrad_wino (with wgrad_tuned; the weight gradient alone): ipdm_conv2d_wgrad_wino_code is asked first.  Non-zero (3: a wide
+    3 x 3 stride-1 layer) goes to ipdm_conv2d_wgrad_wino (csrc/conv_wgrad_wino.hip) with its own workspace query; 0 goes on exactly
+    as without the option.  A negative code or a workspace of 0 bytes raises here too.
+
     shared: a route of the same layer made just before.  Where it and this one both end on conv_grad.hip's entries its size is
     taken over unasked -- the backward's two passes then make one query and share one allocation."""
     default, entry, code_query, bytes_query, lead = _CONV_PASSES[pass_]
     code = 0
-    if (wgrad_tuned if pass_ == "wgrad" else tuned):
+    if pass_ == "wgrad" and wgrad_tuned and wgrad_wino:
+        code = getattr(lib(), _WGRAD_WINO[1])(*geo)
+        if code < 0:
+            raise IpdmError("%s failed (%d): %s" % (_WGRAD_WINO[1], code, lib().ipdm_last_error().decode()))
+        if code:
+            entry, code_query, bytes_query = _WGRAD_WINO
+    if not code and (wgrad_tuned if pass_ == "wgrad" else tuned):
         code = getattr(lib(), code_query)(*lead, *geo)
         if code < 0:
             raise IpdmError("%s failed (%d): %s" % (code_query, code, lib().ipdm_last_error().decode()))
@@ -118,7 +132,7 @@ def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None):
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride, tuned, wgrad_tuned=False):
+    def forward(ctx, x, w, b, stride, tuned, wgrad_tuned=False, wgrad_wino=False):
         x, w = x.contiguous(), w.contiguous()
         b = None if b is None else b.contiguous()
         geo = _geometry(x, w, stride)
@@ -130,7 +144,7 @@ class _Conv2d(torch.autograd.Function):
             ws = _scratch(route.workspace_bytes, x.device)
             call(route.entry, ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(ws), ws.numel(), _lib.current_stream())
         ctx.save_for_backward(x, w)
-        ctx.geo, ctx.has_bias, ctx.tuned, ctx.wgrad_tuned = geo, b is not None, tuned, wgrad_tuned
+        ctx.geo, ctx.has_bias, ctx.tuned, ctx.wgrad_tuned, ctx.wgrad_wino = geo, b is not None, tuned, wgrad_tuned, wgrad_wino
         return y
 
     @staticmethod
@@ -143,7 +157,8 @@ class _Conv2d(torch.autograd.Function):
         dx = dw = db = None
         with torch.cuda.device(x.device):
             dgrad = conv_route("dgrad", geo, tuned=ctx.tuned) if need_x else None
-            wgrad = conv_route("wgrad", geo, wgrad_tuned=ctx.wgrad_tuned, shared=dgrad) if need_w or need_b else None
+            wgrad = (conv_route("wgrad", geo, wgrad_tuned=ctx.wgrad_tuned, shared=dgrad, wgrad_wino=ctx.wgrad_wino)
+                     if need_w or need_b else None)
             # a workspace per pass that runs; the passes that stay on conv_grad.hip share one (one query sizes it for both)
             plain = [r for r in (dgrad, wgrad) if r is not None and r.code == 0]
             plain_ws = _scratch(plain[0].workspace_bytes, x.device) if plain else None
@@ -156,10 +171,10 @@ class _Conv2d(torch.autograd.Function):
                 db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if need_b else None
                 ws = _scratch(wgrad.workspace_bytes, x.device) if wgrad.code else plain_ws
                 call(wgrad.entry, ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(ws), ws.numel(), _lib.current_stream())
-        return dx, (dw if need_w else None), db, None, None, None
+        return dx, (dw if need_w else None), db, None, None, None, None
 
 
-def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip"):
+def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip", wgrad_wino=False):
     """F.conv2d(x, w, b, stride, padding=k // 2) for the reference's layers (k 1 or 3; stride 2 with k 3 only), differentiable
     once: forward, input gradient and weight / bias gradient are HIP kernels on torch's current stream.  Only the gradients
     autograd asks for are computed (the stem's input gradient, the largest one, never is).
@@ -171,12 +186,16 @@ def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip"):
 
     wgrad="hip_tuned" (independent of tuned=) sends the weight / bias gradient through ipdm_conv2d_wgrad_tuned (the streamed /
     tiled kernels of csrc/conv_wgrad.hip) where ipdm_conv2d_wgrad_tuned_code is non-zero, and through ipdm_conv2d_wgrad where it
-    is 0; other bits than wgrad="hip", the same float64 gate.
+    is 0; other bits than wgrad="hip", the same float64 gate.  wgrad_wino=True (with wgrad="hip_tuned" only) sends the layers
+    ipdm_conv2d_wgrad_wino_code takes (3 x 3, stride 1, both sides wider than 32 channels) through ipdm_conv2d_wgrad_wino, the
+    Winograd-domain kernel of csrc/conv_wgrad_wino.hip, instead; other bits again, the same gate.
 
     conv_route decides each pass.  A failing query or call raises: there is no fall-back after a failure."""
     if wgrad not in WGRAD_BACKENDS:
         raise ValueError("wgrad must be one of %s, not %r" % (WGRAD_BACKENDS, wgrad))
-    return _Conv2d.apply(x, w, b, int(stride), bool(tuned), wgrad == "hip_tuned")
+    if wgrad_wino and wgrad != "hip_tuned":
+        raise ValueError("wgrad_wino needs wgrad=\"hip_tuned\", not %r" % (wgrad,))
+    return _Conv2d.apply(x, w, b, int(stride), bool(tuned), wgrad == "hip_tuned", bool(wgrad_wino))
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm (+SiLU) under autograd
@@ -322,6 +341,7 @@ class Conv(nn.Module):
     def __init__(self, cin, cout, k, stride=1, bias=True, backend="hip"):
         super().__init__()
         self.stride, self.backend, self.wgrad = stride, backend, "hip"      # wgrad: set by TrainUNet(wgrad_backend=...)
+        self.wgrad_wino = False                                             # set by TrainUNet(wgrad_wino=...)
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k))
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if bias:
@@ -332,7 +352,8 @@ class Conv(nn.Module):
 
     def forward(self, x):
         if self.backend in ("hip", "hip_tuned"):
-            return conv2d(x, self.weight, self.bias, self.stride, tuned=self.backend == "hip_tuned", wgrad=self.wgrad)
+            return conv2d(x, self.weight, self.bias, self.stride, tuned=self.backend == "hip_tuned", wgrad=self.wgrad,
+                          wgrad_wino=self.wgrad_wino)
         return F.conv2d(x, self.weight, self.bias, stride=self.stride, padding=self.weight.shape[-1] // 2)
 
 
@@ -434,7 +455,7 @@ class TrainUNet(nn.Module):
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(8, 16),
                  dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True, num_heads=4, pre_downsample_times=1,
-                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip"):
+                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip", wgrad_wino=False):
         super().__init__()
         if dropout:
             raise NotImplementedError("dropout is never instantiated by the reference harness (Model/model.py:198)")
@@ -451,6 +472,8 @@ class TrainUNet(nn.Module):
         if wgrad_backend != "hip" and conv_backend == "torch":
             raise ValueError("wgrad_backend=%r needs conv_backend \"hip\" or \"hip_tuned\": conv_backend=\"torch\" leaves the "
                              "weight gradient to torch" % (wgrad_backend,))
+        if wgrad_wino and wgrad_backend != "hip_tuned":
+            raise ValueError("wgrad_wino needs wgrad_backend=\"hip_tuned\", not %r" % (wgrad_backend,))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks, self.num_heads = num_res_blocks, num_heads
         self.attention_resolutions, self.channel_mult = tuple(attention_resolutions), tuple(channel_mult)
@@ -487,10 +510,10 @@ class TrainUNet(nn.Module):
                     ds //= 2
                 self.up_blocks.append(_Stage(layers))
         self.out = nn.Sequential(_norm(ch), nn.SiLU(), Conv(ch, out_channels, 3, backend=be))
-        self.wgrad_backend = wgrad_backend
+        self.wgrad_backend, self.wgrad_wino = wgrad_backend, bool(wgrad_wino)
         for m in self.modules():
             if isinstance(m, Conv):
-                m.wgrad = wgrad_backend
+                m.wgrad, m.wgrad_wino = wgrad_backend, self.wgrad_wino
 
     def unet_kwargs(self):
         """The constructor arguments of a UNetModel of the same topology."""
@@ -514,9 +537,10 @@ class TrainUNet(nn.Module):
     def wgrad_routes(self, shape):
         """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name -> the
         code of its weight / bias gradient under wgrad_backend="hip_tuned" (ipdm_conv2d_wgrad_tuned_code: 1 streamed, 2 tiled;
-        0: the layer stays on ipdm_conv2d_wgrad, as every layer does under the default).  Host only."""
+        0: the layer stays on ipdm_conv2d_wgrad, as every layer does under the default; 3: ipdm_conv2d_wgrad_wino, the layers
+        ipdm_conv2d_wgrad_wino_code takes under wgrad_wino).  Host only."""
         tuned = self.wgrad_backend == "hip_tuned"
-        return self._conv_walk(shape, lambda geo: conv_route("wgrad", geo, wgrad_tuned=tuned).code)
+        return self._conv_walk(shape, lambda geo: conv_route("wgrad", geo, wgrad_tuned=tuned, wgrad_wino=self.wgrad_wino).code)
 
     def _conv_walk(self, shape, code):
         """name -> code((B, Cin, Cout, H, W, k, stride)) of every convolution, the walk following forward() on shapes."""
@@ -769,7 +793,7 @@ class Trainer:
     torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip")."""
 
     def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch",
-                 wgrad_backend="hip"):
+                 wgrad_backend="hip", wgrad_wino=False):
         from .diffusion import GaussianDiffusion, NoiseSource
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
@@ -784,7 +808,7 @@ class Trainer:
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
             self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend,
-                                   wgrad_backend=wgrad_backend, **kw).to(self.device)
+                                   wgrad_backend=wgrad_backend, wgrad_wino=wgrad_wino, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
         adam = HipAdam if optim_backend == "hip" else torch.optim.Adam
@@ -908,14 +932,14 @@ class progressive_domain_trainer:
     Single process: the reference's train() has no gradient all-reduce either.  The reference has no EMA."""
 
     def __init__(self, opt, result_save_path=None):
-        from .config import check_train_backends, check_wgrad_backend
+        from .config import check_train_backends, check_wgrad_backend, check_wgrad_wino
         if opt.mode not in ("train_img", "train_proj"):
             raise ValueError("progressive_domain_trainer runs mode 'train_img' or 'train_proj', not %r (progressive_domain_denoiser "
                              "runs the test_* modes)" % (opt.mode,))
         self.opt, self.opt_temp = opt, copy.deepcopy(opt)
         self.domain = "img" if opt.mode == "train_img" else "proj"
         self.rank = 0
-        backends = dict(check_train_backends(opt), **check_wgrad_backend(opt))
+        backends = dict(check_train_backends(opt), **check_wgrad_backend(opt), **check_wgrad_wino(opt))
         self.train_seed = int(getattr(opt, "train_seed", 0))
         self.result_save_path = result_save_path
         run = "%s_%s" % (opt.model_name, opt.run_name)

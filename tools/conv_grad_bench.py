@@ -18,7 +18,13 @@ and one whole Trainer.step per network under the three conv_backend arms (same i
 norm_backend "torch" and "hip", and under conv_backend="hip_tuned" with wgrad_backend "hip" and "hip_tuned" beside the torch arm.
 --ops restricts the per-layer arms (e.g. --ops wgrad: the weight-gradient arms alone).
 
+  wino   ipdm_conv2d_wgrad_wino (csrc/conv_wgrad_wino.hip: the Winograd-domain weight gradient, with the bias gradient) on the
+         layers ipdm_conv2d_wgrad_wino_code takes -- wgrad_backend="hip_tuned" with wgrad_wino; an arm beside tuned_wgrad, the
+         yardstick, in the same process, and an arm of the wgrad Trainer.step table.  --wino runs those layers' weight-gradient
+         arms and that step table alone.
+
     python tools/conv_grad_bench.py --out profiles/r29_conv_grad_bench.json
+    python tools/conv_grad_bench.py --wino --out profiles/r33_conv_grad_bench.json
 """
 import argparse
 import ctypes
@@ -140,7 +146,7 @@ def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
         "torch_wgrad": lambda: back(dy, x, w, [Cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [False, True, True]),
     }
     arms = {k: v for k, v in arms.items() if k.split("_")[1] in ops}
-    wplan = (ctypes.c_int32 * 14)()
+    wplan, wino_plan = (ctypes.c_int32 * 14)(), (ctypes.c_int32 * 11)()
     for role, op in enumerate(("fprop", "dgrad", "wgrad")):
         if not tuned[op].code or op not in ops:
             continue
@@ -150,6 +156,10 @@ def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
             if tuned[op].code == 1:
                 x2, dy2 = torch.empty_like(x), torch.empty_like(dy)
                 arms["copy_floor"] = lambda: (x2.copy_(x), dy2.copy_(dy))
+            wino = conv_route("wgrad", geo, wgrad_tuned=True, wgrad_wino=True)
+            if wino.code == 3:
+                arms["wino_wgrad"] = launch("wgrad", wino)
+                lib().ipdm_conv2d_wgrad_wino_plan(*geo, wino_plan, 11)
         else:                   # the packer launch alone, of the image the code's kernel reads (csrc/conv_tuned.hip: reads_wino)
             image = 1 if tuned[op].code in (1, 2, 9, 12) else 0
             img = torch.empty(lib().ipdm_conv_image_bytes(image, role, Cin, Cout, k, s), dtype=torch.uint8, device=dev)
@@ -169,6 +179,18 @@ def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
         rec["tuned_wgrad_over_copy_floor"] = out["tuned_wgrad"]["median_ms"] / out["copy_floor"]["median_ms"]
     if "tuned_wgrad" in out:
         rec["tuned_over_torch_wgrad"] = out["tuned_wgrad"]["median_ms"] / out["torch_wgrad"]["median_ms"]
+    if "wino_wgrad" in out:
+        t, w = out["tuned_wgrad"], out["wino_wgrad"]
+        rec["wgrad_wino_workspace_bytes"] = int(wino.workspace_bytes)
+        rec["wgrad_wino_plan"] = {"tiles_y": int(wino_plan[1]), "tiles_x": int(wino_plan[2]), "stage": int(wino_plan[3]),
+                                  "chain": int(wino_plan[4]), "parts": int(wino_plan[5]), "ncog": int(wino_plan[8]), "ncig": int(wino_plan[9]), "rows": int(wino_plan[10])}
+        rec["wino_over_tuned_wgrad"] = w["median_ms"] / t["median_ms"]
+        rec["wino_over_torch_wgrad"] = w["median_ms"] / out["torch_wgrad"]["median_ms"]
+        rec["wino_wgrad_TFLOPs_direct_equivalent"] = flop / (w["median_ms"] * 1e-3) / 1e12
+        # faster (or slower) only when the medians differ by more than both arms' min-to-max spreads
+        spread = max(t["max_ms"] - t["min_ms"], w["max_ms"] - w["min_ms"])
+        rec["wino_verdict"] = ("faster" if t["median_ms"] - w["median_ms"] > spread else
+                               "slower" if w["median_ms"] - t["median_ms"] > spread else "within spread")
     for op in ops:
         h, t = out["hip_" + op]["median_ms"], out["torch_" + op]["median_ms"]
         rec["hip_%s_TFLOPs" % op] = flop / (h * 1e-3) / 1e12
@@ -188,8 +210,10 @@ def bench_wgrad_steps(opt, domain, rounds, norm_backend="torch"):
     images = torch.rand((1, H, W)) * (4.0 if domain == "proj" else 0.3)
     arms = {"wgrad_hip": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend),
             "wgrad_hip_tuned": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend, wgrad_backend="hip_tuned"),
+            "wgrad_wino": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend, wgrad_backend="hip_tuned",
+                                  wgrad_wino=True),
             "torch": Trainer(opt, domain, seed=1, conv_backend="torch", norm_backend=norm_backend)}
-    for be in ("wgrad_hip_tuned", "torch"):
+    for be in ("wgrad_hip_tuned", "wgrad_wino", "torch"):
         arms[be].model.load_state_dict(arms["wgrad_hip"].model.state_dict())
     z = torch.randn((1, 1, H, W), device=opt.device)
     ms, losses = {be: [] for be in arms}, {be: [] for be in arms}
@@ -206,7 +230,13 @@ def bench_wgrad_steps(opt, domain, rounds, norm_backend="torch"):
     spread = (max(ms["wgrad_hip"]) - min(ms["wgrad_hip"])) + (max(ms["wgrad_hip_tuned"]) - min(ms["wgrad_hip_tuned"]))
     routes = arms["wgrad_hip_tuned"].model.wgrad_routes((1, 1, H, W))
     gain = med["wgrad_hip"] - med["wgrad_hip_tuned"]
+    # the option against its yardstick, the hip_tuned arm of the same process
+    wino_gain = med["wgrad_hip_tuned"] - med["wgrad_wino"]
+    wino_spread = max(max(ms["wgrad_hip_tuned"]) - min(ms["wgrad_hip_tuned"]), max(ms["wgrad_wino"]) - min(ms["wgrad_wino"]))
     return {"size": [H, W], "B": 1, "t": 25, "conv_backend": "hip_tuned", "norm_backend": norm_backend,
+            "wino_over_torch": med["wgrad_wino"] / med["torch"], "wino_gain_ms": wino_gain, "wino_spread_ms": wino_spread,
+            "wino_gain_exceeds_spread": wino_gain > wino_spread,
+            "wino_routes": dict(arms["wgrad_wino"].model.wgrad_routes((1, 1, H, W))),
             "step_ms": {be: {"median_ms": med[be], "min_ms": min(v), "max_ms": max(v), "n": len(v)} for be, v in ms.items()},
             "off_over_torch": med["wgrad_hip"] / med["torch"], "on_over_torch": med["wgrad_hip_tuned"] / med["torch"],
             "gain_ms": gain, "spread_ms": spread, "gain_exceeds_spread": gain > spread,
@@ -263,11 +293,17 @@ def main():
                     help="the per-layer arms to run")
     ap.add_argument("--no-conv-steps", action="store_true", help="skip the Trainer.step table of the conv_backend arms")
     ap.add_argument("--no-steps", action="store_true", help="skip both Trainer.step tables")
+    ap.add_argument("--wino", action="store_true", help="the layers ipdm_conv2d_wgrad_wino_code takes alone: their weight-gradient arms "
+                    "and the wgrad Trainer.step table")
     ap.add_argument("--list", action="store_true", help="print the shapes and stop (needs no GPU)")
     a = ap.parse_args()
     import torch
     opt = production_opt("cuda:0")
     shapes = {d: conv_shapes(opt, d) for d in ("img", "proj")}
+    if a.wino:
+        from ipdm_pytorch_amd._lib import lib
+        a.ops, a.no_conv_steps = ["wgrad"], True
+        shapes = {d: {key: names for key, names in s.items() if lib().ipdm_conv2d_wgrad_wino_code(1, *key) == 3} for d, s in shapes.items()}
     if a.list:
         for d, s in shapes.items():
             for key, names in s.items():
@@ -291,6 +327,11 @@ def main():
                      pk("fprop"), hm("torch_fprop"), hm("hip_dgrad"), tm("dgrad"),
                      rec["tuned_codes"]["dgrad"], pk("dgrad"), hm("torch_dgrad"), hm("hip_wgrad"), tm("wgrad"), rec["tuned_codes"]["wgrad"],
                      hm("copy_floor"), hm("torch_wgrad")), flush=True)
+            if "wino_wgrad" in rec["ms"]:
+                w, t = rec["ms"]["wino_wgrad"], rec["ms"]["tuned_wgrad"]
+                print("    wgrad wino %.3f [%.3f .. %.3f] against tuned %.3f [%.3f .. %.3f] ms: %s; %d parts of %d tiles, rows %d"
+                      % (w["median_ms"], w["min_ms"], w["max_ms"], t["median_ms"], t["min_ms"], t["max_ms"], rec["wino_verdict"],
+                         rec["wgrad_wino_plan"]["parts"], rec["wgrad_wino_plan"]["chain"], rec["wgrad_wino_plan"]["rows"]), flush=True)
             torch.cuda.empty_cache()
         net = {"size": list(SIZES[d]), "distinct_shapes": len(layers), "layers": layers, "families": {}}
         for fam in sorted({r["family"] for r in layers}):
@@ -322,6 +363,17 @@ def main():
                                  streamed_ms_per_step=sum(r["ms"]["tuned_wgrad"]["median_ms"] * r["layers"] for r in rows if "copy_floor" in r["ms"]),
                                  tiled_flop_per_step=sum(r["flop_per_pass"] * r["layers"] for r in rows if r["tuned_codes"]["wgrad"] == 2),
                                  tiled_ms_per_step=sum(r["ms"]["tuned_wgrad"]["median_ms"] * r["layers"] for r in rows if r["tuned_codes"]["wgrad"] == 2))
+                    wrows = [r for r in rows if "wino_wgrad" in r["ms"]]
+                    if wrows:       # the layers the Winograd-domain entry takes: its arm against the tuned arm (the yardstick) and torch's
+                        per = lambda arm, stat: sum(r["ms"][arm][stat] * r["layers"] for r in wrows)       # noqa: E731
+                        f[op]["wino"] = {"layers": sum(r["layers"] for r in wrows), "wino_ms_per_step": per("wino_wgrad", "median_ms"),
+                                         "tuned_ms_per_step": per("tuned_wgrad", "median_ms"), "torch_ms_per_step": per("torch_wgrad", "median_ms"),
+                                         "wino_spread_ms": per("wino_wgrad", "max_ms") - per("wino_wgrad", "min_ms"),
+                                         "tuned_spread_ms": per("tuned_wgrad", "max_ms") - per("tuned_wgrad", "min_ms")}
+                        w = f[op]["wino"]
+                        w["gain_ms"] = w["tuned_ms_per_step"] - w["wino_ms_per_step"]
+                        w["gain_exceeds_spread"] = w["gain_ms"] > max(w["wino_spread_ms"], w["tuned_spread_ms"])
+                        w["loss_exceeds_spread"] = -w["gain_ms"] > max(w["wino_spread_ms"], w["tuned_spread_ms"])
                     if f[op]["tiled_ms_per_step"] > 0:
                         f[op]["tiled_TFLOPs"] = f[op]["tiled_flop_per_step"] / (f[op]["tiled_ms_per_step"] * 1e-3) / 1e12
             if "fprop" not in a.ops or "dgrad" not in a.ops:
@@ -345,8 +397,10 @@ def main():
             key = "trainer_step_wgrad" if nb == "torch" else "trainer_step_wgrad_norm_hip"
             s = res["networks"][d][key] = bench_wgrad_steps(opt, d, a.step_rounds, nb)
             print("%s Trainer.step (conv_backend=hip_tuned, norm_backend=%s): wgrad_backend hip %.1f ms, hip_tuned %.1f ms, torch arm %.1f ms; "
-                  "gain %.1f ms, spread %.1f ms" % (d, nb, s["step_ms"]["wgrad_hip"]["median_ms"], s["step_ms"]["wgrad_hip_tuned"]["median_ms"],
-                                                   s["step_ms"]["torch"]["median_ms"], s["gain_ms"], s["spread_ms"]), flush=True)
+                  "gain %.1f ms, spread %.1f ms; with wgrad_wino %.1f ms, gain over hip_tuned %.1f ms, spread %.1f ms"
+                  % (d, nb, s["step_ms"]["wgrad_hip"]["median_ms"], s["step_ms"]["wgrad_hip_tuned"]["median_ms"],
+                     s["step_ms"]["torch"]["median_ms"], s["gain_ms"], s["spread_ms"], s["step_ms"]["wgrad_wino"]["median_ms"],
+                     s["wino_gain_ms"], s["wino_spread_ms"]), flush=True)
             torch.cuda.empty_cache()
             if a.out:
                 dump(a.out + ".partial", res)
