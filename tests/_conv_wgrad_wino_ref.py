@@ -1,5 +1,6 @@
 """Shared by tests/test_conv_wgrad_wino_host.py and tests/test_gpu_conv_wgrad_wino.py: the shapes csrc/conv_wgrad_wino.hip is
-tested on with the plan properties each was chosen for, the plan query as a dict, and a numpy restatement of the kernel's
+tested on with the plan properties each was chosen for, the plan query as a dict, the launch class of a shape (the key of the
+coverage rule) with the shapes that run production's classes, and a numpy restatement of the kernel's
 arithmetic and summation order built from the plan fields alone.  Inputs and float64 / float32 references are those of
 tests/_conv_wgrad_ref (make_inputs, reference, exact_reference): the entry has the arguments of ipdm_conv2d_wgrad_tuned."""
 import ctypes
@@ -43,9 +44,70 @@ SHAPES = {
     (2, 48, 36, 4, 7, 3, 1): dict(rows=0, tiles=16, chain=16, parts=1, ragged_cin=16, ragged_cout=4, odd_w=True),
     (1, 64, 64, 1, 33, 3, 1): dict(rows=4, tiles=17, chain=32, odd_h=True, odd_w=True, last_stage_ragged=True),
 }
+FLAGS = ("crosses", "short last", "dead tiles", "odd H", "odd W", "ragged cin", "ragged cout")
+
+
+def _cls(form, parts, *flags, stages="3+"):
+    """A case chosen for a launch class a production step runs (launch_class below): its form, its parts key and the flags
+    that are set; every such case has parts of three stages or more."""
+    assert set(flags) <= set(FLAGS), flags
+    return dict(cls=(form, parts, stages) + tuple(f if f in flags else "-" for f in FLAGS))
+
+
+MANY = (1, 64, 64, 508, 510, 3, 1)
+# The launch classes of the production layers the rule takes (tools/conv_grad_bench.conv_shapes at B = 1 and 8), none of which the
+# shapes above run, each at the smallest shape that reaches it.  The all-sixteen form needs parts x cout groups x cin groups >= 256:
+# 8 x 8 groups at four parts, 11 x 12 at two; a ragged cin group as production's 144 -> 128 has it (16 channels) at 240 -> 256.
+# "crosses" at three samples whose tile count no part boundary divides.  Every case has fewer than 65536 tiles (the exactness
+# argument of the whole-number test).  tests/test_conv_wgrad_wino_host.py fails when a production class has no case here.
+PRODUCTION_SHAPES = {
+    # conv_wgrad_wino_kernel<false>: chains of 64 stages, blockIdx.x = part
+    (1, 352, 384, 65, 65, 3, 1): _cls("all sixteen", "2-3", "short last", "dead tiles", "odd H", "odd W"),
+    (4, 352, 384, 32, 64, 3, 1): _cls("all sixteen", "2-3", "crosses"),                   # two full parts of two samples each
+    (1, 256, 256, 128, 128, 3, 1): _cls("all sixteen", "4+"),                             # four full parts
+    (1, 256, 256, 130, 96, 3, 1): _cls("all sixteen", "4+", "short last"),                # 3120 tiles: a last part of three stages
+    (1, 256, 256, 100, 130, 3, 1): _cls("all sixteen", "4+", "short last", "dead tiles"),
+    (1, 240, 256, 100, 130, 3, 1): _cls("all sixteen", "4+", "short last", "dead tiles", "ragged cin"),
+    (3, 256, 256, 52, 80, 3, 1): _cls("all sixteen", "4+", "crosses", "short last"),      # 3 x 1040 tiles
+    (3, 240, 256, 52, 80, 3, 1): _cls("all sixteen", "4+", "crosses", "short last", "ragged cin"),
+    (3, 256, 256, 100, 46, 3, 1): _cls("all sixteen", "4+", "crosses", "short last", "dead tiles"),
+    (3, 256, 256, 51, 79, 3, 1): _cls("all sixteen", "4+", "crosses", "short last", "odd H", "odd W"),
+    (3, 256, 256, 77, 57, 3, 1): _cls("all sixteen", "4+", "crosses", "short last", "dead tiles", "odd H", "odd W"),
+    # conv_wgrad_wino_kernel<true>: the row form at 64 -> 64 channels
+    (1, 64, 64, 64, 64, 3, 1): _cls("row", "1"),                                          # one part of 64 stages
+    (1, 64, 64, 63, 29, 3, 1): _cls("row", "1", "odd H", "odd W"),                        # one part of 30 stages, none with dead tiles
+    (8, 64, 64, 32, 32, 3, 1): _cls("row", "2-3", "crosses"),                             # two full parts of four samples each
+    (1, 64, 64, 125, 57, 3, 1): _cls("row", "2-3", "short last", "dead tiles", "odd H", "odd W"),
+    (1, 64, 64, 256, 64, 3, 1): _cls("row", "4+"),
+    (1, 64, 64, 250, 114, 3, 1): _cls("row", "4+", "short last", "dead tiles"),           # seven parts
+    # many parts (64, the fold's loop and the workspace offsets of distant parts): at 64 -> 64 channels 64 parts are 256 workgroups,
+    # so the plan takes the all-sixteen form -- the row form ends at 63 parts by its own rule
+    MANY: dict(parts=64, **_cls("all sixteen", "4+", "short last", "dead tiles")),
+}
 # every other shape runs the row form
 for _props in SHAPES.values():
     _props.setdefault("rows", 4)
+# the classes of the shapes of SHAPES, in its order (none is a production class: no production part has two stages, one part with
+# dead tiles, or a float64 plan)
+_S = "float64 sum"
+for _props, _c in zip(SHAPES.values(), (
+        _cls("row", "1", "dead tiles", stages="2"),
+        _cls("row", "1", "crosses", "dead tiles", "ragged cin", "ragged cout"),
+        _cls("row", "1", "dead tiles", "odd H", "odd W"),
+        _cls("row", "1", "crosses"),
+        _cls("row", "1", "crosses", "dead tiles", "odd H", "odd W"),
+        _cls(_S, "1", "dead tiles", "odd H", "odd W", stages="1"),
+        _cls(_S, "1", "dead tiles", "odd H", "odd W", stages="1"),
+        _cls("row", "2-3"),
+        _cls("row", "1", "dead tiles", "odd H", "odd W", "ragged cin", "ragged cout"),
+        _cls("row", "2-3", "short last", "odd H", "odd W"),
+        _cls(_S, "1", "dead tiles", "odd H", "odd W", stages="1"),
+        _cls("all sixteen", "1", "crosses", "dead tiles", "odd W", "ragged cin", "ragged cout", stages="2"),
+        _cls("all sixteen", "1", "dead tiles", "odd H", "odd W", stages="2"),
+        _cls(_S, "1", "crosses", "odd W", "ragged cin", "ragged cout", stages="1"),
+        _cls("row", "1", "dead tiles", "odd H", "odd W", stages="2"))):
+    _props.update(_c)
+CASES = {**SHAPES, **PRODUCTION_SHAPES}
 
 
 def plan(geo):
@@ -66,8 +128,11 @@ def check_case(geo, props):
     assert p["code"] == 3 and (k, s) == (3, 1), (geo, p)
     tps = p["tiles_y"] * p["tiles_x"]
     tiles = B * tps
+    assert launch_class(geo) == props["cls"], (geo, launch_class(geo), p)          # every case names its launch class
     for key, want in props.items():
-        if key == "tiles":
+        if key == "cls":
+            continue
+        elif key == "tiles":
             assert tiles == want, (geo, key, p)
         elif key == "min_parts":
             assert p["parts"] >= want, (geo, key, p)
@@ -89,6 +154,40 @@ def check_case(geo, props):
         else:
             assert p[key] == want, (geo, key, p)
     return p
+
+
+FORM = {0: "float64 sum", 1: "all sixteen", 4: "row"}
+
+
+def launch_class(geo):
+    """The launch class of a shape, from plan(geo) alone (nothing of make_plan restated): what the main launch's workgroups do
+    that another shape's do not.  A tuple of
+      form        "all sixteen" (rows = 1: conv_wgrad_wino_kernel<false>, grid x = part, 80 KB of LDS, 64 accumulator registers),
+                  "row" (rows = 4: <true>, grid x = 4 part + window row) or "float64 sum" (rows = 0: one stage, no transform);
+      parts       "1", "2-3" or "4+": no fold, a short fold, a loop over distant workspace offsets;
+      stages      of a full part, "1" (the float64 form alone), "2" (the load-ahead loop issues one prefetch and leaves) or "3+"
+                  (its steady state: a stage whose loads were issued behind the stage before's LDS writes);
+      crosses     some part holds tiles of two samples (the sample index moves inside a chain);
+      short last  the last part walks fewer stages than a full one -- counted in stages, not tiles: the loop's trip count is what
+                  differs, and a last part short by less than a stage is the next key;
+      dead tiles  the last stage stages tiles past the last (tiles % 16);
+      odd H, odd W                 a ragged last tile row / column meeting the padding;
+      ragged cin, ragged cout      a last channel group of fewer than 32 channels.
+    Coarser than the plan in one place: the number of parts past four and of stages past three is not keyed (one loop, the
+    same instructions): the suite runs parts of 64 stages in most production cases and 64 parts once (MANY), not per class."""
+    p = plan(geo)
+    B, Cin, Cout, H, W, k, s = geo
+    assert p["code"] == 3 and p["stage"] == STAGE and p["chain"] % STAGE == 0, (geo, p)
+    tps = p["tiles_y"] * p["tiles_x"]
+    tiles, chain, parts = B * tps, p["chain"], p["parts"]
+    assert (parts - 1) * chain < tiles <= parts * chain, (geo, p)
+    stages = chain // STAGE
+    last_stages = -(-(tiles - (parts - 1) * chain) // STAGE)
+    crosses = any(t0 // tps != (min(t0 + chain, tiles) - 1) // tps for t0 in range(0, tiles, chain))
+    return (FORM[p["rows"]], "1" if parts == 1 else "2-3" if parts < 4 else "4+", "1" if stages == 1 else "2" if stages == 2 else "3+",
+            "crosses" if crosses else "-", "short last" if last_stages < stages else "-", "dead tiles" if tiles % STAGE else "-",
+            "odd H" if H % 2 else "-", "odd W" if W % 2 else "-",
+            "ragged cin" if Cin % p["cig"] else "-", "ragged cout" if Cout % p["cog"] else "-")
 
 
 def workspace_bytes(geo, p):
@@ -157,16 +256,18 @@ def restate(geo, x, dy, pairs=None):
     if pairs is None:
         pairs = [(co, ci) for co in range(Cout) for ci in range(Cin)]
     cos, cis = [co for co, _ in pairs], [ci for _, ci in pairs]
-    U, V = transforms(geo, x, dy, cos, cis)                  # [16, n, tiles] each, row n of both belonging to pair n
     idx = chain_index(geo, p)
     live = idx >= 0
     safe = np.where(live, idx, 0)
-    prod = (U * V).astype(np.float32)
-    terms = np.where(live[None, None], prod[:, :, safe], np.float32(0))           # [16, n, parts, chain]
-    parts = np.cumsum(terms, axis=3, dtype=np.float32)[..., -1].astype(np.float64)
-    M = np.zeros(parts.shape[:2], np.float64)
-    for q in range(p["parts"]):
-        M = M + parts[:, :, q]
+    M = np.zeros((16, len(pairs)), np.float64)
+    step = max(16, (1 << 21) // idx.size)                    # pairs at a time: [16, step, parts, chain] float32 stays near 128 MB
+    for n0 in range(0, len(pairs), step):
+        U, V = transforms(geo, x, dy, cos[n0:n0 + step], cis[n0:n0 + step])      # [16, n, tiles] each, row n of both belonging to pair n
+        prod = (U * V).astype(np.float32)
+        terms = np.where(live[None, None], prod[:, :, safe], np.float32(0))       # [16, n, parts, chain]
+        parts = np.cumsum(terms, axis=3, dtype=np.float32)[..., -1].astype(np.float64)
+        for q in range(p["parts"]):
+            M[:, n0:n0 + step] = M[:, n0:n0 + step] + parts[:, :, q]
     M = M.reshape(4, 4, len(pairs)).transpose(2, 0, 1)
     dw = np.einsum("ri,nij,sj->nrs", GT, M, GT).astype(np.float32)
     if len(pairs) == Cout * Cin:

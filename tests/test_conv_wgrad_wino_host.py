@@ -6,7 +6,6 @@ the parts added in float64, G^T . G in float64, one rounding) goes through the g
 arbiter (torch's float32 conv2d_weight on the CPU).  If the restatement passes with room, a miss on the device is the kernel's."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import torch
 from tests import _conv_wgrad_ref as wr
 from tests import _conv_wgrad_wino_ref as ww
 from tests._accuracy import M_ELEM, R_RMS, measure
+from tests.test_conv_wgrad_host import production_shapes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("ipdm_conv2d_wgrad_wino_code", "ipdm_conv2d_wgrad_wino_plan", "ipdm_conv2d_wgrad_wino_workspace_bytes",
@@ -108,16 +108,6 @@ def test_a_default_run_hands_trainer_no_wgrad_wino(tmp_path, monkeypatch):
         train.progressive_domain_trainer(opt, result_save_path=str(tmp_path / "out"))
 
 
-def production_shapes():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import conv_grad_bench as cg
-    finally:
-        sys.path.pop(0)
-    opt = cg.production_opt("cpu")
-    return [key for d in ("img", "proj") for key in cg.conv_shapes(opt, d)]
-
-
 def test_code_is_a_rule_of_the_layer():
     lib = _lib().lib()
     shapes = production_shapes()
@@ -153,7 +143,7 @@ def test_code_is_a_rule_of_the_layer():
 
 def test_plan_covers_every_tile_once_and_names_its_chain_and_workspace():
     lib = _lib().lib()
-    geos = list(ww.SHAPES) + [(B, Cin, Cout, H, W, k, s) for (Cin, Cout, H, W, k, s) in production_shapes() for B in (1, 8)
+    geos = list(ww.CASES) + [(B, Cin, Cout, H, W, k, s) for (Cin, Cout, H, W, k, s) in production_shapes() for B in (1, 8)
                               if rule(Cin, Cout, k, s)]
     longest, forms = 0, set()
     for geo in geos:
@@ -176,9 +166,45 @@ def test_plan_covers_every_tile_once_and_names_its_chain_and_workspace():
             assert idx.shape == (p["parts"], p["chain"]) and np.array_equal(np.sort(live), np.arange(tiles)), geo
     assert longest == ww.CHAIN_MAX and forms == {0, 1, 4}
     assert {ww.plan((1,) + tuple(k))["rows"] for k in production_shapes() if rule(k[0], k[1], k[4], k[5])} == {1, 4}       # production runs both
-    for geo, props in ww.SHAPES.items():
+    for geo, props in ww.CASES.items():
         ww.check_case(geo, props)
     assert ww.plan((1, 64, 64, 8, 8, 1, 1)) == dict.fromkeys(ww.FIELDS, 0)
+
+
+def uncovered(cases):
+    """The launch classes of the production layers the rule takes, at B = 1 and B = 8, that no shape of `cases` launches."""
+    have = {ww.launch_class(geo) for geo in cases}
+    want = {}
+    for key in production_shapes():
+        if rule(key[0], key[1], key[4], key[5]):
+            for B in (1, 8):
+                want.setdefault(ww.launch_class((B,) + tuple(key)), (B,) + tuple(key))
+    return {c: geo for c, geo in want.items() if c not in have}, want
+
+
+def test_every_production_launch_class_has_a_gpu_case():
+    """A launch class is ww.launch_class: (form, parts 1 / 2-3 / 4+, stages of a part 1 / 2 / 3+, a part crossing a sample, a
+    last part of fewer stages, dead tiles in the last stage, odd H, odd W, ragged cin group, ragged cout group), from the plan
+    query alone.  Every class a production layer launches at B = 1 or B = 8 is the class of a shape tests/test_gpu_conv_wgrad_wino.py
+    runs; a new form or part rule fails here until it has a case.  Before PRODUCTION_SHAPES: 17 classes, none of them run by the 15
+    shapes of SHAPES (11 of the 17 the all-sixteen form, which SHAPES runs at two stages and one part alone)."""
+    missing, want = uncovered(list(ww.CASES))
+    assert len(want) >= 17 and {c[0] for c in want} == {"all sixteen", "row"}
+    print("conv_wgrad_wino: %d production launch classes; %d run by SHAPES alone, %d by SHAPES and PRODUCTION_SHAPES"
+          % (len(want), len(want) - len(uncovered(list(ww.SHAPES))[0]), len(want) - len(missing)))
+    assert not missing, "production launch classes without a GPU case (class: first layer): %s" % missing
+    # every production case says what it is there for, and the class it claims is production's (MANY: that of the 28-part layers)
+    for geo, props in ww.PRODUCTION_SHAPES.items():
+        ww.check_case(geo, props)
+        assert props["cls"] in want, geo
+        assert geo[0] * ww.plan(geo)["tiles_y"] * ww.plan(geo)["tiles_x"] < 65536, geo       # the whole-number test's exactness
+    assert ww.plan(ww.MANY)["parts"] >= 64
+    # the list is tight: without either of two of its cases a class is uncovered, and it is named with its first layer
+    gone = ((3, 240, 256, 52, 80, 3, 1), (8, 64, 64, 32, 32, 3, 1))
+    assert all(g in ww.CASES for g in gone)
+    lost, _ = uncovered([g for g in ww.CASES if g not in gone])
+    assert lost == {ww.PRODUCTION_SHAPES[gone[0]]["cls"]: (8, 144, 128, 500, 228, 3, 1),
+                    ww.PRODUCTION_SHAPES[gone[1]]["cls"]: (8, 256, 256, 32, 32, 3, 1)}, lost
 
 
 def test_the_algebra_in_float64():
@@ -201,21 +227,29 @@ def test_the_algebra_in_float64():
 
 
 # a small layer restated whole, and the shape with the longest chain (three parts of 1024 tiles) on a fixed sample of 64 channel
-# pairs spread over both ranges (64 x 64 x 16 chains of 1024 are too many for numpy)
-YARDSTICK = [(2, 48, 36, 12, 10, 3, 1), ww.LONG]
-PAIRS = {ww.LONG: [((37 * i + 5) % 64, (53 * i + 7) % 64) for i in range(64)]}
+# pairs spread over both ranges (64 x 64 x 16 chains of 1024 are too many for numpy); the same for an all-sixteen production case
+# (four parts over three samples of an odd plane, the last short with dead tiles) and for the 64 parts of ww.MANY
+SIXTEEN = (3, 256, 256, 77, 57, 3, 1)
+YARDSTICK = [(2, 48, 36, 12, 10, 3, 1), ww.LONG, SIXTEEN, ww.MANY]
+PAIRS = {ww.LONG: [((37 * i + 5) % 64, (53 * i + 7) % 64) for i in range(64)],
+         SIXTEEN: [((37 * i + 5) % 256, (53 * i + 7) % 256) for i in range(64)],
+         ww.MANY: [((37 * i + 5) % 64, (53 * i + 7) % 64) for i in range(64)]}
 
 
 @pytest.mark.parametrize("geo", YARDSTICK, ids=["x".join(map(str, g)) for g in YARDSTICK])
 def test_restated_order_passes_the_gate_the_kernel_is_held_to(geo):
     """Measured (rms ratio, of 4 / elementwise ratio, of 8): 48 -> 36 at 2 x 12 x 10, one chain of 64 tiles: dW 1.38 / 1.068, db
     0.23 / 0.074; 64 -> 64 at 128 x 96, three chains of 1024 tiles -- the longest a plan may name -- on 64 channel pairs: dW 0.91 /
-    0.750, db 0.25 / 0.020.  An order under the gate on a real plane.  Not on every plane: Winograd is not componentwise stable, and
+    0.750, db 0.25 / 0.020; the all-sixteen form, 256 -> 256 at 3 x 77 x 57, four chains over three samples, 64 pairs: dW 0.44 /
+    0.215, db 0.20 / 0.023; 64 -> 64 at 508 x 510, 64 chains, 64 pairs: dW 0.29 / 0.171, db 0.14 / 0.003 (more parts, more of the
+    sum in float64).  An order under the gate on a real plane.  Not on every plane: Winograd is not componentwise stable, and
     on 64 -> 64 at 1 x 5 (three tiles) this order read 1.74 / 10.92 -- which is why a plan of one stage (rows = 0) is not
     transformed but summed in float64."""
     p = ww.plan(geo)
     if geo == ww.LONG:
         assert p["chain"] == ww.CHAIN_MAX and p["parts"] >= 3
+    if geo in (SIXTEEN, ww.MANY):
+        assert p["rows"] == 1 and p["chain"] == ww.CHAIN_MAX and p["parts"] == (4 if geo == SIXTEEN else 64)
     (x, dy), ref = wr.reference(geo, 9100 + YARDSTICK.index(geo))
     pairs = PAIRS.get(geo)
     dw, db = ww.restate(geo, x, dy, pairs=pairs)
