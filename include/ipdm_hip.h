@@ -46,7 +46,12 @@ int ipdm_abi_version(void);
  * gn_two_stage, unet_transpose, attn_no_zseq, attn_exact_f32, attn_no_presplit, attn_no_pipeline, conv_dbg, art_per_view: every weight form they choose between is packed, the workspace
  * need is re-queried per forward) may change under a live handle.  "gn_train_one_pass_max" (per call, 0 .. 16384, default 0 = the
  * plan's own rule) is the largest group, in floats per sample and group, that the training normalisations (ipdm_gn_act_*) run in
- * their one-pass form; no handle depends on it.  Returns IPDM_ERR_INVALID for an unknown name. */
+ * their one-pass form; no handle depends on it.  "attn_any_dim" (per call, 0 | 1 | 2, default 0) opens the inference attention to
+ * every head dim 1 .. 128 (csrc/attn_gen.hip, kernel family 3): 0 = head dims 64 and 32 only, every other one refused; 1 = 64 and 32
+ * keep their kernels bit for bit, every other d of 1 .. 128 runs on family 3; 2 = 64 and 32 run on family 3 as well (the A/B arm).
+ * ipdm_unet_create accepts a network whose head dims the value at that call accepts; ipdm_unet_workspace_bytes, the forward and the
+ * graph forward of such a handle must run under the same value (a forward under 0 fails with IPDM_ERR_UNSUPPORTED at its first
+ * attention layer), the rule attn_no_presplit lives by.  Returns IPDM_ERR_INVALID for an unknown name. */
 int ipdm_set_option(const char *name, int value);
 int ipdm_get_option(const char *name, int *value);
 
@@ -633,7 +638,7 @@ int ipdm_op_up_conv_chain(const float *d_x, int32_t C, int32_t B, int32_t Hs, in
                           const float *bB_host, int32_t CB, int32_t ksB, float *d_mid, float *d_out,
                           int32_t *used_up2, void *stream);
 /* AttentionBlock core (Model/model.py:148-153): d_qkv [B, heads*3*d, T] (per-head (q,k,v) chunks)
- * -> d_out [B, heads*d, T]. */
+ * -> d_out [B, heads*d, T].  d is 64 or 32; under option attn_any_dim every 1 <= d <= 128 (IPDM_ERR_UNSUPPORTED otherwise). */
 int ipdm_op_attention(const float *d_qkv, float *d_out, int32_t B, int32_t heads, int32_t d, int32_t T,
                       void *stream);
 
@@ -879,17 +884,20 @@ int32_t ipdm_conv_kernel_code(int32_t B, int32_t Cout, int32_t Cin, int32_t ksiz
 int32_t ipdm_conv_kernel_code_stats(int32_t B, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t H, int32_t W);
 /* Which attention kernel a launch with head dim d takes NOW: 0 = 4-wave kernel (d = 32, or IPDM_ATTN_LEGACY),
  * 1 = wave-specialised exact-f32 MFMA (d = 64 under the per-call option attn_exact_f32),
- * 2 = bf16 matrix pipe through an error-free 3-way split of every operand, f32 accumulate (attn_bx3.hip; the default for d = 64). */
+ * 2 = bf16 matrix pipe through an error-free 3-way split of every operand, f32 accumulate (attn_bx3.hip; the default for d = 64),
+ * 3 = the exact-f32 kernel for every head dim 1 .. 128 (attn_gen.hip; option attn_any_dim: every d but 64 and 32 under 1, those too
+ * under 2).  A head dim the current options refuse answers 0, as it always did: ipdm_attention_plan is the query that refuses. */
 int32_t ipdm_attention_kernel_code(int32_t d);
 /* Everything the attention dispatcher decides for a launch of this shape NOW (options read at the call, the key-slice scratch
  * buffer assumed present, as ipdm_op_attention and the UNet executor provide it); host code, answers without a device:
- *   out[0] kernel family: 0 = attention_kernel (4 waves), 1 = attention_ws_kernel (exact f32), 2 = attention_bx3_kernel
+ *   out[0] kernel family: 0 = attention_kernel (4 waves), 1 = attention_ws_kernel (exact f32), 2 = attention_bx3_kernel,
+ *          3 = attention_gen_kernel (any head dim, option attn_any_dim; out[1] = 1, out[3] is 0 or 1, Z <= 8 from (heads, d, T) alone)
  *   out[1] 32-query tiles per wave (1 or 2)
  *   out[2] key slices Z as launched (1 = none)
  *   out[3] 0 = no slices, 1 = split grid + combine pass, 2 = a workgroup walks all slices of its queries
  *   out[4] 64-key tiles per slice (the whole sequence when there are no slices)
  *   out[5] empty slices: those z with z * out[4] >= ceil(T / 64)
- * IPDM_ERR_UNSUPPORTED for a head dim other than 64 and 32.  Test aid: a test asserts the instantiation and form it covers. */
+ * IPDM_ERR_UNSUPPORTED for a head dim other than 64 and 32 (option attn_any_dim = 0), or outside 1 .. 128.  Test aid: a test asserts the instantiation and form it covers. */
 int ipdm_attention_plan(int32_t B, int32_t heads, int32_t d, int32_t T, int32_t out[6]);
 
 #ifdef __cplusplus

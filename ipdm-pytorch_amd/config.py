@@ -63,12 +63,17 @@ _FLAGS = [
     # under wgrad_backend="hip_tuned": the wide 3 x 3 stride-1 layers' weight gradient in the Winograd F(3 x 3, 2 x 2) domain
     # (csrc/conv_wgrad_wino.hip) where ipdm_conv2d_wgrad_wino_code takes the layer
     ("wgrad_wino", bool, False, None),
+    # which attention head dims (channels per head at the attention levels) the sampling networks run (no reference counterpart):
+    # "tuned" = 64 and 32, the head dims with kernels of their own, every other one refused; "any" = every head dim 1 .. 128
+    # (library option attn_any_dim, csrc/attn_gen.hip): what model_channels 48, 96 or 128 need in the default topologies
+    ("attn_head_dims", str, "tuned", None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 NORMAL_BACKENDS = ("sklearn", "hip")
 TRAIN_BACKENDS = dict(conv_backend=("hip", "hip_tuned", "torch"), norm_backend=("torch", "hip"), attn_backend=("torch", "hip"),
                       optim_backend=("torch", "hip"))
 WGRAD_BACKENDS = ("hip", "hip_tuned")
+ATTN_HEAD_DIMS = ("tuned", "any")
 
 
 def check_metrics_backend(value):
@@ -82,6 +87,13 @@ def check_normal_backend(value):
     """An unknown normal_backend is refused (argparse `choices` for the command line; this for a JSON overlay or update_opt)."""
     if value not in NORMAL_BACKENDS:
         raise ValueError("normal_backend must be one of %s, not %r" % (NORMAL_BACKENDS, value))
+    return value
+
+
+def check_attn_head_dims(value):
+    """An unknown attn_head_dims is refused (argparse `choices` for the command line; this for a JSON overlay or update_opt)."""
+    if value not in ATTN_HEAD_DIMS:
+        raise ValueError("attn_head_dims must be one of %s, not %r" % (ATTN_HEAD_DIMS, value))
     return value
 
 
@@ -138,6 +150,8 @@ def default_cfg(argv=None):
             kw["choices"] = TRAIN_BACKENDS[name]
         if name == "wgrad_backend":
             kw["choices"] = WGRAD_BACKENDS
+        if name == "attn_head_dims":
+            kw["choices"] = ATTN_HEAD_DIMS
         parser.add_argument("--" + name, **kw)
     argv = sys.argv[1:] if argv is None else argv
     opt = parser.parse_args(argv)
@@ -146,6 +160,7 @@ def default_cfg(argv=None):
         load_option(opt, opt.load_option_path, given)
     check_metrics_backend(opt.metrics_backend)
     check_normal_backend(opt.normal_backend)
+    check_attn_head_dims(opt.attn_head_dims)
     return opt
 
 

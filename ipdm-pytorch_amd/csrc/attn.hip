@@ -424,6 +424,34 @@ __global__ void __launch_bounds__(256) attention_combine_kernel(const float *__r
     }
 }
 
+// The same pass with the head dim at run time, for family 3 (attn_gen.hip: any d of 1 .. 128; gridDim.z = ceil(d / 16), the last
+// channel group is cut at d).  A kernel of its own, so that attention_combine_kernel<64> keeps its instructions (tools/isa_equal.py);
+// the recurrence is the one of attn_common.h in both.
+__global__ void __launch_bounds__(256) attention_combine_any_kernel(const float *__restrict__ part, float *__restrict__ out, int T, int Z, int ntiles, int d)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x, bh = blockIdx.y, c0 = blockIdx.z * 16;
+    if (t >= T) return;
+    const size_t slice = (size_t)gridDim.y * (d + 2) * T;
+    const float *p = part + (size_t)bh * (d + 2) * T;
+    const int tps = (ntiles + Z - 1) / Z;
+    SliceWeights w[8];
+    float M = -INFINITY, den = 0.0f;
+#pragma unroll
+    for (int z = 0; z < 8; ++z)
+        if (z < Z && z * tps < ntiles) {
+            w[z] = slice_weights(M, p[z * slice + (size_t)d * T + t]);
+            den = slice_fold(den, p[z * slice + (size_t)(d + 1) * T + t], w[z]);
+        }
+    const float inv = 1.0f / den;
+    for (int c = c0; c < min(c0 + 16, d); ++c) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int z = 0; z < 8; ++z)
+            if (z < Z && z * tps < ntiles) acc = slice_fold(acc, p[z * slice + (size_t)c * T + t], w[z]);
+        out[((size_t)bh * d + c) * T + t] = acc * inv;
+    }
+}
+
 // Key slices of the wave-specialised kernel.  Like the K split of the convolutions the count depends on the layer alone
 // (T and the head count, never the batch size), so that a slice of a batch stays bit-equal to the slice sampled alone:
 // only short sequences are split (at most 128 query workgroups per sample: T <= 4096 with 4 heads -- one slice alone fills
@@ -443,9 +471,9 @@ int attention_kv_split(int B, int heads, int d, int T)
 
 // Everything attention_launch decides about a launch, in one place: the launch below and the query ipdm_attention_plan both read it,
 // so a test can assert the kernel and the form a shape takes.  (What attention_bx3_launch decides on its own -- planes, pipelined
-// loop -- changes no bit and is not part of it.)  d is 64 or 32 here.
+// loop -- changes no bit and is not part of it.)  d is a head dim attention_head_dim_check accepted.
 struct AttnPlan {
-    int family;     // 0 = attention_kernel, 1 = attention_ws_kernel, 2 = attention_bx3_kernel
+    int family;     // 0 = attention_kernel, 1 = attention_ws_kernel, 2 = attention_bx3_kernel, 3 = attention_gen_kernel (attn_gen.hip)
     int qt;         // 32-query tiles per wave
     int Z;          // key slices as launched (1: none)
     int form;       // 0 = no slices, 1 = split grid + combine pass, 2 = in-workgroup walk
@@ -453,10 +481,40 @@ struct AttnPlan {
     int empty;      // slices z with z * tps >= ntiles
 };
 
+// Which head dims run at all, and which of them on family 3, under option attn_any_dim (read per call): 0 = 64 and 32 on their own
+// kernels, nothing else; 1 = every other d of 1 .. 128 on family 3; 2 = 64 and 32 there too.
+bool attention_on_gen(int d)
+{
+    const int any = opt(OPT_ATTN_ANY_DIM);
+    return any == 2 || (any == 1 && d != 64 && d != 32);
+}
+
+int attention_head_dim_check(int d)
+{
+    if (opt(OPT_ATTN_ANY_DIM) == 0) {
+        if (d != 64 && d != 32) { set_error("attention: head dim %d unsupported (kernel is specialised for 64 and 32)", d); return IPDM_ERR_UNSUPPORTED; }
+    } else if (d < 1 || d > ATTN_GEN_DMAX) {
+        set_error("attention: head dim %d unsupported (1 .. %d under attn_any_dim)", d, ATTN_GEN_DMAX);
+        return IPDM_ERR_UNSUPPORTED;
+    }
+    return IPDM_OK;
+}
+
 AttnPlan attention_plan(int B, int heads, int d, int T, bool have_scratch)
 {
     const int ntiles = cdiv(T, KV);
     AttnPlan p = {0, 1, 1, 0, ntiles, 0};
+    if (attention_on_gen(d)) {
+        // every head dim, exact f32 (its key tiles are 64 keys too): slices as a split grid + combine pass only
+        p.family = 3;
+        p.Z = have_scratch ? attention_gen_split(heads, d, T) : 1;
+        if (p.Z > 1) {
+            p.form = 1;
+            p.tps = cdiv(ntiles, p.Z);
+            p.empty = p.Z - cdiv(ntiles, p.tps);
+        }
+        return p;
+    }
     if (d != 64) return p;                                   // attention_kernel<32, 1>
     const long wg2 = (long)cdiv(T, 256) * B * heads, wg1 = (long)cdiv(T, 128) * B * heads;
     if (opt(OPT_ATTN_LEGACY) != 0) {
@@ -489,14 +547,14 @@ namespace ipdm {
 
 size_t attention_scratch_floats(int B, int heads, int d, int T)
 {
-    const int Z = attention_kv_split(B, heads, d, T);
+    const int Z = attention_on_gen(d) ? attention_gen_split(heads, d, T) : attention_kv_split(B, heads, d, T);
     return Z > 1 ? (size_t)Z * B * heads * (d + 2) * T : 0;
 }
 
 int attention_launch(const float *qkv, float *out, int B, int heads, int d, int T, hipStream_t st, float *scratch, float *planes)
 {
     IPDM_REQUIRE(qkv && out && B > 0 && heads > 0 && T > 0, "attention: bad argument");
-    if (d != 64 && d != 32) { set_error("attention: head dim %d unsupported (kernel is specialised for 64 and 32)", d); return IPDM_ERR_UNSUPPORTED; }
+    if (int rc = attention_head_dim_check(d)) return rc;
     // scale = 1/sqrt(sqrt(C/heads)) (Model/model.py:149); python double -> f32 scalar
     const float scale = (float)(1.0 / sqrt(sqrt((double)d)));
     const bool prof = prof_enabled();
@@ -504,7 +562,11 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
     const AttnPlan p = attention_plan(B, heads, d, T, scratch != nullptr);
     const int Z = p.Z;
     const bool seq = p.form == 2, q2 = p.qt == 2;
-    if (p.family == 2) {
+    if (p.family == 3) {
+        if (int rc = attention_gen_launch(qkv, out, B, heads, d, T, scale, Z, scratch, st)) return rc;
+        if (p.form == 1)
+            hipLaunchKernelGGL(attention_combine_any_kernel, dim3(cdiv(T, 256), B * heads, cdiv(d, 16)), dim3(256), 0, st, scratch, out, T, Z, cdiv(T, KV), d);
+    } else if (p.family == 2) {
         // bf16 matrix pipe, error-free 3-way split (attn_bx3.hip): the same key slices, and the same choice between the split grid +
         // combine pass and the in-workgroup walk, as the exact kernel below
         // the planes are used only where attention_planes_floats sized them (the same options, read here again: they are per call)
@@ -541,13 +603,14 @@ int attention_launch(const float *qkv, float *out, int B, int heads, int d, int 
 
 extern "C" int32_t ipdm_attention_kernel_code(int32_t d)
 {
-    return d == 64 ? attention_plan(1, 1, d, 1, true).family : 0;      // (the family looks at d and the options alone)
+    if (opt(OPT_ATTN_ANY_DIM) != 0 && (d < 1 || d > ATTN_GEN_DMAX)) return 0;
+    return d == 64 || attention_on_gen(d) ? attention_plan(1, 1, d, 1, true).family : 0;      // (the family looks at d and the options alone)
 }
 
 extern "C" int ipdm_attention_plan(int32_t B, int32_t heads, int32_t d, int32_t T, int32_t out[6])
 {
     IPDM_REQUIRE(out && B > 0 && heads > 0 && T > 0, "attention_plan: bad argument");
-    if (d != 64 && d != 32) { ipdm::set_error("attention: head dim %d unsupported (kernel is specialised for 64 and 32)", d); return IPDM_ERR_UNSUPPORTED; }
+    if (int rc = attention_head_dim_check(d)) return rc;
     const AttnPlan p = attention_plan(B, heads, d, T, true);
     out[0] = p.family; out[1] = p.qt; out[2] = p.Z; out[3] = p.form; out[4] = p.tps; out[5] = p.empty;
     return IPDM_OK;

@@ -621,7 +621,7 @@ namespace ipdm {
 
 size_t attention_planes_floats(int B, int heads, int d, int T)
 {
-    if (d != D || opt(OPT_ATTN_EXACT_F32) || opt(OPT_ATTN_LEGACY) || opt(OPT_ATTN_NO_PRESPLIT)) return 0;
+    if (d != D || opt(OPT_ATTN_EXACT_F32) || opt(OPT_ATTN_LEGACY) || opt(OPT_ATTN_NO_PRESPLIT) || opt(OPT_ATTN_ANY_DIM) == 2) return 0;      // (2: d = 64 runs on attn_gen.hip)
     return (size_t)B * heads * cdiv(T, KT) * TILE_CHUNKS * 4;
 }
 

@@ -44,6 +44,7 @@ const OptDef g_opt_def[OPT_COUNT] = {
     {"attn_no_presplit", 0, true},
     {"attn_no_pipeline", 0, true},
     {"gn_train_one_pass_max", 0, true, 0, 16384},      // (gn_grad.hip's one-pass backward keeps 2 N floats in LDS)
+    {"attn_any_dim", 0, true, 0, 2},
 };
 bool opt_value_ok(int i, int v)
 {
@@ -141,7 +142,8 @@ extern "C" const char *ipdm_last_error(void) { return ipdm::g_err; }
 extern "C" int ipdm_abi_version(void) { return IPDM_ABI_VERSION; }      // 2: ipdm_profile_end takes its array length; ipdm_conv_kernel_code  3: ipdm_profile_begin_classes  4: profile class 6 (IPDM_PROF_CLASSES 7); the split-bf16 switches are gone  5: profile class 7 (conv_wup2; IPDM_PROF_CLASSES 8), kernel code 11, option conv_no_wup2
 // (still 5: option attn_exact_f32 and attention kernel code 2 (attn_bx3.hip, the d = 64 default) changed no signature and no entry point;
 //  neither did options attn_no_presplit and attn_no_pipeline; the query ipdm_attention_plan is an additional entry, and so are
-//  the four ipdm_gn_act_* entries with their option gn_train_one_pass_max)
+//  the four ipdm_gn_act_* entries with their option gn_train_one_pass_max; option attn_any_dim and attention kernel code 3
+//  (attn_gen.hip) changed no signature and added no entry)
 
 extern "C" int ipdm_set_option(const char *name, int value)
 {

@@ -598,7 +598,11 @@ extern "C" int ipdm_unet_create(const ipdm_unet_cfg *cfg, const float *const *we
                 if ((r = make_norm(net, wm, p + ".norm", l.cin, ap.n))) break;
                 if ((r = make_conv(net, wm, p + ".qkv.weight", "", 3 * l.cin, l.cin, 1, ap.qkv))) break;
                 r = make_conv(net, wm, p + ".proj.weight", p + ".proj.bias", l.cin, l.cin, 1, ap.proj);
-                if (!r && l.cin / cfg->num_heads != 64 && l.cin / cfg->num_heads != 32) { set_error("unet_create: attention head dim %d unsupported (64 or 32)", l.cin / cfg->num_heads); r = IPDM_ERR_UNSUPPORTED; }
+                // the head dims the option attn_any_dim accepts NOW (per call: the workspace query and the forwards of this handle run
+                // under the same value, or attention_launch refuses the layer)
+                const int hd = l.cin / cfg->num_heads;
+                if (!r && opt(OPT_ATTN_ANY_DIM) == 0 && hd != 64 && hd != 32) { set_error("unet_create: attention head dim %d unsupported (64 or 32)", hd); r = IPDM_ERR_UNSUPPORTED; }
+                if (!r && opt(OPT_ATTN_ANY_DIM) != 0 && (hd < 1 || hd > ATTN_GEN_DMAX)) { set_error("unet_create: attention head dim %d unsupported (1 .. %d under attn_any_dim)", hd, ATTN_GEN_DMAX); r = IPDM_ERR_UNSUPPORTED; }
                 break;
             }
         }

@@ -183,6 +183,11 @@ size_t attention_planes_floats(int B, int heads, int d, int T);
 // split grid whose partial outputs go to scratch (the caller launches the combine pass)
 void attention_bx3_launch(const float *qkv, float *out, int B, int heads, int T, float scale, int Z, bool seq, float *scratch, float *planes,
                           hipStream_t st);
+// every head dim 1 .. 128 on the exact-f32 MFMA (attn_gen.hip, option attn_any_dim): Z key slices as a split grid whose partial
+// outputs go to scratch (the caller launches the combine pass), decided by attention_gen_split from (heads, d, T) alone
+constexpr int ATTN_GEN_DMAX = 128;
+int attention_gen_split(int heads, int d, int T);
+int attention_gen_launch(const float *qkv, float *out, int B, int heads, int d, int T, float scale, int Z, float *scratch, hipStream_t st);
 
 // time embedding: emb = Linear(SiLU(Linear(sinusoid(t)))) ; out = SiLU(emb)  (Model/model.py:14-32,218-222,105-108)
 int temb_launch(const float *freqs, int mc, int t, const float *w0, const float *b0, const float *w2, const float *b2,

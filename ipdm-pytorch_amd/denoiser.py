@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import cfg_load, check_normal_backend
+from .config import cfg_load, check_attn_head_dims, check_normal_backend
 from .diffusion import GaussianDiffusion, NoiseSource
 from .fbp import FBP, tensor_sharpen
 from .evaluate import EvaluationMixin
@@ -91,6 +91,8 @@ class progressive_domain_denoiser(EvaluationMixin):
     def update_opt(self, ultra_cfg=None):
         if ultra_cfg is not None and "normal_backend" in ultra_cfg:
             check_normal_backend(ultra_cfg["normal_backend"])
+        if ultra_cfg is not None and "attn_head_dims" in ultra_cfg:
+            check_attn_head_dims(ultra_cfg["attn_head_dims"])
         if ultra_cfg is not None:
             cfg_load(ultra_cfg, self.opt.__dict__)
         if "convertor" in ultra_cfg.keys():          # update_opt(None) raises AttributeError as the reference does
@@ -124,8 +126,11 @@ class progressive_domain_denoiser(EvaluationMixin):
     def _net_extras(self, domain):
         """num_res_blocks_<domain> / num_heads_<domain>, when opt has them (the reference has no such keys and always builds its
         constructor defaults, 2 and 4): the keys train.Trainer reads, so that a network trained with them loads here."""
-        return {k: getattr(self.opt, "%s_%s" % (k, domain)) for k in ("num_res_blocks", "num_heads")
-                if getattr(self.opt, "%s_%s" % (k, domain), None) is not None}
+        kw = {k: getattr(self.opt, "%s_%s" % (k, domain)) for k in ("num_res_blocks", "num_heads")
+              if getattr(self.opt, "%s_%s" % (k, domain), None) is not None}
+        # attn_head_dims ("tuned" when the key is absent): which attention head dims the network may have (UNetModel(head_dims=...))
+        kw["head_dims"] = check_attn_head_dims(getattr(self.opt, "attn_head_dims", "tuned"))
+        return kw
 
     def init_convertor(self, convertor):
         """Utils/train_test_utils.py:225-233.  The reference reads Recon/Simens_alut.txt / Simens_theta.txt from its

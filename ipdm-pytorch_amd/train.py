@@ -793,8 +793,10 @@ class Trainer:
     torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip")."""
 
     def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch",
-                 wgrad_backend="hip", wgrad_wino=False):
+                 wgrad_backend="hip", wgrad_wino=False, head_dims="tuned"):
         from .diffusion import GaussianDiffusion, NoiseSource
+        from .unet import check_head_dims
+        self.head_dims = check_head_dims(head_dims)                      # of sampling_model()'s UNetModel; training does not read it
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
         if optim_backend not in OPTIM_BACKENDS:
@@ -871,7 +873,7 @@ class Trainer:
 
     def sampling_model(self):
         """A UNetModel (the inference network of this library) loaded with the current weights, on the trainer's device."""
-        m = UNetModel(**self.model.unet_kwargs())
+        m = UNetModel(head_dims=self.head_dims, **self.model.unet_kwargs())
         m.load_state_dict(self.model.state_dict())
         return m.to(self.device)
 
@@ -932,7 +934,7 @@ class progressive_domain_trainer:
     Single process: the reference's train() has no gradient all-reduce either.  The reference has no EMA."""
 
     def __init__(self, opt, result_save_path=None):
-        from .config import check_train_backends, check_wgrad_backend, check_wgrad_wino
+        from .config import check_attn_head_dims, check_train_backends, check_wgrad_backend, check_wgrad_wino
         if opt.mode not in ("train_img", "train_proj"):
             raise ValueError("progressive_domain_trainer runs mode 'train_img' or 'train_proj', not %r (progressive_domain_denoiser "
                              "runs the test_* modes)" % (opt.mode,))
@@ -955,6 +957,10 @@ class progressive_domain_trainer:
             self.summer = SummaryWriter(log_dir=os.path.dirname(self.scalars_path))
         except Exception:                                          # noqa: BLE001 - tensorboard is optional: the jsonl file is the record
             self.summer = None
+        # attn_head_dims: a keyword only off its default, as wgrad_backend (the test leg's denoiser reads the key itself)
+        head_dims = check_attn_head_dims(getattr(opt, "attn_head_dims", "tuned"))
+        if head_dims != "tuned":
+            backends["head_dims"] = head_dims
         self.trainer = Trainer(opt, self.domain, seed=self.train_seed, **backends)
         self.train_model, self.optimizer = self.trainer.model, self.trainer.optimizer
         self.partial_timesteps = self.trainer.partial_timesteps

@@ -6,6 +6,7 @@ torch is used only to hold the parameters (so `state_dict()` / `load_state_dict(
 checkpoints work, Utils/loggerx.py:62-80) and to own the device workspace.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -14,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import UnetCfg, call, lib, ptr
+from .config import ATTN_HEAD_DIMS
 
 
 def make_cfg(in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, channel_mult,
@@ -29,6 +31,17 @@ def make_cfg(in_channels, model_channels, out_channels, num_res_blocks, attentio
     for i, a in enumerate(attention_resolutions):
         cfg.attention_resolutions[i] = int(a)
     return cfg
+
+
+HEAD_DIMS = ATTN_HEAD_DIMS       # (config.py: the option key attn_head_dims carries the same two values)
+
+
+def check_head_dims(value):
+    """"tuned": the attention head dims with kernels of their own (64 and 32), every other one refused; "any": every head dim
+    1 .. 128 (library option attn_any_dim, csrc/attn_gen.hip).  An unknown value is refused."""
+    if value not in HEAD_DIMS:
+        raise ValueError("head_dims must be one of %s, not %r" % (HEAD_DIMS, value))
+    return value
 
 
 def param_shapes(cfg):
@@ -52,7 +65,8 @@ class UNetModel:
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2,
                  attention_resolutions=(8, 16), dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True,
-                 num_heads=4, pre_downsample_times=1):
+                 num_heads=4, pre_downsample_times=1, head_dims="tuned"):
+        self.head_dims = check_head_dims(head_dims)
         if dropout:
             raise NotImplementedError("dropout is never instantiated on the sampling path (Model/model.py:198)")
         if not conv_resample:
@@ -109,6 +123,13 @@ class UNetModel:
         return self
 
     # ---- native handle
+    def _head_dims_scope(self):
+        """head_dims="any": the create call, the workspace query and both forwards run under attn_any_dim >= 1 (the library reads
+        the option per call and wants the same value in all four); "tuned" leaves the process-wide value alone."""
+        if self.head_dims != "any":
+            return contextlib.nullcontext()
+        return _lib.option("attn_any_dim", max(1, _lib.get_option("attn_any_dim")))
+
     def _destroy(self):
         if self._handle is not None:
             lib().ipdm_unet_destroy(self._handle)
@@ -131,13 +152,14 @@ class UNetModel:
                 keep.append(a)
                 arr[i] = a.ctypes.data
             h = C.c_void_p()
-            with torch.cuda.device(self._device):
+            with torch.cuda.device(self._device), self._head_dims_scope():
                 call("ipdm_unet_create", C.byref(self.cfg), arr, len(keep), C.byref(h))
             self._handle = h
         return self._handle
 
     def workspace(self, B, H, W):
-        need = lib().ipdm_unet_workspace_bytes(self._ensure(), B, H, W)
+        with self._head_dims_scope():
+            need = lib().ipdm_unet_workspace_bytes(self._ensure(), B, H, W)
         if self._ws is None or self._ws.numel() < need or self._ws.device != self._device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self._device)
         return self._ws
@@ -146,7 +168,7 @@ class UNetModel:
         """x [B,Cin,H,W] f32 cuda contiguous, integer timestep t -> out [B,Cout,H,W]."""
         B, _, H, W = x.shape
         ws = self.workspace(B, H, W)
-        with torch.cuda.device(self._device):
+        with torch.cuda.device(self._device), self._head_dims_scope():
             call("ipdm_unet_forward", self._ensure(), ptr(x), int(t), ptr(out), B, H, W, ptr(ws), ws.numel(),
                  _lib.current_stream())
         return out
@@ -195,7 +217,7 @@ class UNetModel:
             self._gbuf = {key: buf}              # one shape at a time: the buffers (and the graphs keyed on them) are large
         gx, gout = buf
         ws = self.workspace(B, H, W)
-        with torch.cuda.device(self._device):
+        with torch.cuda.device(self._device), self._head_dims_scope():
             gx.copy_(x)
             call("ipdm_unet_forward_graph", self._ensure(), ptr(gx), int(t), ptr(gout), B, H, W, ptr(ws), ws.numel(),
                  _lib.current_stream())
