@@ -587,10 +587,15 @@ int ipdm_gn_act_bgrad(const float *d_x, const float *d_shift, const float *d_gam
  * bits for every B.
  *
  * Any 1 <= d <= 64 (zero-padded in LDS and registers to the width ipdm_attn_train_plan reports, never read from the
- * neighbouring rows of qkv) and any T >= 1 (ragged tiles are masked and never stored; rows need no alignment).  Bad arguments
- * -- a NULL pointer (d_lse of ipdm_attn_fprop excepted), a size < 1 -- return IPDM_ERR_INVALID, d > 64 IPDM_ERR_UNSUPPORTED, a
- * short workspace (ipdm_attn_bgrad; the forward uses none) IPDM_ERR_WORKSPACE, all before any launch, with the text in
- * ipdm_last_error.  IPDM_ABI_VERSION stays 5: additive entries, detected by symbol. */
+ * neighbouring rows of qkv) and any T >= 1 (ragged tiles are masked and never stored; rows need no alignment).  Under the
+ * library option attn_train_any_dim = 1 (per call, default 0; IPDM_ATTN_TRAIN_ANY_DIM) the four entries take any 1 <= d <= 128:
+ * the width is 32 ceil(d / 32) -- 32 and 64 are the kernels and bits of the default, 96 and 128 their four-wave siblings, whose
+ * workgroup owns 128 queries (keys) where the narrow one owns 64, the streamed tile staying 64; everything stated above
+ * holds for them, and the workspace stays B*heads*T floats.  At width 128 the dK / dV launch is two (dV, then dK).  Bad
+ * arguments -- a NULL pointer (d_lse of ipdm_attn_fprop excepted), a size < 1 -- return IPDM_ERR_INVALID, d > 64 (d > 128
+ * under the option) IPDM_ERR_UNSUPPORTED, a short workspace (ipdm_attn_bgrad; the forward uses none) IPDM_ERR_WORKSPACE, all
+ * before any launch, with the text in ipdm_last_error.  IPDM_ABI_VERSION stays 5: additive entries, detected by symbol; the
+ * option is one more table entry. */
 /* bytes of d_ws for the two calls of one layer; 0 for arguments a call refuses */
 size_t ipdm_attn_train_workspace_bytes(int32_t B, int32_t heads, int32_t d, int32_t T);
 /* host-only plan query: out = {padded head width, queries (keys) a workgroup owns, keys (queries) per streamed tile, streamed

@@ -65,7 +65,9 @@ _FLAGS = [
     ("wgrad_wino", bool, False, None),
     # which attention head dims (channels per head at the attention levels) the sampling networks run (no reference counterpart):
     # "tuned" = 64 and 32, the head dims with kernels of their own, every other one refused; "any" = every head dim 1 .. 128
-    # (library option attn_any_dim, csrc/attn_gen.hip): what model_channels 48, 96 or 128 need in the default topologies
+    # (library option attn_any_dim, csrc/attn_gen.hip): what model_channels 48, 96 or 128 need in the default topologies.  In a
+    # train_* mode with attn_backend="hip" the same key reaches the training attention core: "tuned" = head dims 1 .. 64, "any" =
+    # 1 .. 128 (library option attn_train_any_dim, csrc/attn_grad.hip); attn_backend="torch" takes every head dim either way
     ("attn_head_dims", str, "tuned", None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")

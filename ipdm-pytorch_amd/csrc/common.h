@@ -57,6 +57,7 @@ enum Opt {
     OPT_ATTN_NO_PIPELINE,    // attn_bx3 on its first loop (S, softmax + split, P.V one behind the other) instead of the pipelined one (per call: the bit oracle)
     OPT_GN_TRAIN_ONE_PASS_MAX,   // the largest group (floats per sample and group) the one-pass form of gn_grad.hip takes; 0 = the plan's own rule (per call)
     OPT_ATTN_ANY_DIM,        // opt-in: inference attention for every head dim 1 .. 128 (attn_gen.hip): 1 = every d but 64 and 32, 2 = those too (per call)
+    OPT_ATTN_TRAIN_ANY_DIM,  // opt-in: training attention (attn_grad.hip) for every head dim 1 .. 128: 65 .. 128 on the four-wave kernels of width 96 / 128 (per call)
     OPT_COUNT
 };
 int opt(Opt o);

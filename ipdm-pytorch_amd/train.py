@@ -34,6 +34,7 @@ A missing kernel is an error: conv_backend="hip" never falls back to F.conv2d, n
 attn_backend="hip" never to the einsums, optim_backend="hip" never to torch.optim.Adam.  The reference has no EMA and no
 gradient all-reduce in train(); neither is here."""
 import collections
+import contextlib
 import copy
 import ctypes
 import json
@@ -49,7 +50,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import IpdmError, call, lib, ptr
-from .unet import UNetModel, make_cfg, param_shapes
+from .unet import UNetModel, check_head_dims, make_cfg, param_shapes
 
 CONV_BACKENDS = ("hip", "hip_tuned", "torch")
 NORM_BACKENDS = ("torch", "hip")
@@ -260,9 +261,15 @@ def group_norm_act(x, gamma, beta, groups, shift=None, act=True, eps=1e-5):
 
 
 # ------------------------------------------------------------------------------------------------ the attention core under autograd
+def _attn_scope(any_dim):
+    """The library option a call of attention(head_dims="any") runs under: attn_train_any_dim = 1 for the call alone (the value
+    before it stands again afterwards); head_dims="tuned" changes nothing."""
+    return _lib.option("attn_train_any_dim", 1) if any_dim else contextlib.nullcontext()
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, grad_mode):
+    def forward(ctx, qkv, heads, grad_mode, any_dim):
         if not (qkv.is_cuda and qkv.dtype == torch.float32):
             raise IpdmError("attention runs on float32 GPU tensors only (no CPU fallback); got %s %s" % (qkv.device, qkv.dtype))
         if qkv.dim() not in (3, 4) or heads < 1 or qkv.shape[1] % (3 * heads):
@@ -274,37 +281,41 @@ class _Attention(torch.autograd.Function):
         out = torch.empty((B, heads * d) + tuple(qkv.shape[2:]), dtype=torch.float32, device=qkv.device)
         keep = grad_mode and ctx.needs_input_grad[0]           # else no backward will follow: the statistics are not written
         lse = torch.empty((B, heads, geo[3]), dtype=torch.float32, device=qkv.device) if keep else None
-        with torch.cuda.device(qkv.device):
+        with torch.cuda.device(qkv.device), _attn_scope(any_dim):
             call("ipdm_attn_fprop", ptr(qkv), ptr(out), ptr(lse), *geo, None, 0, _lib.current_stream())
         if keep:
             ctx.save_for_backward(qkv, out, lse)
-        ctx.geo = geo
+        ctx.geo, ctx.any_dim = geo, any_dim          # (the backward runs later, under autograd: it sets the option again)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         if not ctx.needs_input_grad[0]:
-            return None, None, None
+            return None, None, None, None
         qkv, out, lse = ctx.saved_tensors
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
-        with torch.cuda.device(qkv.device):
+        with torch.cuda.device(qkv.device), _attn_scope(ctx.any_dim):
             need = lib().ipdm_attn_train_workspace_bytes(*ctx.geo)
             if need == 0:
                 raise IpdmError("attention: %s" % lib().ipdm_last_error().decode())
             ws = _scratch(need, qkv.device)
             call("ipdm_attn_bgrad", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), *ctx.geo, ptr(ws), ws.numel(),
                  _lib.current_stream())
-        return dqkv, None, None
+        return dqkv, None, None, None
 
 
-def attention(qkv, heads):
+def attention(qkv, heads, head_dims="tuned"):
     """The attention core of AttentionBlock: qkv [B, 3C, T] or [B, 3C, H, W], per head the rows (q: d, k: d, v: d), ->
     softmax_s((s q)^T (s k)) v with s = d^(-1/4), [B, C, T] or [B, C, H, W]; differentiable once: one fused forward and a
     three-launch backward on torch's current stream (csrc/attn_grad.hip).  Saved for the backward: qkv, the output (the tensor
-    the proj convolution keeps as well) and log-sum-exp per (sample, head, query) -- no [T, T] tensor exists."""
-    return _Attention.apply(qkv, int(heads), torch.is_grad_enabled())          # (inside forward() the grad mode is always off)
+    the proj convolution keeps as well) and log-sum-exp per (sample, head, query) -- no [T, T] tensor exists.
+    head_dims="tuned": head dims 1 .. 64, a larger one is an IpdmError; "any": every head dim 1 .. 128 -- the forward, the
+    workspace query and the backward run under the library option attn_train_any_dim, set for those calls alone (65 .. 128: the
+    four-wave kernels of width 96 and 128; up to 64 the option changes no bit)."""
+    any_dim = check_head_dims(head_dims) == "any"
+    return _Attention.apply(qkv, int(heads), torch.is_grad_enabled(), any_dim)          # (inside forward() the grad mode is always off)
 
 
 # ------------------------------------------------------------------------------------------------ the network
@@ -390,10 +401,11 @@ class ResBlock(nn.Module):
 class AttnBlock(nn.Module):
     """AttentionBlock, Model/model.py:135-155: qkv is chunked per head as (head, {q, k, v}, d)."""
 
-    def __init__(self, channels, heads, backend, norm_backend="torch", attn_backend="torch"):
+    def __init__(self, channels, heads, backend, norm_backend="torch", attn_backend="torch", head_dims="tuned"):
         super().__init__()
         assert channels % heads == 0
         self.heads, self.norm_backend, self.attn_backend = heads, norm_backend, attn_backend
+        self.head_dims = check_head_dims(head_dims)              # of attention(); the torch arm takes every head dim as it is
         self.norm = _norm(channels)
         self.qkv = Conv(channels, 3 * channels, 1, bias=False, backend=backend)
         self.proj = Conv(channels, channels, 1, backend=backend)
@@ -406,7 +418,7 @@ class AttnBlock(nn.Module):
         else:
             h = self.norm(x)
         if self.attn_backend == "hip":              # the qkv convolution's output as it is: no chunk, no scaled copies, no [T, T]
-            return self.proj(attention(self.qkv(h), self.heads)) + x
+            return self.proj(attention(self.qkv(h), self.heads, self.head_dims)) + x
         q, k, v = self.qkv(h).reshape(B * self.heads, -1, H * W).chunk(3, dim=1)
         scale = 1.0 / math.sqrt(math.sqrt(C // self.heads))
         p = torch.einsum("bct,bcs->bts", q * scale, k * scale).softmax(dim=-1)
@@ -451,11 +463,12 @@ class TrainUNet(nn.Module):
     and shapes of unet.param_shapes(cfg) (the reference's state_dict() layout), forward(x, t) with t an int or a [B] tensor of
     per-sample timesteps.  norm_backend="hip" runs every GroupNorm (+SiLU) through group_norm_act; the nn.GroupNorm modules stay
     where they are as the parameter holders, so the keys do not depend on it.  attn_backend="hip" runs every attention core
-    through attention; it has no parameters of its own."""
+    through attention; it has no parameters of its own.  head_dims="any" (with attn_backend="hip") lets those cores have every
+    head dim 1 .. 128 (attention(head_dims="any")) where "tuned" stops at 64; keys and shapes do not depend on it."""
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(8, 16),
                  dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True, num_heads=4, pre_downsample_times=1,
-                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip", wgrad_wino=False):
+                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip", wgrad_wino=False, head_dims="tuned"):
         super().__init__()
         if dropout:
             raise NotImplementedError("dropout is never instantiated by the reference harness (Model/model.py:198)")
@@ -480,6 +493,7 @@ class TrainUNet(nn.Module):
         self.conv_backend = be = conv_backend
         self.norm_backend = nb = norm_backend
         self.attn_backend = ab = attn_backend
+        self.head_dims = hd = check_head_dims(head_dims)         # handed to every AttnBlock; no effect with attn_backend="torch"
         mc, ted = model_channels, model_channels * 4
         self.time_embed = nn.Sequential(nn.Linear(mc, ted), nn.SiLU(), nn.Linear(ted, ted))
         ch = int(self.channel_mult[0] * mc)
@@ -490,21 +504,21 @@ class TrainUNet(nn.Module):
                 layers = [ResBlock(ch, int(mult * mc), ted, be, nb)]
                 ch = int(mult * mc)
                 if ds in self.attention_resolutions:
-                    layers.append(AttnBlock(ch, num_heads, be, nb, ab))
+                    layers.append(AttnBlock(ch, num_heads, be, nb, ab, hd))
                 self.down_blocks.append(_Stage(layers))
                 chans.append(ch)
             if level != len(mults) - 1:
                 self.down_blocks.append(_Stage([Down(ch, be)]))
                 chans.append(ch)
                 ds *= 2
-        self.middle_block = _Stage([ResBlock(ch, ch, ted, be, nb), AttnBlock(ch, num_heads, be, nb, ab), ResBlock(ch, ch, ted, be, nb)])
+        self.middle_block = _Stage([ResBlock(ch, ch, ted, be, nb), AttnBlock(ch, num_heads, be, nb, ab, hd), ResBlock(ch, ch, ted, be, nb)])
         self.up_blocks = nn.ModuleList()
         for level, mult in list(enumerate(mults))[::-1]:
             for i in range(num_res_blocks + 1):
                 layers = [ResBlock(ch + chans.pop(), int(mc * mult), ted, be, nb)]
                 ch = int(mc * mult)
                 if ds in self.attention_resolutions:
-                    layers.append(AttnBlock(ch, num_heads, be, nb, ab))
+                    layers.append(AttnBlock(ch, num_heads, be, nb, ab, hd))
                 if level and i == num_res_blocks:
                     layers.append(Up(ch, be))
                     ds //= 2
@@ -795,8 +809,7 @@ class Trainer:
     def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch",
                  wgrad_backend="hip", wgrad_wino=False, head_dims="tuned"):
         from .diffusion import GaussianDiffusion, NoiseSource
-        from .unet import check_head_dims
-        self.head_dims = check_head_dims(head_dims)                      # of sampling_model()'s UNetModel; training does not read it
+        self.head_dims = check_head_dims(head_dims)          # of the TrainUNet's attention cores and of sampling_model()'s UNetModel
         if domain not in ("img", "proj"):
             raise ValueError("domain must be 'img' or 'proj', not %r" % (domain,))
         if optim_backend not in OPTIM_BACKENDS:
@@ -810,7 +823,7 @@ class Trainer:
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
             self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend,
-                                   wgrad_backend=wgrad_backend, wgrad_wino=wgrad_wino, **kw).to(self.device)
+                                   wgrad_backend=wgrad_backend, wgrad_wino=wgrad_wino, head_dims=self.head_dims, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
         adam = HipAdam if optim_backend == "hip" else torch.optim.Adam

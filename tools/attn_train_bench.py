@@ -18,6 +18,13 @@ Every part (the layer measurements, the steps of each network) runs as a child p
 first part that fails or runs out of time ends the run.
 
     python tools/attn_train_bench.py --out profiles/r23_attn_train_bench.json
+
+--head-dim D [D ...] (default 64: the record above, unchanged) measures the layer part alone at other head dims -- heads 4, the
+two production T at B = 1 and B = 8 -- with the hip arm on train.attention(head_dims="any") above 64 (the four-wave kernels of
+width 96 and 128).  Each cell carries a verdict for forward + backward: "win" or "loss" of the hip arm only where the medians
+differ by more than the sum of both arms' min-max spreads, else "tie".
+
+    python tools/attn_train_bench.py --head-dim 96 128 --out profiles/r36_attn_train_wide_bench.json
 """
 import argparse
 import json
@@ -57,9 +64,19 @@ def torch_core(qkv, heads):
     return torch.einsum("bts,bcs->bct", p, v).reshape(B, -1, T)
 
 
-def bench_layer(T, B, rounds, reps):
+def verdict(hip, torch_arm):
+    """The hip arm against the torch arm: a difference counts only beyond the sum of both arms' min-max spreads."""
+    spread = (hip["max_ms"] - hip["min_ms"]) + (torch_arm["max_ms"] - torch_arm["min_ms"])
+    if abs(hip["median_ms"] - torch_arm["median_ms"]) <= spread:
+        return "tie"
+    return "win" if hip["median_ms"] < torch_arm["median_ms"] else "loss"
+
+
+def bench_layer(T, B, rounds, reps, D=D):
     import torch
-    from ipdm_pytorch_amd.train import attention
+    from ipdm_pytorch_amd import train
+    head_dims = "any" if D > 64 else "tuned"
+    attention = lambda qkv, heads: train.attention(qkv, heads, head_dims=head_dims)      # noqa: E731
     dev = "cuda:0"
     qkv = (1.3 * torch.randn((B, HEADS * 3 * D, T), device=dev)).requires_grad_(True)
     dO = torch.randn((B, HEADS * D, T), device=dev)
@@ -97,6 +114,8 @@ def bench_layer(T, B, rounds, reps):
     return {"shape": [B, HEADS, D, T], "ms": out, "peak_MiB_above_the_inputs": peak,
             "probability_matrix_MiB": B * HEADS * T * T * 4 / 2 ** 20,
             "fwd_hip_over_torch": med("fwd/hip") / med("fwd/torch"), "fwd_bwd_hip_over_torch": med("fwd+bwd/hip") / med("fwd+bwd/torch"),
+            "fwd_verdict_hip": verdict(out["fwd/hip"], out["fwd/torch"]),
+            "fwd_bwd_verdict_hip": verdict(out["fwd+bwd/hip"], out["fwd+bwd/torch"]),
             "fwd_hip_TFLOPs": flops / (med("fwd/hip") * 1e-3) / 1e12,
             "fwd_bwd_hip_TFLOPs": 4.5 * flops / (med("fwd+bwd/hip") * 1e-3) / 1e12}
 
@@ -135,16 +154,18 @@ def run_part(part, a):
         sys.exit("attn_train_bench needs a GPU: a CPU run measures nothing")
     if part == "layers":
         rec = {"device": torch.cuda.get_device_name(0), "layers": []}
-        shapes = [(n, T, B) for n, T in LAYERS.items() for B in BATCHES] + [(n, T, 1) for n, T in WIDE_LAYERS.items()]
+        d = a.head_dim[0]
+        shapes = [(n, T, B) for n, T in LAYERS.items() for B in BATCHES] + ([(n, T, 1) for n, T in WIDE_LAYERS.items()] if d == D else [])
         for net, T, B in shapes:
-            row = bench_layer(T, B, a.rounds, a.reps)
+            row = bench_layer(T, B, a.rounds, a.reps, d)
             row["network"] = net
             rec["layers"].append(row)
             m = row["ms"]
-            print("%s B=%d T=%d  fwd torch %.3f ms hip %.3f (x%.2f)   fwd+bwd torch %.3f hip %.3f (x%.2f)   peak MiB torch %.0f hip %.0f"
-                  % (net, B, T, m["fwd/torch"]["median_ms"], m["fwd/hip"]["median_ms"], row["fwd_hip_over_torch"],
+            print("%s d=%d B=%d T=%d  fwd torch %.3f ms hip %.3f (x%.2f)   fwd+bwd torch %.3f hip %.3f (x%.2f, %s)   peak MiB torch %.0f hip %.0f"
+                  % (net, d, B, T, m["fwd/torch"]["median_ms"], m["fwd/hip"]["median_ms"], row["fwd_hip_over_torch"],
                      m["fwd+bwd/torch"]["median_ms"], m["fwd+bwd/hip"]["median_ms"], row["fwd_bwd_hip_over_torch"],
-                     row["peak_MiB_above_the_inputs"]["torch"], row["peak_MiB_above_the_inputs"]["hip"]), flush=True)
+                     row["fwd_bwd_verdict_hip"], row["peak_MiB_above_the_inputs"]["torch"], row["peak_MiB_above_the_inputs"]["hip"]),
+                  flush=True)
             torch.cuda.empty_cache()
     else:
         domain = part.split("-")[1]
@@ -161,14 +182,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=3, help="back-to-back passes per timed interval")
     ap.add_argument("--step-rounds", type=int, default=3)
+    ap.add_argument("--head-dim", type=int, nargs="+", default=[D], help="head dims of the layer part (default 64: the whole record; "
+                    "any other list: the layer part alone per head dim, 65 .. 128 on train.attention(head_dims=\"any\"))")
     ap.add_argument("--part", choices=[p for p, _ in PARTS], default=None, help="run one part in this process (the driver's children)")
     a = ap.parse_args()
     if a.part:
         return run_part(a.part, a)
-    res = {"rounds": a.rounds, "reps": a.reps, "step_rounds": a.step_rounds, "heads": HEADS, "d": D, "trainer_step": {}}
-    for part, limit in PARTS:
+    if any(not 1 <= d <= 128 for d in a.head_dim):
+        sys.exit("attn_train_bench: --head-dim takes head dims 1 .. 128")
+    whole = a.head_dim == [D]
+    res = {"rounds": a.rounds, "reps": a.reps, "step_rounds": a.step_rounds, "heads": HEADS}
+    res.update({"d": D, "trainer_step": {}} if whole else {"layers_by_head_dim": {}})
+    for part, limit, d in (tuple((p, l, D) for p, l in PARTS) if whole else tuple(("layers", PARTS[0][1], d) for d in a.head_dim)):
         cmd = [sys.executable, os.path.abspath(__file__), "--part", part, "--rounds", str(a.rounds), "--reps", str(a.reps),
-               "--step-rounds", str(a.step_rounds)]
+               "--step-rounds", str(a.step_rounds), "--head-dim", str(d)]
         try:
             done = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=limit)
         except subprocess.TimeoutExpired:
@@ -177,7 +204,10 @@ def main():
         if done.returncode != 0:
             sys.exit("attn_train_bench: part %s ended with status %d; nothing more is started" % (part, done.returncode))
         rec = json.loads([line for line in done.stdout.splitlines() if line.startswith("RECORD ")][-1][len("RECORD "):])
-        if part == "layers":
+        if not whole:
+            res["device"] = rec["device"]
+            res["layers_by_head_dim"][str(d)] = rec["layers"]
+        elif part == "layers":
             res.update(rec)
         else:
             res["trainer_step"][part.split("-")[1]] = rec
