@@ -497,9 +497,23 @@ int ipdm_conv2d_wgrad_wino(const float *d_x, const float *d_dy, float *d_dw, flo
  * non-zero.  Everything else stays on ipdm_conv2d_fprop / ipdm_conv2d_dgrad.  The entries reuse the dispatcher, so row b of a batch
  * has the bits of a call on row b alone, two calls give the same bits, the result of role 0 has the bits of ipdm_op_conv2d on the
  * same weights, and the options conv_no_wino, wino_v1, wino2_min_tiles, pw_force, conv_no_splitk and conv_bf16x3 act as in inference.
- * No allocation, no synchronisation: asynchronous on `stream`. */
+ * No allocation, no synchronisation: asynchronous on `stream`.
+ *
+ * Library option conv_tuned_all = 1 (per call, default 0; IPDM_CONV_TUNED_ALL) widens that rule and nothing else; with it off every
+ * query, workspace size and output bit is as above.  With it on the code query, the workspace query and the two entries also take
+ *   - a role whose layer is narrow (ipdm_conv_layout_code of the role's layer is 0) where the inference plan of that layer names the
+ *     direct kernel: code 5 (6 when the caller has also set conv_nm) -- the role's layer has at most 16 output channels, at most
+ *     direct_max_cin input channels, and at stride 2 at most 32.  The plain image is packed on the device as for the wide layers.  A
+ *     role the plan leaves on the round-1 kernels (code 8: 17 .. 32 output channels in that role, or more input channels) stays at 0;
+ *   - role 1 of every 3x3 stride-2 layer, any channel counts: code 13, which no inference plan returns -- the input gradient in parity
+ *     form (csrc/conv_dgrad_s2.hip: nine tap-GEMMs over the Ho x Wo source grid into four parity classes, 2.25 multiply-adds per dX
+ *     pixel and channel pair instead of 9; exact f32 MFMA, one fmaf-equivalent chain per output in an order that depends on the layer
+ *     alone, so row b of a batch has the bits of row b alone; no atomics, every element of dX written once).  Its workspace holds
+ *     the weights as [tap][Cout rounded up to 4][Cin rounded up to 16].  Other bits than ipdm_conv2d_dgrad, the same float64 gate.
+ * The option is read by each of the four calls: set it around the queries AND around the entry.  A refusal is an error as before. */
 /* role 0 = fprop, 1 = dgrad.  Kernel code in ipdm_conv_kernel_code's numbering that the call will run, or 0: the layer is not taken
- * (narrow in that role; role 1 with stride 2; a size past the kernels' 2 GiB addressing limits), -1 bad argument.  Host only, answers
+ * (narrow in that role; role 1 with stride 2; a size past the kernels' 2 GiB addressing limits -- see conv_tuned_all above for
+ * the first two), -1 bad argument.  Host only, answers
  * without a device, honours the option table. */
 int32_t ipdm_conv2d_tuned_code(int32_t role, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride);
 /* d_ws of the two calls below: the image the planned kernel reads + the plan's K-split buffer; 0 where the code is <= 0 */

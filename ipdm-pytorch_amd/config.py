@@ -63,6 +63,9 @@ _FLAGS = [
     # under wgrad_backend="hip_tuned": the wide 3 x 3 stride-1 layers' weight gradient in the Winograd F(3 x 3, 2 x 2) domain
     # (csrc/conv_wgrad_wino.hip) where ipdm_conv2d_wgrad_wino_code takes the layer
     ("wgrad_wino", bool, False, None),
+    # under conv_backend="hip_tuned": the narrow layers (at most 16 output channels in the role) on conv_direct and the stride-2
+    # input gradient on the parity-form kernel of csrc/conv_dgrad_s2.hip as well (library option conv_tuned_all, set per call)
+    ("conv_tuned_all", bool, False, None),
     # which attention head dims (channels per head at the attention levels) the sampling networks run (no reference counterpart):
     # "tuned" = 64 and 32, the head dims with kernels of their own, every other one refused; "any" = every head dim 1 .. 128
     # (library option attn_any_dim, csrc/attn_gen.hip): what model_channels 48, 96 or 128 need in the default topologies.  In a
@@ -134,6 +137,17 @@ def check_wgrad_wino(opt):
     if getattr(opt, "wgrad_backend", WGRAD_BACKENDS[0]) != "hip_tuned":
         raise ValueError("wgrad_wino needs wgrad_backend=\"hip_tuned\", not %r" % (getattr(opt, "wgrad_backend", WGRAD_BACKENDS[0]),))
     return {"wgrad_wino": True}
+
+
+def check_conv_tuned_all(opt):
+    """The conv_tuned_all key of a training run: {} at its default (or where the options lack the key), so that a default run hands
+    Trainer the four keywords of check_train_backends alone; {"conv_tuned_all": True} otherwise.  It is refused unless
+    conv_backend is "hip_tuned": the option widens that backend's layer rule."""
+    if not getattr(opt, "conv_tuned_all", False):
+        return {}
+    if getattr(opt, "conv_backend", "hip") != "hip_tuned":
+        raise ValueError("conv_tuned_all needs conv_backend=\"hip_tuned\", not %r" % (getattr(opt, "conv_backend", "hip"),))
+    return {"conv_tuned_all": True}
 
 
 def default_cfg(argv=None):

@@ -58,6 +58,7 @@ enum Opt {
     OPT_GN_TRAIN_ONE_PASS_MAX,   // the largest group (floats per sample and group) the one-pass form of gn_grad.hip takes; 0 = the plan's own rule (per call)
     OPT_ATTN_ANY_DIM,        // opt-in: inference attention for every head dim 1 .. 128 (attn_gen.hip): 1 = every d but 64 and 32, 2 = those too (per call)
     OPT_ATTN_TRAIN_ANY_DIM,  // opt-in: training attention (attn_grad.hip) for every head dim 1 .. 128: 65 .. 128 on the four-wave kernels of width 96 / 128 (per call)
+    OPT_CONV_TUNED_ALL,      // opt-in: the tuned training entries (conv_tuned.hip) also take the narrow layers conv_direct runs and the stride-2 input gradient (conv_dgrad_s2.hip, code 13) (per call)
     OPT_COUNT
 };
 int opt(Opt o);

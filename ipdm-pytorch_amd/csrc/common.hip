@@ -46,6 +46,7 @@ const OptDef g_opt_def[OPT_COUNT] = {
     {"gn_train_one_pass_max", 0, true, 0, 16384},      // (gn_grad.hip's one-pass backward keeps 2 N floats in LDS)
     {"attn_any_dim", 0, true, 0, 2},
     {"attn_train_any_dim", 0, true},
+    {"conv_tuned_all", 0, true},
 };
 bool opt_value_ok(int i, int v)
 {
@@ -145,7 +146,8 @@ extern "C" int ipdm_abi_version(void) { return IPDM_ABI_VERSION; }      // 2: ip
 //  neither did options attn_no_presplit and attn_no_pipeline; the query ipdm_attention_plan is an additional entry, and so are
 //  the four ipdm_gn_act_* entries with their option gn_train_one_pass_max; option attn_any_dim and attention kernel code 3
 //  (attn_gen.hip) changed no signature and added no entry; nor did option attn_train_any_dim and the
-//  four-wave kernels of attn_grad.hip for head dims 65 .. 128)
+//  four-wave kernels of attn_grad.hip for head dims 65 .. 128; nor did option conv_tuned_all and training kernel code 13
+//  (conv_dgrad_s2.hip) behind the tuned entries)
 
 extern "C" int ipdm_set_option(const char *name, int value)
 {

@@ -16,6 +16,12 @@
 //                       [h][lk][cout 32][kp] plane IS its thread index, so the stores of a wave to one xi plane are 256 contiguous bytes;
 //                       the bf16 x 3 image behind it (conv_wino3's layers) leaves through LDS as 16-byte stores of 8 channels
 // The entries make no allocation and no synchronisation: images and the plan's K-split buffer live in the caller's workspace.
+//
+// Library option conv_tuned_all (per call, default 0; round 37) widens the layer rule and nothing else:
+//   * a role whose layer has the PLAIN weight layout (interleave 0: at most 32 output channels) is taken where its plan names
+//     conv_direct (code 5; 6 with option conv_nm): the same packer writes its image (group 64, cout_pad 64), role 1 in the mirrored
+//     read order.  A role the plan leaves on conv.hip's 4-wave kernels (code 8) stays at 0;
+//   * role 1 of a stride-2 layer goes to conv_dgrad_s2.hip's parity-form kernel and answers code 13, which no inference plan returns.
 #include <cstdint>
 #include "conv_layer.h"
 #include "conv_train.h"
@@ -154,7 +160,10 @@ struct Role {
     int B, Ci, Co, H, W, ks, stride;        // the layer the dispatcher runs: input [B, Ci, H, W], Co output channels
     int il, cout_pad;
     bool wino_ok;                           // conv_pack_layer's rule: the layer carries the wino image
+    TrainConvGeo g;                         // the layer as the caller named it
 };
+
+constexpr int CODE_DGRAD_S2 = 13;           // conv_dgrad_s2.hip (role 1 of a stride-2 layer under option conv_tuned_all)
 
 constexpr int IMG_PLAIN = 0, IMG_WINO = 1;
 
@@ -170,6 +179,7 @@ int role_of(const char *who, int role, int B, int Cin, int Cout, int H, int W, i
     r->il = conv_weight_interleave(r->Co, r->ks, r->stride);
     r->cout_pad = conv_cout_pad(r->Co, r->il);
     r->wino_ok = conv_wino_shape_ok(r->Co, r->Ci, r->ks, r->stride, r->il);
+    r->g = g;
     *taken = r->il != 0 && !(role == 1 && g.stride == 2);
     return IPDM_OK;
 }
@@ -205,6 +215,19 @@ ConvPlan plan_of(const Role &r, ConvArgs &a)
 }
 bool reads_wino(int code) { return code == 1 || code == 2 || code == 9 || code == 12; }
 
+// The kernel code the role's layer runs on NOW (the option table is read per call), 0: the tuned entries do not take it.  `taken`:
+// role_of's rule.  Under option conv_tuned_all also the plain-layout roles conv_direct runs and role 1 at stride 2 (CODE_DGRAD_S2:
+// a and *p are not filled, the kernel has no plan).
+int code_of(int role, const Role &r, bool taken, ConvArgs &a, ConvPlan *p)
+{
+    const bool all = opt(OPT_CONV_TUNED_ALL) != 0;
+    if (role == 1 && r.g.stride == 2) return all && conv_dgrad_s2_takes(r.g) ? CODE_DGRAD_S2 : 0;
+    if (!taken && !(all && r.il == 0)) return 0;
+    *p = plan_of(r, a);
+    if (!taken && p->code != 5 && p->code != 6) return 0;
+    return addressable(r, a.Ho, a.Wo) ? p->code : 0;
+}
+
 int pack_launch(int image, int role, const float *d_w, const Role &r, float *d_image, hipStream_t st)
 {
     IPDM_REQUIRE(((uintptr_t)d_image & 15) == 0, "conv pack: the image must be 16-byte aligned");
@@ -237,8 +260,10 @@ int run(const char *who, int role, const float *d_src, const float *d_w, const f
     bool taken;
     if (int rc = role_of(who, role, B, Cin, Cout, H, W, ks, stride, &r, &taken)) return rc;
     ConvArgs a;
-    const ConvPlan p = plan_of(r, a);
-    if (!taken || !addressable(r, a.Ho, a.Wo)) {
+    ConvPlan p;
+    const int code = code_of(role, r, taken, a, &p);
+    if (code == CODE_DGRAD_S2) return conv_dgrad_s2_launch(who, d_src, d_w, d_dst, r.g, d_ws, ws_bytes, st);
+    if (!code) {
         set_error("%s: a layer the tuned kernels do not take (ipdm_conv2d_tuned_code is 0): %d -> %d channels, ksize %d, stride %d", who, Cin,
                   Cout, ks, stride);
         return IPDM_ERR_UNSUPPORTED;
@@ -271,20 +296,20 @@ int32_t ipdm_conv2d_tuned_code(int32_t role, int32_t B, int32_t Cin, int32_t Cou
     Role r;
     bool taken;
     if (role_of("ipdm_conv2d_tuned_code", role, B, Cin, Cout, H, W, ksize, stride, &r, &taken)) return -1;
-    if (!taken) return 0;
     ConvArgs a;
-    const ConvPlan p = plan_of(r, a);
-    return addressable(r, a.Ho, a.Wo) ? p.code : 0;
+    ConvPlan p;
+    return code_of(role, r, taken, a, &p);
 }
 
 size_t ipdm_conv2d_tuned_workspace_bytes(int32_t role, int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t stride)
 {
     Role r;
     bool taken;
-    if (role_of("ipdm_conv2d_tuned_workspace_bytes", role, B, Cin, Cout, H, W, ksize, stride, &r, &taken) || !taken) return 0;
+    if (role_of("ipdm_conv2d_tuned_workspace_bytes", role, B, Cin, Cout, H, W, ksize, stride, &r, &taken)) return 0;
     ConvArgs a;
-    const ConvPlan p = plan_of(r, a);
-    return addressable(r, a.Ho, a.Wo) ? workspace_of(r, p) : 0;
+    ConvPlan p;
+    const int code = code_of(role, r, taken, a, &p);
+    return code == CODE_DGRAD_S2 ? conv_dgrad_s2_workspace_bytes(r.g) : code ? workspace_of(r, p) : 0;
 }
 
 int ipdm_conv2d_fprop_tuned(const float *d_x, const float *d_w, const float *d_b, float *d_y, int32_t B, int32_t Cin, int32_t Cout, int32_t H,

@@ -90,7 +90,13 @@ _CONV_PASSES = {
 _WGRAD_WINO = ("ipdm_conv2d_wgrad_wino", "ipdm_conv2d_wgrad_wino_code", "ipdm_conv2d_wgrad_wino_workspace_bytes")
 
 
-def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None, wgrad_wino=False):
+def _tuned_all_scope(tuned_all):
+    """The library option a tuned_all convolution's queries and calls run under: conv_tuned_all = 1 for those alone (the value before
+    it stands again afterwards); tuned_all=False changes nothing."""
+    return _lib.option("conv_tuned_all", 1) if tuned_all else contextlib.nullcontext()
+
+
+def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None, wgrad_wino=False, tuned_all=False):
     """The entry that runs `pass_` ("fprop", "dgrad" or "wgrad") of the layer geo = (B, Cin, Cout, H, W, k, stride), the kernel code
     it will take and the workspace it asks for: the one place that knows which of the training convolutions' entries a pass goes to.
 
@@ -106,7 +112,16 @@ def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None, wgrad_wi
     as without the option.  A negative code or a workspace of 0 bytes raises here too.
 
     shared: a route of the same layer made just before.  Where it and this one both end on conv_grad.hip's entries its size is
-    taken over unasked -- the backward's two passes then make one query and share one allocation."""
+    taken over unasked -- the backward's two passes then make one query and share one allocation.
+
+    tuned_all (with tuned; fprop and dgrad alone): the two queries are asked under the library option conv_tuned_all, which also
+    takes the narrow layers conv_direct runs (code 5) and the stride-2 input gradient (code 13, csrc/conv_dgrad_s2.hip).  The
+    CALL of the entry this names must run under the same option (_tuned_all_scope): the entry reads it again."""
+    if tuned_all and not tuned:
+        raise ValueError("tuned_all needs tuned=True")
+    if tuned_all and pass_ != "wgrad":
+        with _tuned_all_scope(True):
+            return conv_route(pass_, geo, tuned=tuned, shared=shared)
     default, entry, code_query, bytes_query, lead = _CONV_PASSES[pass_]
     code = 0
     if pass_ == "wgrad" and wgrad_tuned and wgrad_wino:
@@ -133,7 +148,7 @@ def conv_route(pass_, geo, tuned=False, wgrad_tuned=False, shared=None, wgrad_wi
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride, tuned, wgrad_tuned=False, wgrad_wino=False):
+    def forward(ctx, x, w, b, stride, tuned, wgrad_tuned=False, wgrad_wino=False, tuned_all=False):
         x, w = x.contiguous(), w.contiguous()
         b = None if b is None else b.contiguous()
         geo = _geometry(x, w, stride)
@@ -141,11 +156,13 @@ class _Conv2d(torch.autograd.Function):
         pad = k // 2
         y = torch.empty((B, Cout, (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            route = conv_route("fprop", geo, tuned=tuned)
+            route = conv_route("fprop", geo, tuned=tuned, tuned_all=tuned_all)
             ws = _scratch(route.workspace_bytes, x.device)
-            call(route.entry, ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(ws), ws.numel(), _lib.current_stream())
+            with _tuned_all_scope(tuned_all):
+                call(route.entry, ptr(x), ptr(w), ptr(b), ptr(y), *geo, ptr(ws), ws.numel(), _lib.current_stream())
         ctx.save_for_backward(x, w)
         ctx.geo, ctx.has_bias, ctx.tuned, ctx.wgrad_tuned, ctx.wgrad_wino = geo, b is not None, tuned, wgrad_tuned, wgrad_wino
+        ctx.tuned_all = tuned_all
         return y
 
     @staticmethod
@@ -157,7 +174,7 @@ class _Conv2d(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         dx = dw = db = None
         with torch.cuda.device(x.device):
-            dgrad = conv_route("dgrad", geo, tuned=ctx.tuned) if need_x else None
+            dgrad = conv_route("dgrad", geo, tuned=ctx.tuned, tuned_all=ctx.tuned_all) if need_x else None
             wgrad = (conv_route("wgrad", geo, wgrad_tuned=ctx.wgrad_tuned, shared=dgrad, wgrad_wino=ctx.wgrad_wino)
                      if need_w or need_b else None)
             # a workspace per pass that runs; the passes that stay on conv_grad.hip share one (one query sizes it for both)
@@ -166,16 +183,17 @@ class _Conv2d(torch.autograd.Function):
             if dgrad is not None:
                 dx = torch.empty_like(x)
                 ws = _scratch(dgrad.workspace_bytes, x.device) if dgrad.code else plain_ws
-                call(dgrad.entry, ptr(dy), ptr(w), ptr(dx), *geo, ptr(ws), ws.numel(), _lib.current_stream())
+                with _tuned_all_scope(ctx.tuned_all):            # (the backward runs later, under autograd: the option is set again)
+                    call(dgrad.entry, ptr(dy), ptr(w), ptr(dx), *geo, ptr(ws), ws.numel(), _lib.current_stream())
             if wgrad is not None:
                 dw = torch.empty_like(w)
                 db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if need_b else None
                 ws = _scratch(wgrad.workspace_bytes, x.device) if wgrad.code else plain_ws
                 call(wgrad.entry, ptr(x), ptr(dy), ptr(dw), ptr(db), *geo, ptr(ws), ws.numel(), _lib.current_stream())
-        return dx, (dw if need_w else None), db, None, None, None, None
+        return dx, (dw if need_w else None), db, None, None, None, None, None
 
 
-def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip", wgrad_wino=False):
+def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip", wgrad_wino=False, tuned_all=False):
     """F.conv2d(x, w, b, stride, padding=k // 2) for the reference's layers (k 1 or 3; stride 2 with k 3 only), differentiable
     once: forward, input gradient and weight / bias gradient are HIP kernels on torch's current stream.  Only the gradients
     autograd asks for are computed (the stem's input gradient, the largest one, never is).
@@ -183,7 +201,9 @@ def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip", wgrad_wino=False):
     tuned=True sends the forward and the input gradient of the layers ipdm_conv2d_tuned_code takes (the wide ones) through
     the inference dispatcher's kernels, their weight images packed on the device in front of each launch
     (ipdm_conv2d_fprop_tuned / ipdm_conv2d_dgrad_tuned); the layers it answers 0 for, and every weight / bias gradient, stay
-    on the entries above.
+    on the entries above.  tuned_all=True (with tuned=True only) asks and calls those entries under the library option
+    conv_tuned_all, set for these calls alone: the narrow layers conv_direct runs (at most 16 output channels in the role, code 5)
+    and the stride-2 input gradient (code 13, the parity-form kernel of csrc/conv_dgrad_s2.hip) are taken too.
 
     wgrad="hip_tuned" (independent of tuned=) sends the weight / bias gradient through ipdm_conv2d_wgrad_tuned (the streamed /
     tiled kernels of csrc/conv_wgrad.hip) where ipdm_conv2d_wgrad_tuned_code is non-zero, and through ipdm_conv2d_wgrad where it
@@ -196,7 +216,9 @@ def conv2d(x, w, b=None, stride=1, tuned=False, wgrad="hip", wgrad_wino=False):
         raise ValueError("wgrad must be one of %s, not %r" % (WGRAD_BACKENDS, wgrad))
     if wgrad_wino and wgrad != "hip_tuned":
         raise ValueError("wgrad_wino needs wgrad=\"hip_tuned\", not %r" % (wgrad,))
-    return _Conv2d.apply(x, w, b, int(stride), bool(tuned), wgrad == "hip_tuned", bool(wgrad_wino))
+    if tuned_all and not tuned:
+        raise ValueError("tuned_all needs tuned=True")
+    return _Conv2d.apply(x, w, b, int(stride), bool(tuned), wgrad == "hip_tuned", bool(wgrad_wino), bool(tuned_all))
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm (+SiLU) under autograd
@@ -353,6 +375,7 @@ class Conv(nn.Module):
         super().__init__()
         self.stride, self.backend, self.wgrad = stride, backend, "hip"      # wgrad: set by TrainUNet(wgrad_backend=...)
         self.wgrad_wino = False                                             # set by TrainUNet(wgrad_wino=...)
+        self.tuned_all = False                                              # set by TrainUNet(conv_tuned_all=...)
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k))
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if bias:
@@ -364,7 +387,7 @@ class Conv(nn.Module):
     def forward(self, x):
         if self.backend in ("hip", "hip_tuned"):
             return conv2d(x, self.weight, self.bias, self.stride, tuned=self.backend == "hip_tuned", wgrad=self.wgrad,
-                          wgrad_wino=self.wgrad_wino)
+                          wgrad_wino=self.wgrad_wino, tuned_all=self.tuned_all)
         return F.conv2d(x, self.weight, self.bias, stride=self.stride, padding=self.weight.shape[-1] // 2)
 
 
@@ -468,7 +491,8 @@ class TrainUNet(nn.Module):
 
     def __init__(self, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(8, 16),
                  dropout=0, channel_mult=(1, 2, 2, 2), conv_resample=True, num_heads=4, pre_downsample_times=1,
-                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip", wgrad_wino=False, head_dims="tuned"):
+                 conv_backend="hip", norm_backend="torch", attn_backend="torch", wgrad_backend="hip", wgrad_wino=False, head_dims="tuned",
+                 conv_tuned_all=False):
         super().__init__()
         if dropout:
             raise NotImplementedError("dropout is never instantiated by the reference harness (Model/model.py:198)")
@@ -487,6 +511,8 @@ class TrainUNet(nn.Module):
                              "weight gradient to torch" % (wgrad_backend,))
         if wgrad_wino and wgrad_backend != "hip_tuned":
             raise ValueError("wgrad_wino needs wgrad_backend=\"hip_tuned\", not %r" % (wgrad_backend,))
+        if conv_tuned_all and conv_backend != "hip_tuned":
+            raise ValueError("conv_tuned_all needs conv_backend=\"hip_tuned\", not %r" % (conv_backend,))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks, self.num_heads = num_res_blocks, num_heads
         self.attention_resolutions, self.channel_mult = tuple(attention_resolutions), tuple(channel_mult)
@@ -524,10 +550,10 @@ class TrainUNet(nn.Module):
                     ds //= 2
                 self.up_blocks.append(_Stage(layers))
         self.out = nn.Sequential(_norm(ch), nn.SiLU(), Conv(ch, out_channels, 3, backend=be))
-        self.wgrad_backend, self.wgrad_wino = wgrad_backend, bool(wgrad_wino)
+        self.wgrad_backend, self.wgrad_wino, self.conv_tuned_all = wgrad_backend, bool(wgrad_wino), bool(conv_tuned_all)
         for m in self.modules():
             if isinstance(m, Conv):
-                m.wgrad, m.wgrad_wino = wgrad_backend, self.wgrad_wino
+                m.wgrad, m.wgrad_wino, m.tuned_all = wgrad_backend, self.wgrad_wino, self.conv_tuned_all
 
     def unet_kwargs(self):
         """The constructor arguments of a UNetModel of the same topology."""
@@ -544,9 +570,11 @@ class TrainUNet(nn.Module):
         """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name ->
         (fprop code, dgrad code), the kernels of ipdm_conv_kernel_code's numbering its forward and input gradient take under
         conv_backend="hip_tuned"; 0: that pass stays on conv_grad.hip's entry (every pass does under the other backends).
-        Host only: the walk follows forward() on shapes, and the codes are conv_route's (option table included)."""
+        Host only: the walk follows forward() on shapes, and the codes are conv_route's (option table included; under
+        conv_tuned_all also 5, a narrow layer on conv_direct, and 13, the stride-2 input gradient of csrc/conv_dgrad_s2.hip)."""
         tuned = self.conv_backend == "hip_tuned"
-        return self._conv_walk(shape, lambda geo: tuple(conv_route(p, geo, tuned=tuned).code for p in ("fprop", "dgrad")))
+        return self._conv_walk(shape, lambda geo: tuple(conv_route(p, geo, tuned=tuned, tuned_all=self.conv_tuned_all).code
+                                                        for p in ("fprop", "dgrad")))
 
     def wgrad_routes(self, shape):
         """For an input of `shape` [B, C, H, W]: an OrderedDict, in forward order, of every convolution's module name -> the
@@ -807,7 +835,7 @@ class Trainer:
     torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip")."""
 
     def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch",
-                 wgrad_backend="hip", wgrad_wino=False, head_dims="tuned"):
+                 wgrad_backend="hip", wgrad_wino=False, head_dims="tuned", conv_tuned_all=False):
         from .diffusion import GaussianDiffusion, NoiseSource
         self.head_dims = check_head_dims(head_dims)          # of the TrainUNet's attention cores and of sampling_model()'s UNetModel
         if domain not in ("img", "proj"):
@@ -823,7 +851,8 @@ class Trainer:
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
             self.model = TrainUNet(conv_backend=conv_backend, norm_backend=norm_backend, attn_backend=attn_backend,
-                                   wgrad_backend=wgrad_backend, wgrad_wino=wgrad_wino, head_dims=self.head_dims, **kw).to(self.device)
+                                   wgrad_backend=wgrad_backend, wgrad_wino=wgrad_wino, head_dims=self.head_dims,
+                                   conv_tuned_all=conv_tuned_all, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
         adam = HipAdam if optim_backend == "hip" else torch.optim.Adam
@@ -947,14 +976,14 @@ class progressive_domain_trainer:
     Single process: the reference's train() has no gradient all-reduce either.  The reference has no EMA."""
 
     def __init__(self, opt, result_save_path=None):
-        from .config import check_attn_head_dims, check_train_backends, check_wgrad_backend, check_wgrad_wino
+        from .config import check_attn_head_dims, check_conv_tuned_all, check_train_backends, check_wgrad_backend, check_wgrad_wino
         if opt.mode not in ("train_img", "train_proj"):
             raise ValueError("progressive_domain_trainer runs mode 'train_img' or 'train_proj', not %r (progressive_domain_denoiser "
                              "runs the test_* modes)" % (opt.mode,))
         self.opt, self.opt_temp = opt, copy.deepcopy(opt)
         self.domain = "img" if opt.mode == "train_img" else "proj"
         self.rank = 0
-        backends = dict(check_train_backends(opt), **check_wgrad_backend(opt), **check_wgrad_wino(opt))
+        backends = dict(check_train_backends(opt), **check_wgrad_backend(opt), **check_wgrad_wino(opt), **check_conv_tuned_all(opt))
         self.train_seed = int(getattr(opt, "train_seed", 0))
         self.result_save_path = result_save_path
         run = "%s_%s" % (opt.model_name, opt.run_name)

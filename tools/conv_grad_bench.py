@@ -23,8 +23,15 @@ norm_backend "torch" and "hip", and under conv_backend="hip_tuned" with wgrad_ba
          yardstick, in the same process, and an arm of the wgrad Trainer.step table.  --wino runs those layers' weight-gradient
          arms and that step table alone.
 
+  all    --tuned-all: the passes that conv_backend="hip_tuned" routes differently under conv_tuned_all (library option
+         conv_tuned_all: the narrow layers on conv_direct, code 5; the stride-2 input gradient on csrc/conv_dgrad_s2.hip, code 13)
+         alone.  Per pass three arms taking turns: tuned (what hip_tuned runs without the flag -- the yardstick, in the same
+         process), all (the tuned entry under the option) and torch; the plain-image packer alone beside the code-5 passes; and
+         one Trainer.step per network with the flag off and on beside the torch arm, norm_backend "torch" and "hip".
+
     python tools/conv_grad_bench.py --out profiles/r29_conv_grad_bench.json
     python tools/conv_grad_bench.py --wino --out profiles/r33_conv_grad_bench.json
+    python tools/conv_grad_bench.py --tuned-all --out profiles/r37_conv_grad_bench.json
 """
 import argparse
 import ctypes
@@ -201,6 +208,153 @@ def bench_shape(key, rounds, reps, ops=("fprop", "dgrad", "wgrad")):
     return rec
 
 
+def family_all(key):
+    Cin, Cout, H, W, k, s = key
+    return "1x1 narrow" if k == 1 else "3x3 stride 2" if s == 2 else "3x3 narrow"
+
+
+def bench_shape_all(key, rounds, reps):
+    """The passes of one layer that conv_tuned_all routes differently: arms tuned (the route without the flag), all, torch."""
+    import contextlib
+    import torch
+    import torch.nn.functional as F
+    from ipdm_pytorch_amd import _lib
+    from ipdm_pytorch_amd._lib import call, lib, ptr
+    from ipdm_pytorch_amd.train import conv_route
+    Cin, Cout, H, W, k, s = key
+    dev, p = "cuda:0", k // 2
+    geo = (1, Cin, Cout, H, W, k, s)
+    x = torch.randn((1, Cin, H, W), device=dev)
+    w = torch.randn((Cout, Cin, k, k), device=dev) * (1.0 / (Cin * k * k)) ** 0.5
+    b = torch.randn((Cout,), device=dev)
+    y = F.conv2d(x, w, b, stride=s, padding=p)
+    dy = torch.randn_like(y)
+    dx = torch.empty_like(x)
+    st = _lib.current_stream
+    back = torch.ops.aten.convolution_backward
+    operands = {"fprop": (ptr(x), ptr(w), ptr(b), ptr(y)), "dgrad": (ptr(dy), ptr(w), ptr(dx))}
+    torch_arm = {"fprop": lambda: F.conv2d(x, w, b, stride=s, padding=p),
+                 "dgrad": lambda: back(dy, x, w, [Cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [True, False, False])}
+    rec = {"shape": list(geo), "family": family_all(key), "passes": {}}
+    for role, op in enumerate(("fprop", "dgrad")):
+        off, on = conv_route(op, geo, tuned=True), conv_route(op, geo, tuned=True, tuned_all=True)
+        if on == off or (op == "dgrad" and Cin == 1):      # (Cin = 1: the stems, whose input gradient is never asked for)
+            continue
+
+        def launch(route):
+            ws = torch.empty(route.workspace_bytes, dtype=torch.uint8, device=dev)
+            return lambda: call(route.entry, *operands[op], *geo, ptr(ws), route.workspace_bytes, st())
+        # (arm, what it calls, the option's value around its timed interval)
+        arms = [("tuned", launch(off), 0), ("all", launch(on), 1), ("torch", torch_arm[op], 0)]
+        if on.code in (5, 6):
+            img = torch.empty(lib().ipdm_conv_image_bytes(0, role, Cin, Cout, k, s), dtype=torch.uint8, device=dev)
+            arms.append(("pack", lambda role=role, img=img: call("ipdm_conv_pack_device", 0, role, ptr(w), Cin, Cout, k, s, ptr(img), st()), 0))
+        ms = {name: [] for name, _, _ in arms}
+        for r in range(rounds + 1):                # round 0: warm-up
+            for name, fn, flag in arms:
+                with (_lib.option("conv_tuned_all", 1) if flag else contextlib.nullcontext()):
+                    t = device_ms(fn, reps)
+                if r:
+                    ms[name].append(t)
+        out = {name: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "n": len(v)} for name, v in ms.items()}
+        gain = out["tuned"]["median_ms"] - out["all"]["median_ms"]
+        spread = (out["tuned"]["max_ms"] - out["tuned"]["min_ms"]) + (out["all"]["max_ms"] - out["all"]["min_ms"])
+        rec["passes"][op] = {"code_off": off.code, "code_on": on.code, "entry_off": off.entry, "ms": out, "gain_ms": gain, "spread_ms": spread,
+                             "verdict": "faster" if gain > spread else "slower" if -gain > spread else "within spread",
+                             "all_over_torch": out["all"]["median_ms"] / out["torch"]["median_ms"]}
+    return rec
+
+
+def bench_steps_all(opt, domain, rounds, norm_backend="torch"):
+    """One Trainer.step per round and arm under conv_backend="hip_tuned": conv_tuned_all off (the yardstick) and on, beside the torch arm."""
+    import time
+    import torch
+    from ipdm_pytorch_amd.train import Trainer
+    H, W = SIZES[domain]
+    images = torch.rand((1, H, W)) * (4.0 if domain == "proj" else 0.3)
+    arms = {"off": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend),
+            "on": Trainer(opt, domain, seed=1, conv_backend="hip_tuned", norm_backend=norm_backend, conv_tuned_all=True),
+            "torch": Trainer(opt, domain, seed=1, conv_backend="torch", norm_backend=norm_backend)}
+    for be in ("on", "torch"):
+        arms[be].model.load_state_dict(arms["off"].model.state_dict())
+    z = torch.randn((1, 1, H, W), device=opt.device)
+    ms, losses = {be: [] for be in arms}, {be: [] for be in arms}
+    for r in range(rounds + 1):                    # round 0: warm-up
+        for be, tr in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss = tr.step(images, t=[25], noise=z)
+            torch.cuda.synchronize()
+            if r:
+                ms[be].append(1e3 * (time.perf_counter() - t0))
+            losses[be].append(loss)
+    med = {be: statistics.median(v) for be, v in ms.items()}
+    spread = (max(ms["off"]) - min(ms["off"])) + (max(ms["on"]) - min(ms["on"]))
+    gain = med["off"] - med["on"]
+    return {"size": [H, W], "B": 1, "t": 25, "conv_backend": "hip_tuned", "norm_backend": norm_backend,
+            "step_ms": {be: {"median_ms": med[be], "min_ms": min(v), "max_ms": max(v), "n": len(v)} for be, v in ms.items()},
+            "off_over_torch": med["off"] / med["torch"], "on_over_torch": med["on"] / med["torch"],
+            "gain_ms": gain, "spread_ms": spread, "gain_exceeds_spread": gain > spread, "losses": losses,
+            "routes_on": {k: list(v) for k, v in arms["on"].model.conv_routes((1, 1, H, W)).items()},
+            "peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
+
+
+def main_all(a, opt, shapes):
+    import torch
+    res = {"device": torch.cuda.get_device_name(0), "B": 1, "rounds": a.rounds, "reps": a.reps, "mode": "tuned_all", "networks": {}}
+    for d in ("img", "proj"):
+        layers = []
+        for key, names in shapes[d].items():
+            rec = bench_shape_all(key, a.rounds, a.reps)
+            if not rec["passes"]:
+                continue
+            rec["layers"] = len(names)
+            layers.append(rec)
+            for op, q in rec["passes"].items():
+                print("%s %-26s %-13s %-5s code %d -> %2d: tuned %.3f [%.3f .. %.3f]  all %.3f [%.3f .. %.3f]  torch %.3f ms  x%d layers: %s%s"
+                      % (d, "x".join(map(str, key)), rec["family"], op, q["code_off"], q["code_on"], q["ms"]["tuned"]["median_ms"],
+                         q["ms"]["tuned"]["min_ms"], q["ms"]["tuned"]["max_ms"], q["ms"]["all"]["median_ms"], q["ms"]["all"]["min_ms"],
+                         q["ms"]["all"]["max_ms"], q["ms"]["torch"]["median_ms"], rec["layers"], q["verdict"],
+                         "  (pack %.3f)" % q["ms"]["pack"]["median_ms"] if "pack" in q["ms"] else ""), flush=True)
+            torch.cuda.empty_cache()
+        fams = {}
+        for fam in sorted({r["family"] for r in layers}):
+            for op in ("fprop", "dgrad"):
+                rows = [r for r in layers if r["family"] == fam and op in r["passes"]]
+                if not rows:
+                    continue
+                per = lambda arm, stat: sum(r["passes"][op]["ms"][arm][stat] * r["layers"] for r in rows)       # noqa: E731
+                f = {"layers": sum(r["layers"] for r in rows), "tuned_ms_per_step": per("tuned", "median_ms"), "all_ms_per_step": per("all", "median_ms"),
+                     "torch_ms_per_step": per("torch", "median_ms"),
+                     "spread_ms": per("tuned", "max_ms") - per("tuned", "min_ms") + per("all", "max_ms") - per("all", "min_ms"),
+                     "pack_ms_per_step": sum(r["passes"][op]["ms"]["pack"]["median_ms"] * r["layers"] for r in rows if "pack" in r["passes"][op]["ms"]),
+                     "losing_layers": ["x".join(map(str, r["shape"])) for r in rows if r["passes"][op]["verdict"] == "slower"]}
+                f["gain_ms"] = f["tuned_ms_per_step"] - f["all_ms_per_step"]
+                f["gain_exceeds_spread"] = f["gain_ms"] > f["spread_ms"]
+                f["all_over_torch"] = f["all_ms_per_step"] / f["torch_ms_per_step"]
+                fams.setdefault(fam, {})[op] = f
+        res["networks"][d] = {"size": list(SIZES[d]), "layers": layers, "families": fams}
+        if a.out:
+            dump(a.out + ".partial", res)
+    for d in ("img", "proj"):
+        if a.no_steps:
+            break
+        for nb in ("torch", "hip"):
+            s = res["networks"][d]["trainer_step" if nb == "torch" else "trainer_step_norm_hip"] = bench_steps_all(opt, d, a.step_rounds, nb)
+            print("%s Trainer.step (conv_backend=hip_tuned, norm_backend=%s): conv_tuned_all off %.1f ms, on %.1f ms, torch arm %.1f ms; gain %.1f ms, "
+                  "spread %.1f ms" % (d, nb, s["step_ms"]["off"]["median_ms"], s["step_ms"]["on"]["median_ms"], s["step_ms"]["torch"]["median_ms"],
+                                      s["gain_ms"], s["spread_ms"]), flush=True)
+            torch.cuda.empty_cache()
+            if a.out:
+                dump(a.out + ".partial", res)
+    if a.out:
+        dump(a.out, res)
+        if os.path.exists(a.out + ".partial"):
+            os.remove(a.out + ".partial")
+    for d, net in res["networks"].items():
+        print(d, json.dumps(net["families"], sort_keys=True))
+
+
 def bench_wgrad_steps(opt, domain, rounds, norm_backend="torch"):
     """The same for wgrad_backend off and on under conv_backend="hip_tuned", beside the torch arm."""
     import time
@@ -295,6 +449,8 @@ def main():
     ap.add_argument("--no-steps", action="store_true", help="skip both Trainer.step tables")
     ap.add_argument("--wino", action="store_true", help="the layers ipdm_conv2d_wgrad_wino_code takes alone: their weight-gradient arms "
                     "and the wgrad Trainer.step table")
+    ap.add_argument("--tuned-all", action="store_true", help="the passes conv_tuned_all routes differently alone: arms tuned (the "
+                    "yardstick) / all / torch, and the Trainer.step table with the flag off and on")
     ap.add_argument("--list", action="store_true", help="print the shapes and stop (needs no GPU)")
     a = ap.parse_args()
     import torch
@@ -311,6 +467,8 @@ def main():
         return
     if not torch.cuda.is_available():
         sys.exit("conv_grad_bench needs a GPU: a CPU run measures nothing")
+    if a.tuned_all:
+        return main_all(a, opt, shapes)
     res = {"device": torch.cuda.get_device_name(0), "B": 1, "rounds": a.rounds, "reps": a.reps, "ops": list(a.ops), "networks": {}}
     for d in ("img", "proj"):
         layers = []
