@@ -840,6 +840,38 @@ int64_t ipdm_adam_chunks(const int64_t *sizes, int32_t n_tensors, ipdm_adam_chun
  * a beta outside [0, 1): IPDM_ERR_INVALID before any launch.  Asynchronous on `stream`, allocates nothing, does not synchronise. */
 int ipdm_adam_step(const ipdm_adam_tensor *d_tensors, int32_t n_tensors, const ipdm_adam_chunk *d_chunks, int64_t n_chunks,
                    double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void *stream);
+/* Gradient clipping by the global norm and an exponential moving average of the weights, inside the optimiser's launches (the
+ * reference has neither; both are opt-in).  Three additive entries, detected by symbol (dlsym of ipdm_adam_step_ex); a clipped
+ * step is ipdm_grad_sumsq (once per parameter set, into consecutive ranges of one buffer), ipdm_grad_clip_coef (once), then
+ * ipdm_adam_step_ex per set with the coefficient's device address -- no host synchronisation anywhere.
+ *
+ * ipdm_grad_sumsq: d_partials[c] = sum of g[i]^2 over chunk c of the table (n_chunks doubles), every float widened to double
+ * before it is squared.  A chunk of a tensor with g == NULL, or a record ipdm_adam_step would skip, writes 0.  The order of
+ * the additions inside a chunk is a function of (len, 16-byte alignment of g) alone -- lane l of 256 takes the elements (16-byte
+ * groups where g + offset is aligned, single floats otherwise) l, l + 256, ..., then a fixed tree over the lanes and the four
+ * waves -- and there are no atomics: the same inputs give the same bits whatever the grid.  g is only read, and no float
+ * outside [0, n) of a tensor is read.  A NULL table or a negative count: IPDM_ERR_INVALID before any launch. */
+int ipdm_grad_sumsq(const ipdm_adam_tensor *d_tensors, int32_t n_tensors, const ipdm_adam_chunk *d_chunks, int64_t n_chunks,
+                    double *d_partials, void *stream);
+/* One workgroup folds n_partials doubles in index order (lane k of 256 takes k, k + 256, ..., then the same fixed tree) and
+ * writes d_norm[0] = sqrt(sum) and d_coef[0] = (float)min(1, max_norm / (norm + 1e-6)), formed in double and rounded once:
+ * torch.nn.utils.clip_grad_norm_'s expression.  As there, a non-finite norm is not special-cased: a NaN norm gives a NaN
+ * coefficient, an infinite one the coefficient 0 (which turns the infinite gradients into NaN).  n_partials == 0: norm 0,
+ * coefficient 1.  NULL d_norm / d_coef, NULL partials with a count, a negative count, max_norm that is not > 0:
+ * IPDM_ERR_INVALID before any launch. */
+int ipdm_grad_clip_coef(const double *d_partials, int64_t n_partials, double max_norm, double *d_norm, float *d_coef, void *stream);
+/* ipdm_adam_step with two optional legs, the same kernel with either compiled in or out (both NULL: ipdm_adam_step's bits).
+ * d_gscale: NULL, or the device address of ONE float c; the update then uses gs = c * g (one float32 rounding, no contraction)
+ * in place of g, in front of the weight-decay term.  g is still only read.
+ * d_ema: NULL, or a device array of n_tensors pointers (an entry may be NULL); for a non-NULL entry e (n floats, contiguous),
+ * after the update, e' = e + w (p' - e), w = (float)(1 - ema_decay), in float32 without contraction, p' the value just written.
+ * A tensor with g == NULL and an EMA entry still moves its average toward its unchanged p; its p, m, v stay untouched.
+ * 16-byte accesses only where every address the chunk touches allows them, the average's included.  ema_decay outside [0, 1)
+ * with a non-NULL d_ema, or any argument ipdm_adam_step refuses: IPDM_ERR_INVALID before any launch.  Asynchronous on `stream`,
+ * allocates nothing, does not synchronise, no atomics. */
+int ipdm_adam_step_ex(const ipdm_adam_tensor *d_tensors, int32_t n_tensors, const ipdm_adam_chunk *d_chunks, int64_t n_chunks,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                      const float *d_gscale, float *const *d_ema, double ema_decay, void *stream);
 /* replaces Siemens_dataset_npz.get_patch (Dataset/npz_data_loader.py:170-177) for a batch, with the `/ 10` of the projections
  * under clip_proj (:97-98) and the .clamp(min=0) of train() (Utils/train_test_utils.py:262) fused:
  *   d_out[i, j, y, x] = max(d_slices[i, r + y, c + x] (/ 10 when div10), 0),   (r, c) = offsets_host[i * m + j]

@@ -189,6 +189,9 @@ PROTOTYPES = {
     "ipdm_yj_fit_host": (C.c_int, [_vp, _i32, _i64, C.POINTER(_f64), C.POINTER(_i32)]),
     "ipdm_adam_chunks": (_i64, [_vp, _i32, _vp, _i64]),
     "ipdm_adam_step": (C.c_int, [_vp, _i32, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "ipdm_grad_sumsq": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _vp]),
+    "ipdm_grad_clip_coef": (C.c_int, [_vp, _i64, _f64, _vp, _vp, _vp]),
+    "ipdm_adam_step_ex": (C.c_int, [_vp, _i32, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _vp, _vp, _f64, _vp]),
     "ipdm_crop_patches": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp, _i32, _vp]),
 }
 

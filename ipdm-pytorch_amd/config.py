@@ -72,6 +72,11 @@ _FLAGS = [
     # train_* mode with attn_backend="hip" the same key reaches the training attention core: "tuned" = head dims 1 .. 64, "any" =
     # 1 .. 128 (library option attn_train_any_dim, csrc/attn_grad.hip); attn_backend="torch" takes every head dim either way
     ("attn_head_dims", str, "tuned", None),
+    # two things a training run may turn on that the reference has not (train.Trainer / train.HipAdam): max_grad_norm > 0 clips the
+    # gradients of every step by their global norm (0 = off), ema_decay in (0, 1) keeps an exponential moving average of the
+    # weights, saved as ema_{img,proj}_model-<epoch> beside every checkpoint (0 = off); use_ema_weights makes fit()'s test(it) leg
+    # score the averaged weights and makes a test_* mode load the ema_ files in place of the raw ones
+    ("max_grad_norm", float, 0.0, None), ("ema_decay", float, 0.0, None), ("use_ema_weights", bool, False, None),
 ]
 METRICS_BACKENDS = ("numpy", "hip")
 NORMAL_BACKENDS = ("sklearn", "hip")
@@ -150,6 +155,31 @@ def check_conv_tuned_all(opt):
     return {"conv_tuned_all": True}
 
 
+def check_clip_ema(opt):
+    """The max_grad_norm / ema_decay keys of a training run as Trainer keywords: {} at their defaults of 0 = off (or where the
+    options lack the keys), so that a default run hands Trainer the four keywords of check_train_backends alone.  max_grad_norm
+    is a finite number >= 0, ema_decay a number in [0, 1); anything else is refused by name."""
+    out = {}
+    for name, ok in (("max_grad_norm", lambda v: 0.0 <= v < float("inf")), ("ema_decay", lambda v: 0.0 <= v < 1.0)):
+        value = getattr(opt, name, 0.0)
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not ok(float(value)):
+            raise ValueError("%s must be %s, not %r" % (name, "a finite number >= 0 (0 = off)" if name == "max_grad_norm"
+                                                         else "in [0, 1) (0 = off)", value))
+        if float(value) != 0.0:
+            out[name] = float(value)
+    return out
+
+
+def check_use_ema_weights(opt, training=False):
+    """The use_ema_weights key: a bool; in a training run it needs ema_decay on (there is no average to score otherwise)."""
+    value = getattr(opt, "use_ema_weights", False)
+    if not isinstance(value, bool):
+        raise ValueError("use_ema_weights must be a bool, not %r" % (value,))
+    if value and training and not check_clip_ema(opt).get("ema_decay"):
+        raise ValueError("use_ema_weights needs ema_decay > 0 in a training run: without it no average is kept")
+    return value
+
+
 def default_cfg(argv=None):
     """Config/default_config.py:7-172: argparse defaults, then --load_option_path JSON overlays every
     key that was not given on the command line."""
@@ -177,6 +207,8 @@ def default_cfg(argv=None):
     check_metrics_backend(opt.metrics_backend)
     check_normal_backend(opt.normal_backend)
     check_attn_head_dims(opt.attn_head_dims)
+    check_clip_ema(opt)
+    check_use_ema_weights(opt)
     return opt
 
 

@@ -166,11 +166,26 @@ class progressive_domain_denoiser(EvaluationMixin):
         """Utils/train_test_utils.py:247-251 + LoggerX.load_checkpoints / load_network (Utils/loggerx.py:69-80,131-140):
         state_dict files `<load path>/{proj_model,img_model}-<epoch>` (what LoggerX.checkpoints writes into its
         save_models directory), `module.` removed from the keys.  A file that does not exist is skipped as in the
-        reference (osp.exists guard) -- but not silently: the network then keeps its initial weights."""
+        reference (osp.exists guard) -- but not silently: the network then keeps its initial weights.
+        Under use_ema_weights (no reference counterpart) the files are `ema_{proj_model,img_model}-<epoch>`, the averaged weights
+        a training run with ema_decay writes beside every checkpoint, and a file that does not exist is an error that names it:
+        falling back to the raw weights would score something other than what was asked for."""
         import warnings
         o = self.opt
+        use_ema = getattr(o, "use_ema_weights", False)
         for name, model, ep, path in (("img_model", self.img_model, o.resume_epochs_img, o.load_img_model_path),
                                       ("proj_model", self.proj_model, o.resume_epochs_proj, o.load_proj_model_path)):
+            if use_ema and ep > 0 and path is not None and model is not None:
+                name = "ema_" + name
+                f = os.path.join(path, "%s-%d" % (name, ep))
+                if not os.path.exists(f):
+                    f = os.path.join(path, "save_models", "%s-%d" % (name, ep))      # a run directory was given
+                if not os.path.exists(f):
+                    raise FileNotFoundError("use_ema_weights: %s-%d not found under %s (nor its save_models): a training run "
+                                            "writes it when ema_decay is on" % (name, ep, path))
+                sd = torch.load(f, map_location="cpu")
+                model.load_state_dict({k.replace("module.", ""): v for k, v in sd.items()})
+                continue
             if ep > 0 and path is not None and model is not None:
                 f = os.path.join(path, "%s-%d" % (name, ep))
                 if not os.path.exists(f) and os.path.exists(os.path.join(path, "save_models", "%s-%d" % (name, ep))):

@@ -661,15 +661,38 @@ class HipAdam(torch.optim.Optimizer):
     A parameter whose .grad is None is skipped, as torch skips it: its record goes into the table with a NULL gradient and its
     `step` does not advance.  (Parameters of one group whose `step` counts differ -- only after such skips -- have different
     bias corrections: the group is then updated with one launch per distinct count.)  Parameters are float32 GPU tensors,
-    contiguous; a view that starts at any float offset is fine.  There is no fall-back to torch's update."""
+    contiguous; a view that starts at any float offset is fine.  There is no fall-back to torch's update.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+    Two opt-in keywords ride in the same launches (neither is in the reference; without them nothing about the class changes):
+    max_grad_norm clips the gradients by their global norm over EVERY param group, as torch.nn.utils.clip_grad_norm_ does,
+    without a host synchronisation -- ipdm_grad_sumsq per group, ipdm_grad_clip_coef once, and the update reads the coefficient
+    from device memory (the gradients themselves are not rewritten); last_grad_norm is then the one-element float64 device
+    tensor holding the norm of the last step.  ema (a list of tensors parallel to the parameters, owned by the caller, an
+    entry may be None) with ema_decay keeps e' = e + (1 - ema_decay)(p' - e) of every parameter in the update's launch; a
+    parameter without a gradient still moves its average toward its unchanged value.  The averages are NOT optimiser state:
+    `state` and state_dict() keep torch.optim.Adam's layout."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=None, ema=None, ema_decay=None):
         if not (lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("HipAdam: lr %r, betas %r, eps %r, weight_decay %r" % (lr, betas, eps, weight_decay))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("HipAdam: max_grad_norm %r (None, or a positive number)" % (max_grad_norm,))
+        if (ema is None) != (ema_decay is None) or (ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0):
+            raise ValueError("HipAdam: ema and ema_decay come together, ema_decay in [0, 1) (got ema_decay %r)" % (ema_decay,))
         self._plans, self._tables, self._steady = {}, {}, {}
         # the keys (and the other defaults) of THIS torch's Adam: param_groups then round-trip through either class
         probe = torch.optim.Adam([torch.zeros(1, requires_grad=True)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, dict(probe.defaults))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.last_grad_norm = None
+        self._ema, self._clip_buffers = None, None
+        if ema is not None:
+            flat = [p for g in self.param_groups for p in g["params"]]
+            ema = list(ema)
+            if len(ema) != len(flat):
+                raise ValueError("HipAdam: %d ema tensors for %d parameters" % (len(ema), len(flat)))
+            self._ema = {id(p): e for p, e in zip(flat, ema) if e is not None}
 
     # whatever replaces parameters or state drops what step() remembers of them
     def _forget(self):
@@ -687,6 +710,10 @@ class HipAdam(torch.optim.Optimizer):
     def __setstate__(self, state):
         super().__setstate__(state)
         self._plans, self._tables, self._steady = {}, {}, {}
+
+    @property
+    def _extended(self):
+        return self.max_grad_norm is not None or self._ema is not None
 
     def _plan(self, gi, sizes, device):
         """The chunk table of param group gi on the device, built once per (sizes, device) by ipdm_adam_chunks."""
@@ -739,6 +766,7 @@ class HipAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        jobs = [] if self._extended else None
         for gi, group in enumerate(self.param_groups):
             if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
                 raise NotImplementedError("HipAdam: amsgrad / maximize / decoupled_weight_decay are not what the reference builds")
@@ -756,15 +784,83 @@ class HipAdam(torch.optim.Optimizer):
                 steady["t"] += 1
                 columns = [[t.data_ptr() for t in params], [g.data_ptr() for g in grads], [t.data_ptr() for t in steady["m"]],
                            [t.data_ptr() for t in steady["v"]], steady["n"]]
-                self._launch(gi, group, columns, steady["device"], steady["t"])
+                if jobs is None:
+                    self._launch(gi, group, columns, steady["device"], steady["t"])
+                else:                                 # one more address column: the averages'
+                    jobs.append((gi, group, steady["device"], columns, [(steady["t"], columns[1], steady.get("ema"))], None))
                 continue
-            self._step_checked(gi, group, params, grads)
+            self._step_checked(gi, group, params, grads, jobs)
+        if jobs:
+            self._run_extended(jobs)
         return loss
 
-    def _step_checked(self, gi, group, params, grads):
+    def _ema_column(self, params, device):
+        col = []
+        for p in params:
+            e = self._ema.get(id(p))
+            if e is not None:
+                self._check(e, "an ema tensor", device, p.shape)
+            col.append(0 if e is None else e.data_ptr())
+        return col
+
+    def _table_ex(self, key, columns, ecol, device):
+        """_table with the averages' addresses behind the records (n_tensors more 8-byte words of the same upload)."""
+        last = self._tables.get(key)
+        if last is not None and last[0] == (columns, ecol):
+            return last[1]
+        host = torch.tensor(list(columns) + [ecol], dtype=torch.int64)
+        dev = torch.cat([host[:5].t().reshape(-1), host[5]]).pin_memory().to(device, non_blocking=True)
+        self._tables[key] = ((columns, ecol), dev)
+        return dev
+
+    def _run_extended(self, jobs):
+        """A step with max_grad_norm and / or ema: the sum of squares of every group's gradients into consecutive ranges of one
+        buffer, one fold to the norm and the coefficient, then the groups' updates -- all on the current stream."""
+        device = jobs[0][2]
+        if any(j[2] != device for j in jobs):
+            raise IpdmError("HipAdam: max_grad_norm / ema need every param group on one GPU")
+        with torch.cuda.device(device):
+            stream = _lib.current_stream()
+            plans = [self._plan(gi, tuple(columns[4]), device) for gi, _, _, columns, _, _ in jobs]
+            tables = {}
+            for (gi, group, _, columns, launches, _) in jobs:
+                n = len(columns[4])
+                for li, (t, gcol, ecol) in enumerate(launches):
+                    cols = [columns[0], gcol, columns[2], columns[3], columns[4]]
+                    tables[gi, li] = self._table_ex((gi, li), cols, ecol if ecol is not None else [0] * n, device)
+            coef = None
+            if self.max_grad_norm is not None:
+                total = sum(p[3] for p in plans)
+                buf = self._clip_buffers
+                if buf is None or buf[0].device != device or buf[0].numel() < max(1, total):
+                    buf = self._clip_buffers = (torch.zeros(max(1, total), dtype=torch.float64, device=device),
+                                                torch.zeros(1, dtype=torch.float64, device=device),
+                                                torch.zeros(1, dtype=torch.float32, device=device))
+                partials, norm, coef = buf
+                lo = 0
+                for (gi, group, _, columns, launches, _), plan in zip(jobs, plans):
+                    n = len(columns[4])
+                    # the whole group's gradients, each once (launches of several step counts split them between them)
+                    full = tables[gi, 0] if len(launches) == 1 else self._table_ex((gi, "norm"), columns, [0] * n, device)
+                    call("ipdm_grad_sumsq", ptr(full), n, ptr(plan[2]), plan[3], ctypes.c_void_p(partials.data_ptr() + 8 * lo), stream)
+                    lo += plan[3]
+                call("ipdm_grad_clip_coef", ptr(partials), total, self.max_grad_norm, ptr(norm), ptr(coef), stream)
+                self.last_grad_norm = norm
+            for (gi, group, _, columns, launches, _), plan in zip(jobs, plans):
+                n = len(columns[4])
+                beta1, beta2 = group["betas"]
+                for li, (t, gcol, ecol) in enumerate(launches):
+                    table = tables[gi, li]
+                    eptr = ctypes.c_void_p(table.data_ptr() + 40 * n) if (ecol is not None and self._ema is not None) else None
+                    call("ipdm_adam_step_ex", ptr(table), n, ptr(plan[2]), plan[3], float(group["lr"]), float(beta1), float(beta2),
+                         float(group["eps"]), float(group["weight_decay"]), int(t), None if coef is None else ptr(coef), eptr,
+                         0.0 if self.ema_decay is None else self.ema_decay, stream)
+
+    def _step_checked(self, gi, group, params, grads, jobs=None):
         """A step with everything looked at: state made where it is missing, tensors checked, parameters without a gradient
         skipped, one launch per distinct step count.  When it ends with every parameter updated at one common count, the next
-        steps take the short way (step())."""
+        steps take the short way (step()).  jobs: under max_grad_norm / ema the launches are not made here but appended there
+        (the norm is over every group, so the first update comes after the last group was looked at)."""
         self._steady.pop(gi, None)
         device = params[0].device
         cols, steps, keep = ([], [], [], [], []), [], []
@@ -794,9 +890,18 @@ class HipAdam(torch.optim.Optimizer):
                 c.append(x)
             steps.append(count)
         counts = sorted({t for t in steps if t is not None})
-        for t in counts:                              # (one launch unless skipped gradients have left the counts apart)
+        launches = []
+        ecol = self._ema_column(params, device) if self._ema is not None else None
+        for t in counts or ([1] if ecol is not None else []):          # (no gradient at all: the averages still move)
             gcol = cols[1] if len(counts) == 1 else [g if s == t else 0 for g, s in zip(cols[1], steps)]
-            self._launch(gi, group, [cols[0], gcol, cols[2], cols[3], cols[4]], device, t)
+            if jobs is None:                          # (one launch unless skipped gradients have left the counts apart)
+                self._launch(gi, group, [cols[0], gcol, cols[2], cols[3], cols[4]], device, t)
+                continue
+            # an average moves once: in its tensor's own launch, a tensor without a gradient in the first
+            first = not launches
+            launches.append((t, gcol, None if ecol is None else [e if (s == t or (s is None and first)) else 0 for e, s in zip(ecol, steps)]))
+        if jobs is not None and launches:
+            jobs.append((gi, group, device, [list(c) for c in cols], launches, keep))          # (`keep`: alive until the launches are on the stream)
         del keep
         if len(counts) == 1 and None not in steps:
             # from here on the step counts of the group are views of ONE host vector (still a float32 scalar each, as torch lays
@@ -806,6 +911,8 @@ class HipAdam(torch.optim.Optimizer):
                 self.state[p]["step"] = vec[i]
             self._steady[gi] = dict(params=list(params), m=[self.state[p]["exp_avg"] for p in params],
                                     v=[self.state[p]["exp_avg_sq"] for p in params], n=list(cols[4]), steps=vec, t=counts[0], device=device)
+            if ecol is not None:
+                self._steady[gi]["ema"] = ecol
 
 
 def _same(a, b):
@@ -832,10 +939,16 @@ class Trainer:
     """train() of the reference harness (Utils/train_test_utils.py:146-168,253-272) for one domain ("img" or "proj"): the
     network of opt's *_img / *_proj fields (num_res_blocks_<domain> / num_heads_<domain>, when opt has them, override the
     reference's constructor defaults 2 and 4), that domain's GaussianDiffusion, and Adam as the reference builds it:
-    torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip")."""
+    torch.optim.Adam (optim_backend="torch") or HipAdam, the same update as one launch per step ("hip").
+
+    Two opt-in keywords the reference has no counterpart of: max_grad_norm clips the gradients of a step by their global norm
+    (last_grad_norm is then the norm of the last step, a float), ema_decay keeps an exponential moving average of the weights
+    (self.ema, tensors parallel to model.parameters(), started as a copy of the weights).  Under optim_backend="hip" both ride
+    in HipAdam's launches; under "torch" they run as torch.nn.utils.clip_grad_norm_ and torch._foreach_lerp_ (the A/B arm).
+    save_checkpoint then also writes ema_<domain>_model-<epoch>, and sampling_model(ema=True) samples from the average."""
 
     def __init__(self, opt, domain, seed=0, conv_backend="hip", norm_backend="torch", attn_backend="torch", optim_backend="torch",
-                 wgrad_backend="hip", wgrad_wino=False, head_dims="tuned", conv_tuned_all=False):
+                 wgrad_backend="hip", wgrad_wino=False, head_dims="tuned", conv_tuned_all=False, max_grad_norm=None, ema_decay=None):
         from .diffusion import GaussianDiffusion, NoiseSource
         self.head_dims = check_head_dims(head_dims)          # of the TrainUNet's attention cores and of sampling_model()'s UNetModel
         if domain not in ("img", "proj"):
@@ -855,8 +968,21 @@ class Trainer:
                                    conv_tuned_all=conv_tuned_all, **kw).to(self.device)
         self.diffusion = GaussianDiffusion(timesteps=o("timesteps"), beta_schedule="cosine", schedule_power=o("schedule_power"))
         self.partial_timesteps = o("partial_timesteps")
-        adam = HipAdam if optim_backend == "hip" else torch.optim.Adam
-        self.optimizer = adam(self.model.parameters(), lr=getattr(opt, "init_lr", 2e-4), weight_decay=1e-5, betas=(0.9, 0.999))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be None or a positive number, not %r" % (max_grad_norm,))
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must be None or in [0, 1), not %r" % (ema_decay,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema = None if ema_decay is None else [p.detach().clone() for p in self.model.parameters()]
+        self.last_grad_norm = None
+        kw = dict(lr=getattr(opt, "init_lr", 2e-4), weight_decay=1e-5, betas=(0.9, 0.999))
+        if optim_backend == "hip":
+            if self.max_grad_norm is not None or self.ema is not None:             # (without them: the class as it always was)
+                kw.update(max_grad_norm=self.max_grad_norm, ema=self.ema, ema_decay=self.ema_decay)
+            self.optimizer = HipAdam(self.model.parameters(), **kw)
+        else:
+            self.optimizer = torch.optim.Adam(self.model.parameters(), **kw)
         self.noise = NoiseSource(self.seed)
         self._gen = torch.Generator().manual_seed(self.seed)
 
@@ -886,37 +1012,74 @@ class Trainer:
         tt = torch.tensor(ts, dtype=torch.long, device=self.device)
         loss = F.mse_loss(z, self.model(x_t, tt))
         loss.backward()
-        self.optimizer.step()
+        norm = None
+        if self.optim_backend == "hip":
+            self.optimizer.step()
+            norm = self.optimizer.last_grad_norm
+        else:                                          # the A/B arm of the two options: torch's own clipping and lerp
+            if self.max_grad_norm is not None:
+                norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+            self.optimizer.step()
+            if self.ema is not None:
+                with torch.no_grad():
+                    torch._foreach_lerp_(self.ema, [p.detach() for p in self.model.parameters()], 1.0 - self.ema_decay)
         val = float(loss.item())
+        if norm is not None:                           # (behind the synchronisation loss.item() already is)
+            self.last_grad_norm = float(norm.item())
         return (val, (x_t, z, tt)) if record else val
+
+    def ema_state_dict(self):
+        """The averaged weights as a state_dict with the model's keys (the reference's layout), on the host."""
+        if self.ema is None:
+            raise ValueError("this Trainer keeps no EMA (ema_decay is off)")
+        avg = {n: e for (n, _), e in zip(self.model.named_parameters(), self.ema)}
+        return collections.OrderedDict((k, avg.get(k, v).detach().cpu()) for k, v in self.model.state_dict().items())
 
     def save_checkpoint(self, directory, epoch):
         """LoggerX.checkpoints (Utils/loggerx.py:62-67): <directory>/save_models/{img_model,proj_model}-<epoch>, a state_dict;
         progressive_domain_denoiser.load_model reads it (load_*_model_path = directory, resume_epochs_* = epoch).  Beside it
         <directory>/save_models/optimizer-<epoch>, the optimiser's state_dict (torch.optim.Adam's layout under either
-        optim_backend).  Returns the model file."""
+        optim_backend).  With ema_decay also <directory>/save_models/ema_{img,proj}_model-<epoch>, the averaged weights as a
+        state_dict of the same keys.  Returns the model file."""
         d = os.path.join(directory, "save_models")
         os.makedirs(d, exist_ok=True)
         f = os.path.join(d, "%s_model-%d" % (self.domain, int(epoch)))
         torch.save(collections.OrderedDict((k, v.detach().cpu()) for k, v in self.model.state_dict().items()), f)
+        if self.ema is not None:
+            torch.save(self.ema_state_dict(), os.path.join(d, "ema_%s_model-%d" % (self.domain, int(epoch))))
         torch.save(self.optimizer.state_dict(), os.path.join(d, "optimizer-%d" % int(epoch)))
         return f
 
     def load_checkpoint(self, directory, epoch):
         """LoggerX.load_checkpoints (Utils/loggerx.py:71-80) for this trainer: <directory>[/save_models]/<domain>_model-<epoch>
         into the network and optimizer-<epoch> into the optimiser (written under either optim_backend), both through
-        load_network's key clean-up.  A file that does not exist is skipped with a warning, as load_model does."""
+        load_network's key clean-up.  A file that does not exist is skipped with a warning, as load_model does.  With ema_decay
+        the averages come from ema_<domain>_model-<epoch>; without that file (a warning) they restart from the loaded weights."""
         for name, module in (("%s_model" % self.domain, self.model), ("optimizer", self.optimizer)):
             f = checkpoint_file(directory, name, epoch)
             if f is None:
                 warnings.warn("checkpoint %s-%d not found under %s: %s keeps its state" % (name, int(epoch), directory, name), UserWarning)
                 continue
             module.load_state_dict(clean_keys(torch.load(f, map_location="cpu")))
+        if self.ema is not None:
+            name = "ema_%s_model" % self.domain
+            f = checkpoint_file(directory, name, epoch)
+            if f is None:
+                warnings.warn("checkpoint %s-%d not found under %s: the average restarts from the loaded weights"
+                              % (name, int(epoch), directory), UserWarning)
+                src = [p.detach() for p in self.model.parameters()]
+            else:
+                sd = clean_keys(torch.load(f, map_location="cpu"))
+                src = [torch.as_tensor(sd[n]) for n, _ in self.model.named_parameters()]
+            with torch.no_grad():                      # in place: the optimiser holds these tensors
+                for e, x in zip(self.ema, src):
+                    e.copy_(x)
 
-    def sampling_model(self):
-        """A UNetModel (the inference network of this library) loaded with the current weights, on the trainer's device."""
+    def sampling_model(self, ema=False):
+        """A UNetModel (the inference network of this library) loaded with the current weights, on the trainer's device; with
+        ema=True with the averaged weights."""
         m = UNetModel(head_dims=self.head_dims, **self.model.unet_kwargs())
-        m.load_state_dict(self.model.state_dict())
+        m.load_state_dict(self.ema_state_dict() if ema else self.model.state_dict())
         return m.to(self.device)
 
 
@@ -973,10 +1136,16 @@ class progressive_domain_trainer:
     resume_epochs_<domain> > 0 with load_<domain>_model_path loads <domain>_model-<epochs> and optimizer-<epochs> and skips the
     sampler to the reference's resume_iter = resume_epochs * save_freq // batch_size (which is the iteration the checkpoint was
     written at when batch_size == 1, as in the reference's shipped options; init_data_loader(resume_iter=...) names another).
-    Single process: the reference's train() has no gradient all-reduce either.  The reference has no EMA."""
+    Single process: the reference's train() has no gradient all-reduce either.
+
+    The reference has neither gradient clipping nor an EMA of the weights; both are opt-in here.  max_grad_norm > 0 clips every
+    step's gradients by their global norm and logs the norm as train/grad_norm per step; ema_decay in (0, 1) keeps the average,
+    written as ema_<domain>_model-<it> beside every checkpoint and read back on resume; use_ema_weights makes test(it) score
+    the averaged weights.  With the keys at their defaults (0, 0, False) nothing changes."""
 
     def __init__(self, opt, result_save_path=None):
-        from .config import check_attn_head_dims, check_conv_tuned_all, check_train_backends, check_wgrad_backend, check_wgrad_wino
+        from .config import (check_attn_head_dims, check_clip_ema, check_conv_tuned_all, check_train_backends, check_use_ema_weights,
+                             check_wgrad_backend, check_wgrad_wino)
         if opt.mode not in ("train_img", "train_proj"):
             raise ValueError("progressive_domain_trainer runs mode 'train_img' or 'train_proj', not %r (progressive_domain_denoiser "
                              "runs the test_* modes)" % (opt.mode,))
@@ -984,6 +1153,8 @@ class progressive_domain_trainer:
         self.domain = "img" if opt.mode == "train_img" else "proj"
         self.rank = 0
         backends = dict(check_train_backends(opt), **check_wgrad_backend(opt), **check_wgrad_wino(opt), **check_conv_tuned_all(opt))
+        backends.update(check_clip_ema(opt))                       # max_grad_norm / ema_decay: keywords only when they are on
+        self.use_ema_weights = check_use_ema_weights(opt, training=True)
         self.train_seed = int(getattr(opt, "train_seed", 0))
         self.result_save_path = result_save_path
         run = "%s_%s" % (opt.model_name, opt.run_name)
@@ -1081,6 +1252,9 @@ class progressive_domain_trainer:
         loss_temp[0] += loss
         self.losses.append((int(n_iter), loss))
         self.add_scalar("train/loss_step", loss, n_iter, lr=float(lr))
+        grad_norm = getattr(self.trainer, "last_grad_norm", None)
+        if grad_norm is not None:                                  # (clipping is on)
+            self.add_scalar("train/grad_norm", grad_norm, n_iter)
         self.msg(loss, lr, n_iter)
 
     # ---- test() (:274-324) through an inner denoiser of the matching test_* mode
@@ -1089,19 +1263,20 @@ class progressive_domain_trainer:
         topt = copy.deepcopy(self.opt)
         topt.mode = "test_" + self.domain
         topt.resume_epochs_img = topt.resume_epochs_proj = 0       # its network comes from sampling_model(), not from a file
+        topt.use_ema_weights = False                               # (and so do the averaged weights)
         den = progressive_domain_denoiser(topt, result_save_path=None, seed=self.train_seed)
         den._init_evaluation(self.save_root)
         return den
 
     def test(self, epoch):
         """test(it) of the reference in a train_* mode: the test dataset scored with the current weights (the inference network
-        of sampling_model()), metric files under <root>/save_test_results/Save_Iter_<it>, and the psnr / ssim groups of the
+        of sampling_model(); under use_ema_weights the averaged weights, sampling_model(ema=True)), metric files under <root>/save_test_results/Save_Iter_<it>, and the psnr / ssim groups of the
         totals as scalars.  As in the reference the per-sample list is never cleared: the totals of test(it) are over every
         sample scored so far."""
         if self._tester is None:
             self._tester = self._make_tester()
         den = self._tester
-        setattr(den, self.domain + "_model", self.trainer.sampling_model())
+        setattr(den, self.domain + "_model", self.trainer.sampling_model(ema=True) if self.use_ema_weights else self.trainer.sampling_model())
         den.test(epoch)
         for key in den.metric_total.keys():
             group = den.metric_total[key]

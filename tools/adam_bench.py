@@ -12,10 +12,20 @@ that builds them, the kernels) and by two device events around them (the stream'
           parameter = 28; the copy reads 14 and writes 14) -- the bandwidth floor
   copy28  a device-to-device copy of 28 bytes per parameter (twice the update's traffic)
 
-Bytes of the update: 28 per parameter.  Then one whole Trainer.step per network at B = 1 under optim_backend "torch" and "hip"
-(the other backends at the Trainer's defaults), host clock around a step that ends in loss.item().
+The two opt-in legs of the update (clipping by the global norm, an exponential moving average of the weights), same protocol:
+  hip_clip      HipAdam(max_grad_norm=): ipdm_grad_sumsq + ipdm_grad_clip_coef + ipdm_adam_step_ex, 4 + 28 bytes per parameter
+  hip_ema       HipAdam(ema=, ema_decay=): ipdm_adam_step_ex, 36 bytes per parameter
+  hip_both      both: 4 + 36 = 40 bytes per parameter
+  foreach_both  torch.nn.utils.clip_grad_norm_ + torch.optim.Adam + torch._foreach_lerp_ (what Trainer runs under
+                optim_backend="torch"); fused_both the same around Adam(fused=True)
+  copy20        a device-to-device copy of 20 bytes per parameter: the traffic of hip_both -- its bandwidth floor
+The yardstick of the three hip_* arms is plain `hip` of the same process.
 
-    python tools/adam_bench.py --out profiles/r24_adam_bench.json
+Bytes of the update: 28 per parameter.  Then one whole Trainer.step per network at B = 1 under optim_backend "torch" and "hip"
+(the other backends at the Trainer's defaults), host clock around a step that ends in loss.item(); and the same under both
+backends with max_grad_norm and ema_decay on ("torch+clip+ema", "hip+clip+ema").
+
+    python tools/adam_bench.py --out profiles/r38_adam_bench.json
 """
 import argparse
 import json
@@ -32,6 +42,8 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
 from conv_grad_bench import SIZES, network_kwargs, production_opt      # noqa: E402
 
 BYTES_PER_PARAM = 28
+BYTES_EXT = {"hip_clip": 32, "hip_ema": 36, "hip_both": 40}           # the norm pass reads 4, the average adds 4 in and 4 out
+MAX_NORM, EMA_DECAY = 1.0, 0.999
 ADAM = dict(lr=2e-4, weight_decay=1e-5, betas=(0.9, 0.999))           # as the reference builds it
 
 
@@ -88,7 +100,26 @@ def bench_optimiser(opt, domain, rounds, reps):
         arms["fused"] = fused.step
     except Exception as e:                                         # noqa: BLE001 - this torch does not build it here: say so
         notes["fused"] = "not available: %s" % (str(e).splitlines()[0] if str(e) else type(e).__name__)
-    for name, per in (("copy14", 14), ("copy28", 28)):
+    for name, kw in (("hip_clip", dict(max_grad_norm=MAX_NORM)), ("hip_ema", dict(ema=True)), ("hip_both", dict(max_grad_norm=MAX_NORM, ema=True))):
+        params = make_params(shapes, dev, 1)
+        if kw.pop("ema", False):
+            kw.update(ema=[p.detach().clone() for p in params], ema_decay=EMA_DECAY)
+        arms[name] = HipAdam(params, **ADAM, **kw).step
+
+    def torch_both(optim, params):
+        ema, weights = [p.detach().clone() for p in params], [p.detach() for p in params]
+
+        def step():
+            torch.nn.utils.clip_grad_norm_(params, MAX_NORM)
+            optim.step()
+            torch._foreach_lerp_(ema, weights, 1.0 - EMA_DECAY)
+        return step
+    params = make_params(shapes, dev, 1)
+    arms["foreach_both"] = torch_both(torch.optim.Adam(params, **ADAM), params)
+    if "fused" in arms:
+        params = make_params(shapes, dev, 1)
+        arms["fused_both"] = torch_both(torch.optim.Adam(params, fused=True, **ADAM), params)
+    for name, per in (("copy14", 14), ("copy28", 28), ("copy20", 20)):
         src = torch.empty((n_params * per + 3) // 4, dtype=torch.float32, device=dev).normal_()
         dst = torch.empty_like(src)
         arms[name] = (lambda s, d: (lambda: d.copy_(s)))(src, dst)
@@ -107,6 +138,11 @@ def bench_optimiser(opt, domain, rounds, reps):
     out["hip_GBps"] = BYTES_PER_PARAM * n_params / (med["hip"] * 1e-3) / 1e9
     out["copy14_GBps"] = BYTES_PER_PARAM * n_params / (med["copy14"] * 1e-3) / 1e9
     out["ratios_of_host_medians"] = {"hip_over_" + k: med["hip"] / med[k] for k in arms if k != "hip"}
+    out["extended"] = {k: {"bytes_per_parameter": b, "GBps": b * n_params / (med[k] * 1e-3) / 1e9, "over_hip": med[k] / med["hip"],
+                           "over_foreach_both": med[k] / med["foreach_both"],
+                           "over_fused_both": med[k] / med["fused_both"] if "fused_both" in med else None}
+                       for k, b in BYTES_EXT.items()}
+    out["extended"]["hip_both"]["over_copy20"] = med["hip_both"] / med["copy20"]
     f = out["host_ms"]["foreach"]
     out["foreach_spread"] = (f["max_ms"] - f["min_ms"]) / f["median_ms"]
     out["hip_faster_than_foreach_beyond_its_spread"] = bool(out["host_ms"]["hip"]["max_ms"] < f["min_ms"])
@@ -120,7 +156,11 @@ def bench_steps(opt, domain, rounds):
     H, W = SIZES[domain]
     images = torch.rand((1, H, W)) * (4.0 if domain == "proj" else 0.3)
     arms = {b: Trainer(opt, domain, seed=1, optim_backend=b) for b in ("torch", "hip")}
-    arms["hip"].model.load_state_dict(arms["torch"].model.state_dict())
+    for b in ("torch", "hip"):
+        arms[b + "+clip+ema"] = Trainer(opt, domain, seed=1, optim_backend=b, max_grad_norm=MAX_NORM, ema_decay=EMA_DECAY)
+    for b, tr in arms.items():
+        if b != "torch":
+            tr.model.load_state_dict(arms["torch"].model.state_dict())
     z = torch.randn((1, 1, H, W), device=opt.device)
     ms, losses = {b: [] for b in arms}, {b: [] for b in arms}
     for r in range(rounds + 1):                     # round 0: warm-up
@@ -135,6 +175,10 @@ def bench_steps(opt, domain, rounds):
     out = {"size": [H, W], "B": 1, "t": 25, "step_ms": {"optim=" + b: summary(v) for b, v in ms.items()},
            "losses": {"optim=" + b: v for b, v in losses.items()}}
     out["hip_over_torch"] = out["step_ms"]["optim=hip"]["median_ms"] / out["step_ms"]["optim=torch"]["median_ms"]
+    out["hip_clip_ema_over_hip"] = out["step_ms"]["optim=hip+clip+ema"]["median_ms"] / out["step_ms"]["optim=hip"]["median_ms"]
+    out["hip_clip_ema_over_torch_clip_ema"] = (out["step_ms"]["optim=hip+clip+ema"]["median_ms"]
+                                               / out["step_ms"]["optim=torch+clip+ema"]["median_ms"])
+    out["grad_norms"] = {"optim=" + b: tr.last_grad_norm for b, tr in arms.items()}
     return out
 
 
