@@ -103,4 +103,10 @@ def test_isa_equal_pairs_kernels_and_tells_same_code_from_other_code(tmp_path):
     assert r.returncode == 1 and len(lines) == 4 and all("lines differ" in ln for ln in lines), r.stdout[-2000:]
     r = subprocess.run([sys.executable, ISA_EQUAL, built, other, "--kernel", "no_such_kernel"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 1, r.stdout[-2000:]                                                 # nothing compared is not "identical"
+    # --rename rewrites the OLD object's names before pairing: renamed away from the new names nothing pairs, renamed back all four do
+    r = subprocess.run([sys.executable, ISA_EQUAL, built, same, "--rename", "conv_wino2_kernelIL=conv_wino2_formerIL"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 1 and r.stdout.count(": only in") == 8, r.stdout[-2000:]
+    r = subprocess.run([sys.executable, ISA_EQUAL, built, same, "--rename", "conv_wino2_kernelIL=conv_wino2_formerIL", "--rename", "wino2_former=wino2_kernel"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.count(": identical") == 4, r.stdout[-2000:]
 

@@ -2,7 +2,9 @@
 """Are two objects the same device code?  Disassembles every gfx950 kernel of both (as tools/isa_census.py does), drops the
 addresses and the address comments, pairs the kernels by mangled name and compares the instruction text line by line -- the
 instrument of a refactor that must leave a fenced kernel's code alone.
-    python tools/isa_equal.py OLD.o NEW.o [--kernel SUBSTR]
+    python tools/isa_equal.py OLD.o NEW.o [--kernel SUBSTR] [--rename OLD=NEW]...
+--rename (repeatable) replaces the substring OLD by NEW in OLD.o's kernel names before pairing: for a refactor that renames a
+kernel or changes its template parameters.
 Prints per kernel `identical`, or the number of differing lines with the first few; exit 1 on any difference or unpaired kernel."""
 import difflib
 import os
@@ -26,9 +28,16 @@ def main():
         i = args.index("--kernel")
         pat = args[i + 1]
         del args[i:i + 2]
-    if len(args) != 2:
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
+    if len(args) != 2 or any(len(r) != 2 for r in renames):
         sys.exit(__doc__)
     old, new = kernels(args[0], pat), kernels(args[1], pat)
+    for src, dst in renames:
+        old = {name.replace(src, dst): body for name, body in old.items()}
     bad = 0
     if not old and not new:
         print("no kernel matched %r in either object" % pat)
